@@ -2,10 +2,14 @@
 """bench.py -- Msamples/s of the volpath hot path on the metric scene (BASELINE.json: C3, heterogeneous 128^3
 grid + HG, 512x512x1024 spp) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one complete render of the workload with scene (grids) and film resident in HBM.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` then also writes the film(s) of the last
+timed step to DIR (see dump_outputs).  Everything else -- the roofline figures (one extra render with the counting kernel), the CPU
+baseline, the weak-scaling side figure and the N-rank film check -- runs only under `--full`.
 
 STRONG scaling (the headline, `"scaling": "strong"`): every N renders the SAME 512x512x1024 job.  For N > 1 the job is cut
 into N passes of 1024/N spp with the reference's own `samples_per_pass` mechanism (librender/integrator.cpp:58-65), which
@@ -16,7 +20,7 @@ that the reduced film equals the film ONE rank renders of the same job (`"film_c
 
 WEAK scaling (side figure, `"weak"`): 512x512x(1024 N) spp in passes of 1024 spp, one 512x512x1024 job per GPU.
 
-Rank 0 prints ONE JSON line; see DESIGN.md for how `roofline` and `cpu_baseline` are derived.
+Rank 0 prints ONE JSON line; see DESIGN.md for how `roofline` and `cpu_baseline` are derived (both null without `--full`).
 """
 import argparse
 import importlib
@@ -218,6 +222,103 @@ def partition(width, height, spp, n, block=32):
     return {"spp_pass": spp_pass, "passes": passes, "blocks_total": blocks_total, "workgroups_per_rank": per_rank}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(films, out_dir, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs DIR`: what a caller of the timed path receives, the film(s) of the last timed step (H x W x (X, Y, Z, A, W [+ 2 AOV
+    channels per bin])), as float32 `film.npy` -- `film_00.npy` ... when the step renders several scenes (C5's wavelength batches).
+    When the films exceed `limit` bytes in all, every film is cut to the same fixed sample of pixels (seed 0, sorted): N x channels,
+    and `film_pixels.npy` holds their flat indices y * W + x (float64).  Returns the names written."""
+    import numpy as np
+    films = [np.ascontiguousarray(f, dtype=np.float32) for f in films]
+    h, w, c = films[0].shape
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    if sum(f.nbytes for f in films) > limit:
+        keep = min(h * w, limit // (4 * c * len(films) + 8))
+        pixels = np.sort(np.random.default_rng(0).choice(h * w, size=keep, replace=False))
+        films = [f.reshape(h * w, c)[pixels] for f in films]
+        out["film_pixels"] = pixels.astype(np.float64)
+    if len(films) == 1:
+        out["film"] = films[0]
+    else:
+        out.update(("film_%02d" % k, f) for k, f in enumerate(films))
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
+def roofline_figures(torch, job, args, rank, n, local_rank, variant, integ_type, kernel_ms, launches, samples_rank, cal_ms):
+    """`--full` only: the roofline record of the line (one extra render with the counting kernel variant)."""
+    # ---- roofline of the dominant kernel: algorithmic bytes / measured launch duration (SURVEY.md 8(d) convention).
+    # Counters come from one extra, untimed render with the counting kernel variant; they are deterministic and equal the
+    # oracle's at the same seed (tests/test_gpu_parity.py).
+    cs = job.render(rank, n, collect_counters=True)
+    c_iter, c_look, c_nee, c_samp = (sum(s[k] for s in cs) for k in ("n_iter", "n_lookup", "n_nee_step", "samples"))
+    bytes_per_sample = (224.0 * c_iter + 64.0 * c_look + 128.0 * c_nee) / c_samp + 40.0
+    avg_launch_ms = kernel_ms / max(launches, 1)
+    bytes_per_launch = bytes_per_sample * samples_rank * (args.steps / max(launches, 1))
+    achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9
+    kv = os.environ.get("MTSAMD_KERNEL", "wga1024")
+    if integ_type == "path" and kv != "nested":
+        kernel_name = ("v_spectral::" if variant == "gpu_spectral" else "") + "render_kernel<false, true, 0>"      # path_pixel_flat: one flat loop with regeneration
+    elif integ_type == "path" or kv == "nested":
+        kernel_name = "render_kernel<false, false, %d>" % {"path": 0, "volpath": 1, "volpathmis": 2}.get(integ_type, 0)
+    elif kv == "flat" and integ_type == "volpath":
+        kernel_name = "render_kernel<false, true, 1>"
+    elif integ_type == "volpathmis":
+        kernel_name = "v_spectral::render_kernel_wga_mis<false, true, 256, 256>" if args.config == "C5SM" else "render_kernel_wga_mis<false, true, 512, 512>"
+    elif args.config in ("C5S", "C5SB"):
+        kernel_name = "v_spectral::render_kernel_wga<false, 256, 256, 2, false>"
+    else:
+        paths = int(kv[3:]); nt = int(os.environ.get("MTSAMD_WG_THREADS", str(paths)))
+        kernel_name = "render_kernel_%s<false, %d, %d, %d%s>" % (kv[:3], paths, nt, {1: 4, 0.75: 3, 0.5: 2}[nt / paths], ", false" if kv[:3] == "wga" else "")
+    # a scene that keeps the promises of a lean translation unit runs that unit's copy of the kernel (mts_stats.kernel_variant + 100000 / 200000)
+    lean = {1: "v_rgb_lean_a::", 2: "v_rgb_lean_b::", 3: "v_spectral_lean::", 4: "v_rgb_lean_p::", 5: "v_spectral_lean_p::", 6: "v_rgb_lean_h::", 7: "v_rgb_lean_c::"}.get(getattr(job, "kernel_variant", 0) // 100000, "")
+    if lean:
+        kernel_name = lean + kernel_name.replace("v_spectral::", "")
+        if lean == "v_spectral_lean::":
+            kernel_name = kernel_name.replace("render_kernel_wga<false, 256, 256, 2, false>", "render_kernel_wga<false, 256, 256, 3, false>")       # budget of three waves per SIMD
+        if lean == "v_rgb_lean_a::":
+            kernel_name = kernel_name.replace("render_kernel_wga_mis<false, true, 512, 512>", "render_kernel_wga_mis<false, true, 512, 768>")   # three waves per SIMD
+    # `achieved` / `frac` follow the contract: ALGORITHMIC bytes (a wavefront formulation's state round trips, SURVEY.md 8(d)) over
+    # the kernel's measured time.  This kernel keeps path state in LDS, so its real HBM traffic is several times lower and its
+    # bound is latency at 4 waves per SIMD; `traffic*` and `valu_pipe_busy` (rocprofv3 --pmc, profiles/) say so whenever this run
+    # matches the profiled configuration.
+    # `bound`: what the counters say limits this kernel (rocprofv3 --pmc, profiles/: latency at 4 waves per SIMD, vector pipes half busy, HBM
+    # at ~15 % of peak).  `achieved` / `peak` / `frac` stay the contract's HBM-roofline figure, which is a MODEL here (`model_bound`):
+    # the algorithmic bytes of a wavefront formulation that round-trips path state through HBM, over the measured launch time.
+    roofline = {"bound": "latency", "model_bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                "achieved_is": "algorithmic bytes per launch / measured launch time (SURVEY.md 8(d)): a modelling figure, not a bandwidth measurement",
+                "kernel": kernel_name, "avg_launch_ms": round(avg_launch_ms, 3), "launches_per_step": round(launches / args.steps, 3),
+                "calibration_ms_per_step": round(cal_ms / args.steps, 3),
+                "peak_source": "MI355X HBM3E peak (8 TB/s)", "peak_device_query": device_hbm_peak_gbs(torch, local_rank),
+                "bytes_per_sample": round(bytes_per_sample, 1),
+                "n_iter_per_sample": round(c_iter / c_samp, 3),
+                "n_lookup_per_sample": round(c_look / c_samp, 3),
+                "n_nee_step_per_sample": round(c_nee / c_samp, 3)}
+    this_run = {"config": args.config, "width": args.width, "height": args.height, "spp": args.spp, "res": args.res, "n_gpus": n, "kernel": kernel_name}
+    for fname in ("traffic_bytes_per_launch.json",):
+        path = os.path.join(ROOT, "profiles", fname)
+        try:
+            prof = json.load(open(path))
+        except Exception:
+            continue
+        if prof.get("run") == this_run:                          # counters describe THIS configuration and kernel only
+            roofline["traffic"] = prof.get("bytes_per_launch")
+            roofline["traffic_source"] = "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this configuration; not measured in this run)" % fname
+            roofline["traffic_gbs"] = round(prof["bytes_per_launch"] / (avg_launch_ms * 1e-3) / 1e9, 1)
+            roofline["traffic_frac_of_peak"] = round(roofline["traffic_gbs"] / HBM_PEAK_GBS, 4)
+            dv = prof.get("derived") or {}
+            if "valu_pipe_busy" in dv:
+                roofline["valu_pipe_busy"] = dv["valu_pipe_busy"]
+                roofline["real_bound"] = ("latency at 4 waves per SIMD: vector pipes %.0f %% busy, a wave waits %.0f %% of its time in s_waitcnt, "
+                                          "HBM at %.0f %% of peak" % (100 * dv["valu_pipe_busy"], 100 * dv.get("wave_wait_share", 0.0), 100 * roofline["traffic_frac_of_peak"]))
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -233,7 +334,13 @@ def main():
     ap.add_argument("--no-weak", action="store_true", help="skip the weak-scaling side measurement (N > 1)")
     ap.add_argument("--no-film-check", action="store_true", help="skip the N-rank == 1-rank film check (N > 1)")
     ap.add_argument("--cpu-spp", type=int, default=0, help="spp of the bounded CPU-baseline sample (0 = sized for ~15 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side figures and checks: roofline (an extra counting render), CPU baseline, weak scaling and film check (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film(s) of the last timed step to DIR as float32 .npy (at most 64 MB: a fixed pixel sample beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))                  # `python bench.py --gpus N`: start the N ranks ourselves
@@ -306,6 +413,8 @@ def main():
     if (args.width, args.height, args.spp) == CONFIG_SIZES[args.config] and args.config not in ("C1", "C1W") and workgroups_per_rank < 256:
         raise SystemExit("bench.py: %d workgroups per rank (< 256 CUs) at --gpus %d" % (workgroups_per_rank, n))
     elapsed, kernel_ms, launches, samples_rank, cal_ms = timed(job, args.steps, args.warmup, barrier, all_max)
+    if args.dump_outputs and rank == 0:                           # before anything else renders into the films (film check, counters)
+        dump_outputs([f.cpu().numpy() for f in job.films], args.dump_outputs)
     value = job.samples_step * args.steps / elapsed / 1e6
     # kernel time per step of every rank (HIP events around the launches): a SCALE record shows load imbalance directly
     per_rank_ms = [kernel_ms / args.steps]
@@ -316,7 +425,7 @@ def main():
         per_rank_ms = [float(g.item()) for g in gathered]
 
     film_check = None
-    if n > 1 and not args.no_film_check:
+    if args.full and n > 1 and not args.no_film_check:
         # the reduced film of the N ranks against the film ONE rank renders of the same job with the same samples_per_pass.  Box
         # filter: every film entry is the sum of the same per-pass values; only the order of those <= N additions differs.
         reduced = [f.clone() for f in job.films]
@@ -328,76 +437,12 @@ def main():
         if rank == 0 and not film_check["ok"]:
             raise SystemExit("bench.py: the %d-rank film differs from the 1-rank film (max rel %.3g)" % (n, film_check["max_rel_diff"]))
 
-    # ---- roofline of the dominant kernel: algorithmic bytes / measured launch duration (SURVEY.md 8(d) convention).
-    # Counters come from one extra, untimed render with the counting kernel variant; they are deterministic and equal the
-    # oracle's at the same seed (tests/test_gpu_parity.py).
-    cs = job.render(rank, n, collect_counters=True)
-    c_iter, c_look, c_nee, c_samp = (sum(s[k] for s in cs) for k in ("n_iter", "n_lookup", "n_nee_step", "samples"))
-    bytes_per_sample = (224.0 * c_iter + 64.0 * c_look + 128.0 * c_nee) / c_samp + 40.0
-    avg_launch_ms = kernel_ms / max(launches, 1)
-    bytes_per_launch = bytes_per_sample * samples_rank * (args.steps / max(launches, 1))
-    achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9
     integ_type = (job.dicts[0]["integrator"].get("integrator") or job.dicts[0]["integrator"])["type"]
-    kv = os.environ.get("MTSAMD_KERNEL", "wga1024")
-    if integ_type == "path" and kv != "nested":
-        kernel_name = ("v_spectral::" if variant == "gpu_spectral" else "") + "render_kernel<false, true, 0>"      # path_pixel_flat: one flat loop with regeneration
-    elif integ_type == "path" or kv == "nested":
-        kernel_name = "render_kernel<false, false, %d>" % {"path": 0, "volpath": 1, "volpathmis": 2}.get(integ_type, 0)
-    elif kv == "flat" and integ_type == "volpath":
-        kernel_name = "render_kernel<false, true, 1>"
-    elif integ_type == "volpathmis":
-        kernel_name = "v_spectral::render_kernel_wga_mis<false, true, 256, 256>" if args.config == "C5SM" else "render_kernel_wga_mis<false, true, 512, 512>"
-    elif args.config in ("C5S", "C5SB"):
-        kernel_name = "v_spectral::render_kernel_wga<false, 256, 256, 2, false>"
-    else:
-        paths = int(kv[3:]); nt = int(os.environ.get("MTSAMD_WG_THREADS", str(paths)))
-        kernel_name = "render_kernel_%s<false, %d, %d, %d%s>" % (kv[:3], paths, nt, {1: 4, 0.75: 3, 0.5: 2}[nt / paths], ", false" if kv[:3] == "wga" else "")
-    # a scene that keeps the promises of a lean translation unit runs that unit's copy of the kernel (mts_stats.kernel_variant + 100000 / 200000)
-    lean = {1: "v_rgb_lean_a::", 2: "v_rgb_lean_b::", 3: "v_spectral_lean::", 4: "v_rgb_lean_p::", 5: "v_spectral_lean_p::", 6: "v_rgb_lean_h::", 7: "v_rgb_lean_c::"}.get(getattr(job, "kernel_variant", 0) // 100000, "")
-    if lean:
-        kernel_name = lean + kernel_name.replace("v_spectral::", "")
-        if lean == "v_spectral_lean::":
-            kernel_name = kernel_name.replace("render_kernel_wga<false, 256, 256, 2, false>", "render_kernel_wga<false, 256, 256, 3, false>")       # budget of three waves per SIMD
-        if lean == "v_rgb_lean_a::":
-            kernel_name = kernel_name.replace("render_kernel_wga_mis<false, true, 512, 512>", "render_kernel_wga_mis<false, true, 512, 768>")   # three waves per SIMD
-    # `achieved` / `frac` follow the contract: ALGORITHMIC bytes (a wavefront formulation's state round trips) over
-    # the kernel's measured time.  This kernel keeps path state in LDS, so its real HBM traffic is several times lower and its
-    # bound is latency at 4 waves per SIMD; `traffic*` and `valu_pipe_busy` (rocprofv3 --pmc, profiles/) say so whenever this run
-    # matches the profiled configuration.
-    # `bound`: what the counters say limits this kernel (rocprofv3 --pmc, profiles/: latency at 4 waves per SIMD, vector pipes half busy, HBM
-    # at ~15 % of peak).  `achieved` / `peak` / `frac` stay the contract's HBM-roofline figure, which is a MODEL here (`model_bound`):
-    # the algorithmic bytes of a wavefront formulation that round-trips path state through HBM, over the measured launch time.
-    roofline = {"bound": "latency", "model_bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                "achieved_is": "algorithmic bytes per launch / measured launch time (SURVEY.md 8(d)): a modelling figure, not a bandwidth measurement",
-                "kernel": kernel_name, "avg_launch_ms": round(avg_launch_ms, 3), "launches_per_step": round(launches / args.steps, 3),
-                "calibration_ms_per_step": round(cal_ms / args.steps, 3),
-                "peak_source": "MI355X_MICROARCH.md (HBM3E, 8 TB/s)", "peak_device_query": device_hbm_peak_gbs(torch, local_rank),
-                "bytes_per_sample": round(bytes_per_sample, 1),
-                "n_iter_per_sample": round(c_iter / c_samp, 3),
-                "n_lookup_per_sample": round(c_look / c_samp, 3),
-                "n_nee_step_per_sample": round(c_nee / c_samp, 3)}
-    this_run = {"config": args.config, "width": args.width, "height": args.height, "spp": args.spp, "res": args.res, "n_gpus": n, "kernel": kernel_name}
-    for fname in ("traffic_bytes_per_launch.json",):
-        path = os.path.join(ROOT, "profiles", fname)
-        try:
-            prof = json.load(open(path))
-        except Exception:
-            continue
-        if prof.get("run") == this_run:                          # counters describe THIS configuration and kernel only
-            roofline["traffic"] = prof.get("bytes_per_launch")
-            roofline["traffic_source"] = "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this configuration; not measured in this run)" % fname
-            roofline["traffic_gbs"] = round(prof["bytes_per_launch"] / (avg_launch_ms * 1e-3) / 1e9, 1)
-            roofline["traffic_frac_of_peak"] = round(roofline["traffic_gbs"] / HBM_PEAK_GBS, 4)
-            dv = prof.get("derived") or {}
-            if "valu_pipe_busy" in dv:
-                roofline["valu_pipe_busy"] = dv["valu_pipe_busy"]
-                roofline["real_bound"] = ("latency at 4 waves per SIMD: vector pipes %.0f %% busy, a wave waits %.0f %% of its time in s_waitcnt, "
-                                          "HBM at %.0f %% of peak" % (100 * dv["valu_pipe_busy"], 100 * dv.get("wave_wait_share", 0.0), 100 * roofline["traffic_frac_of_peak"]))
+    roofline = roofline_figures(torch, job, args, rank, n, local_rank, variant, integ_type, kernel_ms, launches, samples_rank, cal_ms) if args.full else None
 
     # ---- weak scaling side figure (N > 1): one 512x512x1024 job per GPU
     weak = None
-    if n > 1 and not args.no_weak:
+    if args.full and n > 1 and not args.no_weak:
         del job
         torch.cuda.empty_cache()
         wjob = Job(pkg, scenes, args, rank, n, local_rank, backend, args.spp * n, args.spp)
@@ -407,7 +452,7 @@ def main():
         del wjob
 
     cpu_baseline = None
-    if rank == 0 and n == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n == 1 and not args.no_cpu_baseline:
         # the oracle (CPU restatement of scalar_rgb) on all host cores, on a bounded sample of the same workload
         import tests.oracle_binding as ob
         cores = os.cpu_count() or 1

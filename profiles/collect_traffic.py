@@ -1,5 +1,5 @@
 """Reduce the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE -- they do not fit one pass on gfx950)
-of `python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline [...]` into a traffic record.
+of `python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline [...]` into a traffic record (`--full`: the line's roofline names the kernel).
 
 usage: python profiles/collect_traffic.py <fetch_pass_dir> <write_pass_dir> <out.json> <bench_log_of_one_pass> [pmc_summary.json]
 

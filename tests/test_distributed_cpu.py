@@ -138,3 +138,25 @@ def test_bench_fails_when_a_rank_fails():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 3 and "rank 1 exited with status 3" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs`: the film(s) of the last step as float32 .npy; beyond the size limit, the same seeded pixel sample for
+    every film and every run, within the limit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    film = rng.random((6, 10, 5))
+    assert bench.dump_outputs([film], str(tmp_path / "one")) == ["film"]
+    one = np.load(tmp_path / "one" / "film.npy")
+    assert one.dtype == np.float32 and np.array_equal(one, film.astype(np.float32))
+    films = [rng.random((6, 10, 7)).astype(np.float32) for _ in range(3)]
+    limit = 3 * 7 * 4 * 20 + 8 * 20                                           # room for 20 of the 60 pixels
+    for d in ("a", "b"):
+        assert bench.dump_outputs(films, str(tmp_path / d), limit=limit) == ["film_00", "film_01", "film_02", "film_pixels"]
+    pixels = np.load(tmp_path / "a" / "film_pixels.npy")
+    assert pixels.dtype == np.float64 and len(pixels) == 20 and np.all(np.diff(pixels) > 0)
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= limit      # 128: the .npy header
+    for k, f in enumerate(films):
+        a, b = np.load(tmp_path / "a" / ("film_%02d.npy" % k)), np.load(tmp_path / "b" / ("film_%02d.npy" % k))
+        assert np.array_equal(a, b) and np.array_equal(a, f.reshape(60, 7)[pixels.astype(np.int64)])

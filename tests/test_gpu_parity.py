@@ -205,7 +205,7 @@ def test_bench_strong_scaling_rehearsal(gpu_rgb, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MTSAMD_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--width", "128", "--height", "96", "--spp", "64", "--res", "16"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--width", "128", "--height", "96", "--spp", "64", "--res", "16", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -217,7 +217,7 @@ def test_bench_strong_scaling_rehearsal(gpu_rgb, tmp_path):
     # (round 4; rounds 1-3 exited with "must be launched with torch.distributed.run")
     env_plain = {k: v for k, v in env.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     cmd4 = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-            "--config", "C4", "--width", "128", "--height", "96", "--spp", "32", "--no-weak"]
+            "--config", "C4", "--width", "128", "--height", "96", "--spp", "32", "--no-weak", "--full"]
     out = subprocess.run(cmd4, env=env_plain, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -227,7 +227,7 @@ def test_bench_strong_scaling_rehearsal(gpu_rgb, tmp_path):
     assert line4["workgroups_per_rank_per_launch"] == 12 and line4["kernel_ms_per_step"]["max_over_min"] < 3.0
     # four ranks the same way (4 passes x 12 blocks of the metric scene in miniature; at most 6 processes may share the card)
     cmd8 = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0",
-            "--width", "128", "--height", "96", "--spp", "64", "--res", "16", "--no-weak"]
+            "--width", "128", "--height", "96", "--spp", "64", "--res", "16", "--no-weak", "--full"]
     out = subprocess.run(cmd8, env=env_plain, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line8 = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -239,6 +239,31 @@ def test_bench_strong_scaling_rehearsal(gpu_rgb, tmp_path):
     parts = [gpu_render(gpu_rgb, d, shard_index=i, shard_count=2) for i in range(2)]
     assert parts[0][1]["samples"] == parts[1][1]["samples"] == st["samples"] // 2      # 12 (pass, block) pairs each
     assert np.allclose(parts[0][0] + parts[1][0], full, rtol=1e-6, atol=0)
+
+
+def test_bench_plain_run_dumps_the_last_step(gpu_rgb, tmp_path):
+    """A plain `bench.py` run times its steps and nothing else (roofline and CPU baseline only under --full); `--dump-outputs` writes
+    the film of the last timed step, which is the film one render of the same scene gives."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--width", "64", "--height", "48", "--spp", "16", "--res", "16", "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    assert sorted(os.listdir(tmp_path / "out")) == ["film.npy"]
+    film = np.load(tmp_path / "out" / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (48, 64, 5)
+    ref, _ = gpu_render(gpu_rgb, bench.build_scene_dict(scenes, "C3", 64, 48, 16, -1, 16))
+    assert np.allclose(film, ref, rtol=1e-6, atol=0)
 
 
 def test_pm_rcp_is_the_division_for_every_argument(gpu_rgb, tmp_path):
