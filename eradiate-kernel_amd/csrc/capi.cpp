@@ -218,6 +218,76 @@ int mts_sigint_scope_exit(void) {
     return 0;
 }
 
+#if !defined(MTSAMD_HOST_ONLY)
+// The render kernel of a scene, the one place that reads MTSAMD_KERNEL and MTSAMD_LEAN.  mts_stats.kernel_variant = variant + 100000 * unit.
+// variant: 0 = nested per lane, 1 = flat per lane, 10000 + P = the regrouping machine with P paths per workgroup.
+// unit: 0 = the general kernels (kernels.hip, kernels_spectral.hip), else the lean translation unit of RENDER_LAUNCHERS: the regrouping
+// machines of `volpath` and `volpathmis` (or `path`'s flat loop) compiled WITHOUT what this scene cannot contain (integrator_dev.h:
+// MTS_TRAITS) -- the leanest unit whose promises the scene keeps.
+struct KernelChoice { int variant, unit; };
+static KernelChoice choose_kernel(const HostScene &hs, uint32_t block_size) {
+    const DSensor &se = hs.scene.sensor;
+    const bool path = hs.integrator.type == MTS_INTEGRATOR_PATH, vol = hs.integrator.type == MTS_INTEGRATOR_VOLPATH;
+    const bool mis = hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS, spectral = hs.integrator.spectral;
+    // MTSAMD_KERNEL = nested | flat | wga256 | wga1024 (default: asynchronous regrouping, 1024 paths served by 1024 threads)
+    int variant = 11024;
+    if (const char *kv = getenv("MTSAMD_KERNEL")) {
+        if (!strcmp(kv, "nested")) variant = 0; else if (!strcmp(kv, "flat")) variant = 1;
+        else if (!strcmp(kv, "wga256")) variant = 10256; else if (!strcmp(kv, "wga1024")) variant = 11024;
+        else throw std::runtime_error("MTSAMD_KERNEL must be one of nested, flat, wga256, wga1024");
+    }
+    // without media there are no tracking walks to regroup: the per-lane kernels win (cornell box 512 x 512 x 256, volpath: rings 992,
+    // per lane 1242 Msamples/s; `path` per lane: 2342, as one flat loop with regeneration 2910)
+    else if (hs.media.empty() && !path) variant = 0;
+    if (path) variant = variant != 0 ? 1 : 0;                   // per lane: flat loop with regeneration (every variant), or nested (MTSAMD_KERNEL=nested)
+    if (variant >= 10000) {                                     // variant = 10000 + paths per workgroup
+        uint32_t wg = (uint32_t) (variant - 10000);
+        if (mis) wg = std::min(wg, 512u);                       // four weight matrices per path: 512 paths fill the LDS
+        if (spectral) wg = std::min(wg, 256u);                  // four-wide spectra: 42 hot dwords per path; three 256-path workgroups per CU (12 waves) beat one of 512 (8 waves) by 10 %
+        // a workgroup of the regrouping kernels sits in ONE spiral block: blocks smaller than its path count get the largest
+        // workgroup that divides them (16 x 16 -> 256 paths); only blocks below 256 pixels fall back to the per-lane kernel
+        while (wg > 256 && (block_size * block_size) % wg != 0) wg /= 2;
+        variant = (block_size * block_size) % wg != 0 ? 1 : 10000 + (int) wg;
+    }
+    if (spectral && variant == 1 && !path) variant = 0;         // the spectral build's per-lane flat kernel is `path`'s
+    // AOV channels (nbins / bins) and a sensor response function: `volpath` and (round 4) `volpathmis` carry them on the regrouping
+    // machines (their NEW blocks) and `path` in its flat loop (kernels.hip: path_pixel_flat); a discrete response function with repeated
+    // wavelengths keeps the volumetric integrators per lane
+    if ((hs.scene.bin_count > 0 || hs.scene.srf >= 0) && !(variant == 1 && path) && !(variant >= 10000 && !path && hs.srf_lookup_by_wavelength)) variant = 0;
+    // Wavefront (gpu_*) streams carry their own PCG32 increment per (pixel, sample).  The regrouping machine of rgb / mono `volpath` keeps
+    // only the generator's 64-bit state in LDS and recomputes the increment on every load (round 4: wg_block's WF instantiation, 1024-path
+    // workgroups); everything else runs per lane, where the generator lives in registers: `volpath` as the flat state machine, the
+    // others nested
+    if (se.wavefront && variant >= 10000 && !(variant == 11024 && vol && !spectral)) variant = vol && !spectral ? 1 : 0;
+    int unit = 0;
+#if !defined(MTSAMD_BLOCKSTATS)                                 // the diagnostic build compiles no lean unit
+    const char *lv = getenv("MTSAMD_LEAN");                     // 0: never a lean unit; 2: the b unit on a scene that qualifies for a
+    if (!(lv && atoi(lv) == 0)) {
+        auto keeps = [&](int promises) { return (hs.traits & promises) == promises; };      // dscene.h: MT_UNIT_*
+        const bool spec_mis = mis && hs.integrator.use_spectral_mis;
+        const bool machine = spectral ? (variant == 10256 && (vol || spec_mis)) : ((variant == 11024 && vol) || (variant == 10512 && spec_mis));
+        if (machine && !se.wavefront) {
+            if (spectral) { if (keeps(MT_UNIT_B)) unit = 3; }                // kernels_lean_s.hip
+            else if (keeps(MT_UNIT_A)) unit = lv && atoi(lv) == 2 ? 2 : 1;  // every promise: no call left
+            else if (keeps(MT_UNIT_B)) unit = 2;                             // rpv and grids behind volume_eval() allowed
+            else if (keeps(MT_UNIT_C)) unit = 7;                             // ... and a BVH
+            else if (keeps(MT_UNIT_H)) unit = 6;                             // homogeneous media
+        }
+        // `path` as the flat loop: kernels_lean_p.hip / _ps.hip want a walked primitive list, no spheres, no rpv
+        if (variant == 1 && path && keeps(MT_UNIT_P_NEEDS)) unit = spectral ? 5 : 4;
+    }
+#endif
+    return { variant, unit };
+}
+// the launcher of each unit number (unit 0: launch_render, or launch_render_spectral for a scene of the spectral variant)
+#if defined(MTSAMD_BLOCKSTATS)
+static const RenderLauncher RENDER_LAUNCHERS[1] = { launch_render };
+#else
+static const RenderLauncher RENDER_LAUNCHERS[8] = { launch_render, launch_render_lean_a, launch_render_lean_b, launch_render_lean_s,
+                                                    launch_render_lean_p, launch_render_lean_ps, launch_render_lean_h, launch_render_lean_c };
+#endif
+#endif
+
 int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_stats *stats) {
     API_TRY
     if (!scene || !film) throw std::runtime_error("mts_render: NULL argument");
@@ -340,67 +410,10 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
                                      ", workgroup " + std::to_string(c[9]) + ")");
     };
     try {
-        // ---- kernel variant: MTSAMD_KERNEL = nested | flat | wga256 | wga512 | wga1024 (default) | wgl1024
-        int variant = 11024;                                       // asynchronous regrouping, 1024 paths served by 1024 threads
-        if (const char *kv = getenv("MTSAMD_KERNEL")) {
-            if (!strcmp(kv, "nested")) variant = 0; else if (!strcmp(kv, "flat")) variant = 1;
-            else if (!strcmp(kv, "wga256")) variant = 10256; else if (!strcmp(kv, "wga512")) variant = 10512; else if (!strcmp(kv, "wga1024")) variant = 11024;
-            else if (!strcmp(kv, "wgl1024")) variant = 21024;
-            else throw std::runtime_error("MTSAMD_KERNEL must be one of nested, flat, wga256, wga512, wga1024, wgl1024");
-        }
-        // without media there are no tracking walks to regroup: the per-lane kernels win (cornell box 512 x 512 x 256, volpath: rings 992,
-        // per lane 1242 Msamples/s; `path` per lane: 2342, as one flat loop with regeneration 2910)
-        if (!getenv("MTSAMD_KERNEL") && hs.media.empty() && hs.integrator.type != MTS_INTEGRATOR_PATH) variant = 0;
-        if (hs.integrator.type == MTS_INTEGRATOR_PATH) variant = variant != 0 ? 1 : 0;   // per lane: flat loop with regeneration (every variant), or nested (MTSAMD_KERNEL=nested)
-        // variant = family * 10000 + paths per workgroup (family 1: ring driver, 2: lane-affine driver)
-        if (variant >= 10000) {
-            int family = variant / 10000, wg = variant % 10000;
-            if (hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS) { family = 1; wg = std::min(wg, 512); }   // four weight matrices per path: 512 paths fill the LDS
-            if (hs.integrator.spectral) { family = 1; wg = std::min(wg, 256); }   // four-wide spectra: 42 hot dwords per path; three 256-path workgroups per CU (12 waves) beat one of 512 (8 waves) by 10 %
-            // a workgroup of the regrouping kernels sits in ONE spiral block: blocks smaller than its path count get the largest
-            // workgroup that divides them (16 x 16 -> 256 paths); only blocks below 256 pixels fall back to the per-lane kernel
-            while (wg > 256 && (block_size * block_size) % (uint32_t) wg != 0) wg /= 2;
-            if (wg != 1024) family = 1;                           // the lane-affine driver is built for 1024 paths only
-            variant = (block_size * block_size) % (uint32_t) wg != 0 ? 1 : family * 10000 + wg;
-        }
-        if (hs.integrator.spectral && variant == 1 && hs.integrator.type != MTS_INTEGRATOR_PATH) variant = 0;   // the spectral build's per-lane flat kernel is `path`'s
-        // AOV channels (nbins / bins) and a sensor response function: `volpath` and (round 4) `volpathmis` carry them on the regrouping
-        // machines (their NEW blocks) and `path` in its flat loop (kernels.hip: path_pixel_flat); a discrete response function with repeated
-        // wavelengths keeps the volumetric integrators per lane
-        if ((hs.scene.bin_count > 0 || hs.scene.srf >= 0) && !(variant == 1 && hs.integrator.type == MTS_INTEGRATOR_PATH) &&
-            !(variant >= 10000 && hs.integrator.type != MTS_INTEGRATOR_PATH && hs.srf_lookup_by_wavelength)) variant = 0;
-        // Wavefront (gpu_*) streams carry their own PCG32 increment per (pixel, sample).  The regrouping machine of rgb / mono `volpath` keeps
-        // only the generator's 64-bit state in LDS and recomputes the increment on every load (round 4: wg_block's WF instantiation, 1024-path
-        // workgroups); everything else runs per lane, where the generator lives in registers: `volpath` as the flat state machine, the
-        // others nested
-        if (se.wavefront && variant >= 10000 &&
-            !(variant == 11024 && hs.integrator.type == MTS_INTEGRATOR_VOLPATH && !hs.integrator.spectral && !getenv("MTSAMD_WG_THREADS")))
-            variant = (hs.integrator.type == MTS_INTEGRATOR_VOLPATH && !hs.integrator.spectral) ? 1 : 0;
-        int wg_threads = 0;                                         // MTSAMD_WG_THREADS: threads per workgroup of the wga kernels (<= paths; default = paths)
-        if (const char *tv = getenv("MTSAMD_WG_THREADS")) wg_threads = atoi(tv);
-        // Lean kernels (kernels_lean_a.hip / _b.hip: the regrouping machines of rgb / mono `volpath` and `volpathmis` compiled WITHOUT what
-        // this scene cannot contain, integrator_dev.h: MTS_TRAITS): the leanest unit whose promises the scene keeps.  MTSAMD_LEAN=0: never.
-        // mts_stats.kernel_variant reports it as + 100000 (a) / + 200000 (b) / + 300000 (s: the spectral variant's unit) / + 400000, + 500000 (`path`: p, ps) / + 600000 (h: homogeneous media) / + 700000 (c: as b, with a BVH).
-        int lean = 0;
-#if !defined(MTSAMD_BLOCKSTATS)
-        {
-            const char *lv = getenv("MTSAMD_LEAN");
-            const bool mis = hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS && hs.integrator.use_spectral_mis, vol = hs.integrator.type == MTS_INTEGRATOR_VOLPATH;
-            const bool machine = hs.integrator.spectral ? (variant == 10256 && (vol || mis)) : ((variant == 11024 && vol) || (variant == 10512 && mis));
-            if (!(lv && atoi(lv) == 0) && machine && !se.wavefront && wg_threads == 0) {
-                auto keeps = [&](int promises) { return (hs.traits & promises) == promises; };      // dscene.h: MT_UNIT_*
-                if (hs.integrator.spectral) { if (keeps(MT_UNIT_B)) lean = 3; }     // kernels_lean_s.hip
-                else if (keeps(MT_UNIT_A)) lean = 1;                                 // every promise: no call left
-                else if (keeps(MT_UNIT_B)) lean = 2;                                 // rpv and grids behind volume_eval() allowed
-                else if (keeps(MT_UNIT_C)) lean = 7;                                 // ... and a BVH
-                else if (keeps(MT_UNIT_H)) lean = 6;                                 // homogeneous media
-                if (lv && atoi(lv) == 2 && lean == 1) lean = 2;                     // diagnostics: the b unit on a scene that qualifies for a
-            }
-            // `path` as the flat loop: kernels_lean_p.hip / _ps.hip want a walked primitive list, no spheres, no rpv
-            if (!(lv && atoi(lv) == 0) && variant == 1 && hs.integrator.type == MTS_INTEGRATOR_PATH && (hs.traits & MT_UNIT_P_NEEDS) == MT_UNIT_P_NEEDS) lean = hs.integrator.spectral ? 5 : 4;
-        }
-#endif
-        last_variant = variant + 100000 * lean;
+        const KernelChoice kc = choose_kernel(hs, block_size);
+        const int variant = kc.variant;
+        last_variant = variant + 100000 * kc.unit;
+        const RenderLauncher launcher = kc.unit == 0 && hs.integrator.spectral ? launch_render_spectral : RENDER_LAUNCHERS[kc.unit];
 
         // one launch over `blocks` with `spp` samples per pixel, watched for cancel() / the timeout (which reach the kernel through the stop word).
         // `tiles`: the cost-sorted tile table of the regrouping kernels (volpath_flat.h, WgArgs::tiles), or empty: one workgroup per
@@ -418,14 +431,9 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
             // one 128-byte cold record per path in flight; volpathmis parks the path's two weight matrices in a second one (volpathmis_flat.h)
             const size_t ws_records = hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS ? 2 : 1;
             float *d_ws = (float *) rc.get(3, render_workspace_floats(paths, variant) * ws_records * sizeof(float));
-            auto launcher = hs.integrator.spectral ? launch_render_spectral : launch_render;
-#if !defined(MTSAMD_BLOCKSTATS)
-            if (lean == 1) launcher = launch_render_lean_a; else if (lean == 2) launcher = launch_render_lean_b; else if (lean == 3) launcher = launch_render_lean_s;
-            else if (lean == 4) launcher = launch_render_lean_p; else if (lean == 5) launcher = launch_render_lean_ps; else if (lean == 6) launcher = launch_render_lean_h; else if (lean == 7) launcher = launch_render_lean_c;
-#endif
-            HIP_CHECK(launcher(
-                          hs.scene, d_blocks, (uint32_t) blocks.size(), block_size, spp, d_target, d_counters,
-                          opts.collect_counters != 0, variant, wg_threads, d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream));
+            const RenderArgs args = { &hs.scene, d_blocks, (uint32_t) blocks.size(), block_size, spp, d_target, d_counters, opts.collect_counters != 0, variant,
+                                      d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream };
+            HIP_CHECK(launcher(args));
             HIP_CHECK(hipEventRecord(ev1, stream));
             for (;;) {
                 hipError_t q = hipEventQuery(ev1);
@@ -463,7 +471,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
             lpt_mode = lpt ? atoi(lpt) : -1;
             const bool force = lpt && (atoi(lpt) == 2 || atoi(lpt) == 3);   // 2, 3: calibrate whatever the block count (tests, diagnostics with MTSAMD_LPT_DEBUG)
             const uint32_t cal_spp = (uint32_t) std::max<size_t>(std::min<size_t>(4, launch_spp / 128), force && launch_spp >= 2 ? 1 : 0);
-            if (variant >= 10000 && variant < 20000 && block_size <= 256 && (!lpt || atoi(lpt) != 0) && cal_spp > 0 &&
+            if (variant >= 10000 && block_size <= 256 && (!lpt || atoi(lpt) != 0) && cal_spp > 0 &&
                 (force || pass_blocks[0].size() > (size_t) std::max(cu_count, 1)) && !should_stop()) {
                 std::vector<DBlock> cal(pass_blocks[0]);           // the distinct block positions of the first chunk
                 std::sort(cal.begin(), cal.end(), [&](const DBlock &x, const DBlock &y) { return pos(x) < pos(y); });

@@ -36,8 +36,8 @@ inline namespace MTS_VARIANT_NS {
 #define DEV_NOINLINE __device__ __noinline__
 // functions that are calls in the general kernels so that scenes which never reach them do not carry their registers, and inline in the
 // lean translation units that keep them: a unit has few enough of them left, and a kernel WITHOUT any call does not pay the calling
-// convention at all (EXP_LEAN_CALLS restores the calls: measurement)
-#if defined(MTS_LEAN) && !defined(EXP_LEAN_CALLS)
+// convention at all
+#if defined(MTS_LEAN)
 #define DEV_CALL_UNLESS_LEAN DEV
 #else
 #define DEV_CALL_UNLESS_LEAN DEV_NOINLINE

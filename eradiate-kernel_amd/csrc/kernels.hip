@@ -6,12 +6,10 @@
 // registers, the scene is read with scalar loads, the only vector memory traffic is the volume
 // gathers and one film update per pixel.  Citations are relative to /root/reference.
 // Compiled twice into libmtsamd.so: as it is (MTS_SPEC_N = 3: the rgb / mono variants, all kernels) and through kernels_spectral.hip
-// (MTS_SPEC_N = 4: the spectral variant: `volpath` on the regrouping machine with 512-path workgroups, `path` per lane; launchers carry
+// (MTS_SPEC_N = 4: the spectral variant: `volpath` on the regrouping machine with 256-path workgroups, `path` per lane; launchers carry
 // the suffix _spectral).
 #include <hip/hip_runtime.h>
-#if !defined(EXP_PM_TABLES_CONST)     // measurement only: the tables of pm_log / pm_exp read from the constant address space
 #define PM_TABLES_IN_LDS 1            // pmath.h: LDS copies of the two hot lookup tables; every kernel below fills them first
-#endif
 #include "integrator_dev.h"
 #include "volpath_flat.h"
 #include "volpathmis_flat.h"
@@ -219,11 +217,7 @@ __global__ void __launch_bounds__(256, (FLAT && INTEG != NI_PATH) ? 1 : (INTEG =
     // LDS-staged BVH top: the breadth-first top levels of the host-built BVH (dscene.h), shared by the workgroup's traversals
     __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];
     {
-#if defined(EXP_NO_BVH_LDS)
-        const int staged = 0;                                 // measurement only
-#else
         const int staged = min(sc.bvh_node_count, MTS_BVH_LDS_NODES);
-#endif
         for (int k = (int) threadIdx.x; k < staged * 8; k += (int) blockDim.x) bvh_top[k] = sc.bvh_nodes[k];
         pm_tables_to_lds(threadIdx.x);
         __syncthreads();
@@ -292,24 +286,6 @@ __global__ void __launch_bounds__(NT, WPE) render_kernel_wga(DScene sc, const DB
     }
 }
 static_assert(sizeof(WgArgs) % 4 == 0, "WgArgs mirrors the kernel parameters");
-
-#if !defined(MTS_LEAN)
-// The same machine on the lane-affine driver (volpath_flat.h, driver 3): conflict-free LDS state, mask claims instead of rings.
-template <bool COUNT, int WG, int NT, int WPE>
-__global__ void __launch_bounds__(NT, WPE) render_kernel_wgl(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
-                                                           uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
-                                                           unsigned long long *counters, const uint32_t *stop_flag,
-                                                           const uint32_t *tiles, uint32_t n_tiles) {
-    Counters cnt = {};
-    workgroup_lanes<COUNT, WG, NT, VolpathLanes<COUNT, WG>>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
-    if (COUNT) {
-        atomicAdd(counters + 0, (unsigned long long) cnt.n_iter);
-        atomicAdd(counters + 1, (unsigned long long) cnt.n_lookup);
-        atomicAdd(counters + 2, (unsigned long long) cnt.n_nee_step);
-    }
-}
-
-#endif // !MTS_LEAN
 
 // The same driver for volpathmis (volpathmis_flat.h): four weight matrices per path, 512 paths per workgroup, two waves per SIMD.
 template <bool COUNT, bool SPEC, int WG, int NT>
@@ -412,186 +388,92 @@ hipError_t launch_film_sum_slots(float *d_film, const float *d_slots, size_t fil
 }
 
 size_t render_workspace_floats(uint64_t threads, int variant) {
-    if (variant < 256) return 0;
-    if (variant >= 20000) variant -= 20000;
-    if (variant >= 10000) variant -= 10000;
-    const uint64_t padded = (threads + variant - 1) / variant * variant;
-    return (size_t) padded * (variant >= 256 && variant <= 4096 ? MTS_COLD_RECORD : C_COUNT) + 32;      // workgroup drivers: one 128-byte record per path
+    if (variant < 10000) return 0;
+    const uint64_t wg = (uint64_t) (variant - 10000), padded = (threads + wg - 1) / wg * wg;
+    return (size_t) padded * MTS_COLD_RECORD + 32;      // workgroup drivers: one 128-byte record per path
 }
 
 #endif // MTS_SPEC_N == 3
 
-#if defined(MTS_LEAN)
-// the 1024-path `volpath` machine and the 512-path `volpathmis` machine, nothing else (mts_render sends everything else to launch_render)
-hipError_t MTS_LAUNCHER(launch_render)(const DScene &sc, const DBlock *d_blocks, uint32_t n_blocks, uint32_t block_size, uint32_t sample_count,
-                         float *d_film, unsigned long long *d_counters, bool count, int variant, int wg_threads, float *d_workspace,
-                         const uint32_t *d_stop_flag, const uint32_t *d_tiles, uint32_t n_tiles, hipStream_t stream) {
-    if (n_blocks == 0) return hipSuccess;
-    const uint64_t threads = d_tiles != nullptr ? (uint64_t) n_tiles * MTS_TILE_PIXELS : (uint64_t) n_blocks * block_size * block_size;
-    if (threads + 1024 >= ((uint64_t) 1 << 32)) return hipErrorInvalidValue;
-#if defined(MTS_LEAN_PATH)    // kernels_lean_p.hip / _ps.hip: `path` as the flat loop with regeneration, nothing else
-    if (variant == 1 && sc.integrator.type == MTS_INTEGRATOR_PATH) {
-        const uint32_t grid = (uint32_t) ((threads + 255) / 256);
-        if (count) hipLaunchKernelGGL((render_kernel<true, true, NI_PATH>), dim3(grid), dim3(256), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_counters, d_stop_flag);
-        else hipLaunchKernelGGL((render_kernel<false, true, NI_PATH>), dim3(grid), dim3(256), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_counters, d_stop_flag);
-        return hipGetLastError();
-    }
-    (void) d_workspace; (void) wg_threads;
-    return hipErrorInvalidConfiguration;
-#else
-    if (sc.sensor.wavefront || wg_threads != 0) return hipErrorInvalidConfiguration;
-#if MTS_SPEC_N != 3          // the spectral variant's machines: 256-path workgroups
-    if (variant == 10256 && sc.integrator.type == MTS_INTEGRATOR_VOLPATH) {
-        const uint32_t grid = (uint32_t) ((threads + 255) / 256), stride = grid * 256;
-        // register budget of three waves per SIMD (three 256-path workgroups per CU): with the spectral grid lookups inline the allocator needs the bound
-        if (count) hipLaunchKernelGGL((render_kernel_wga<true, 256, 256, 3>), dim3(grid), dim3(256), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        else hipLaunchKernelGGL((render_kernel_wga<false, 256, 256, 3>), dim3(grid), dim3(256), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        return hipGetLastError();
-    }
-    if (variant == 10256 && sc.integrator.type == MTS_INTEGRATOR_VOLPATHMIS && sc.integrator.use_spectral_mis) {
-        const uint32_t grid = (uint32_t) ((threads + 255) / 256), stride = grid * 256;
-        if (count) hipLaunchKernelGGL((render_kernel_wga_mis<true, true, 256, 256>), dim3(grid), dim3(256), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        else hipLaunchKernelGGL((render_kernel_wga_mis<false, true, 256, 256>), dim3(grid), dim3(256), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        return hipGetLastError();
-    }
-    return hipErrorInvalidConfiguration;
-#else
-    if (variant == 11024 && sc.integrator.type == MTS_INTEGRATOR_VOLPATH) {
-        const uint32_t grid = (uint32_t) ((threads + 1023) / 1024), stride = grid * 1024;
-        if (count) hipLaunchKernelGGL((render_kernel_wga<true, 1024, 1024, 4>), dim3(grid), dim3(1024), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        else hipLaunchKernelGGL((render_kernel_wga<false, 1024, 1024, 4>), dim3(grid), dim3(1024), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        return hipGetLastError();
-    }
-    if (variant == 10512 && sc.integrator.type == MTS_INTEGRATOR_VOLPATHMIS && sc.integrator.use_spectral_mis) {
-        const uint32_t grid = (uint32_t) ((threads + 511) / 512), stride = grid * 512;
-#if defined(MTS_LEAN_MIS_768)   // the 512 paths served by 768 threads: three waves per SIMD want <= 168 VGPRs, which this unit's kernel meets (C3M 375 -> 393)
-        if (count) hipLaunchKernelGGL((render_kernel_wga_mis<true, true, 512, 768>), dim3(grid), dim3(768), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        else hipLaunchKernelGGL((render_kernel_wga_mis<false, true, 512, 768>), dim3(grid), dim3(768), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        return hipGetLastError();
-#endif
-        if (count) hipLaunchKernelGGL((render_kernel_wga_mis<true, true, 512, 512>), dim3(grid), dim3(512), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        else hipLaunchKernelGGL((render_kernel_wga_mis<false, true, 512, 512>), dim3(grid), dim3(512), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        return hipGetLastError();
-    }
-    return hipErrorInvalidConfiguration;
-#endif
-#endif // MTS_LEAN_PATH
-}
-#else
-hipError_t MTS_LAUNCHER(launch_render)(const DScene &sc, const DBlock *d_blocks, uint32_t n_blocks, uint32_t block_size, uint32_t sample_count,
-                         float *d_film, unsigned long long *d_counters, bool count, int variant, int wg_threads, float *d_workspace,
-                         const uint32_t *d_stop_flag, const uint32_t *d_tiles, uint32_t n_tiles, hipStream_t stream) {
-    if (n_blocks == 0) return hipSuccess;
-    // cost-sorted tiles (regrouping kernels only): the launch covers n_tiles slots of 16 paths instead of the blocks' concatenated Morton orders
-    const uint64_t threads = d_tiles != nullptr ? (uint64_t) n_tiles * MTS_TILE_PIXELS : (uint64_t) n_blocks * block_size * block_size;
-    if (d_tiles != nullptr && variant < 10000) return hipErrorInvalidConfiguration;
-    if (threads + 1024 >= ((uint64_t) 1 << 32)) return hipErrorInvalidValue;      // thread and path indices are 32 bit (mts_render launches in chunks)
-#if MTS_SPEC_N == 3
-    if (variant >= 20000 && sc.integrator.type == MTS_INTEGRATOR_VOLPATH) {        // lane-affine regrouping, variant = 20000 + paths per workgroup
-        const uint32_t wg = (uint32_t) (variant - 20000);
-        const uint32_t grid = (uint32_t) ((threads + wg - 1) / wg);
-        const uint32_t stride = grid * wg;
-        const int nt = wg_threads > 0 ? wg_threads : (int) wg;
-#define LAUNCH_WGL(W, T, E) do { if (count) hipLaunchKernelGGL((render_kernel_wgl<true, W, T, E>), dim3(grid), dim3(T), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles); \
-                                 else hipLaunchKernelGGL((render_kernel_wgl<false, W, T, E>), dim3(grid), dim3(T), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles); } while (0)
-        if (wg == 1024 && nt == 1024) LAUNCH_WGL(1024, 1024, 4);
-        else return hipErrorInvalidConfiguration;
-#undef LAUNCH_WGL
-        return hipGetLastError();
-    }
-    if (variant >= 10000 && sc.integrator.type == MTS_INTEGRATOR_VOLPATH) {        // asynchronous regrouping, variant = 10000 + paths per workgroup
-        const uint32_t wg = (uint32_t) (variant - 10000);
-        const uint32_t grid = (uint32_t) ((threads + wg - 1) / wg);
-        const uint32_t stride = grid * wg;
-        const int nt = wg_threads > 0 ? wg_threads : (int) wg;
-#define LAUNCH_WGA(W, T, E) do { if (count) hipLaunchKernelGGL((render_kernel_wga<true, W, T, E>), dim3(grid), dim3(T), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles); \
-                                 else hipLaunchKernelGGL((render_kernel_wga<false, W, T, E>), dim3(grid), dim3(T), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles); } while (0)
-        if (sc.sensor.wavefront) {                              // gpu_* streams: the instantiation that recomputes the generator's increment (wg_block, WF)
-            if (wg != 1024 || nt != 1024) return hipErrorInvalidConfiguration;
-            if (count) hipLaunchKernelGGL((render_kernel_wga<true, 1024, 1024, 4, true>), dim3(grid), dim3(1024), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-            else hipLaunchKernelGGL((render_kernel_wga<false, 1024, 1024, 4, true>), dim3(grid), dim3(1024), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        } else
-        if (wg == 256 && nt == 256) LAUNCH_WGA(256, 256, 4);
-        else if (wg == 512 && nt == 512) LAUNCH_WGA(512, 512, 4);
-        else if (wg == 512 && nt == 256) LAUNCH_WGA(512, 256, 2);
-        else if (wg == 1024 && nt == 1024) LAUNCH_WGA(1024, 1024, 4);
-        else if (wg == 1024 && nt == 768) LAUNCH_WGA(1024, 768, 3);
-        else if (wg == 1024 && nt == 512) LAUNCH_WGA(1024, 512, 2);
-        else return hipErrorInvalidConfiguration;
-#undef LAUNCH_WGA
-        return hipGetLastError();
-    }
-    if (variant >= 10000 && sc.integrator.type == MTS_INTEGRATOR_VOLPATHMIS) {     // the same machinery, variant = 10000 + paths per workgroup (<= 512)
-        const uint32_t wg = (uint32_t) (variant - 10000);
-        const uint32_t grid = (uint32_t) ((threads + wg - 1) / wg);
-        const uint32_t stride = grid * wg;
-        const bool spec = sc.integrator.use_spectral_mis != 0;
-#define LAUNCH_MIS(C, S, W) hipLaunchKernelGGL((render_kernel_wga_mis<C, S, W, W>), dim3(grid), dim3(W), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles)
-#define LAUNCH_MIS_W(W) do { if (count) { if (spec) LAUNCH_MIS(true, true, W); else LAUNCH_MIS(true, false, W); } \
-                             else { if (spec) LAUNCH_MIS(false, true, W); else LAUNCH_MIS(false, false, W); } } while (0)
-        if (wg == 512) LAUNCH_MIS_W(512);
-        else if (wg == 256) LAUNCH_MIS_W(256);
-        else return hipErrorInvalidConfiguration;
-#undef LAUNCH_MIS_W
-#undef LAUNCH_MIS
-        return hipGetLastError();
-    }
-    const bool flat = variant != 0;
-#else
-    if (variant >= 10000 && sc.integrator.type == MTS_INTEGRATOR_VOLPATH) {        // four-wide state: 42 hot dwords per path, 512 paths fill the LDS
-        const uint32_t wg = (uint32_t) (variant - 10000);
-        const uint32_t grid = (uint32_t) ((threads + wg - 1) / wg);
-        const uint32_t stride = grid * wg;
-#define LAUNCH_WGA(W) do { if (count) hipLaunchKernelGGL((render_kernel_wga<true, W, W, 2>), dim3(grid), dim3(W), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles); \
-                           else hipLaunchKernelGGL((render_kernel_wga<false, W, W, 2>), dim3(grid), dim3(W), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles); } while (0)
-        if (wg == 512) LAUNCH_WGA(512);
-        else if (wg == 256) LAUNCH_WGA(256);
-        else return hipErrorInvalidConfiguration;
-#undef LAUNCH_WGA
-        return hipGetLastError();
-    }
-    if (variant >= 10000 && sc.integrator.type == MTS_INTEGRATOR_VOLPATHMIS) {     // 4 x 4 weight matrices: 101 hot dwords per path with spectral MIS (256 paths, one workgroup per CU), 53 without
-        const uint32_t wg = (uint32_t) (variant - 10000);
-        const uint32_t grid = (uint32_t) ((threads + wg - 1) / wg);
-        const uint32_t stride = grid * wg;
-        const bool spec = sc.integrator.use_spectral_mis != 0;
-        if (wg != 256) return hipErrorInvalidConfiguration;
-#define LAUNCH_MIS(C, S) hipLaunchKernelGGL((render_kernel_wga_mis<C, S, 256, 256>), dim3(grid), dim3(256), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles)
-        // 69 hot dwords per path with spectral MIS (round 4: the path's matrices are parked during walks): two 256-path workgroups per CU,
-        // 8 waves at <= 256 VGPRs.  (Before: 101 dwords, ONE workgroup per CU -- 256 threads: 38.7 Msamples/s on C5SM, 512 threads: 42.3;
-        // MTSAMD_WG_THREADS=512 still gives the latter launch.)
-        if (spec && wg_threads == 512) {
-            if (count) hipLaunchKernelGGL((render_kernel_wga_mis<true, true, 256, 512>), dim3(grid), dim3(512), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-            else hipLaunchKernelGGL((render_kernel_wga_mis<false, true, 256, 512>), dim3(grid), dim3(512), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_workspace, stride, d_counters, d_stop_flag, d_tiles, n_tiles);
-        } else
-        if (count) { if (spec) LAUNCH_MIS(true, true); else LAUNCH_MIS(true, false); }
-        else { if (spec) LAUNCH_MIS(false, true); else LAUNCH_MIS(false, false); }
-#undef LAUNCH_MIS
-        return hipGetLastError();
-    }
-    const bool flat = variant != 0; (void) d_workspace;                           // path: the per-lane kernels
-#endif
-    const uint32_t grid = (uint32_t) ((threads + 255) / 256);
-    const bool use_flat = flat && sc.integrator.type == MTS_INTEGRATOR_VOLPATH;
-#define LAUNCH(C, F, I) hipLaunchKernelGGL((render_kernel<C, F, I>), dim3(grid), dim3(256), 0, stream, sc, d_blocks, n_blocks, block_size, sample_count, d_film, d_counters, d_stop_flag)
-#define LAUNCH_C(F, I) do { if (count) LAUNCH(true, F, I); else LAUNCH(false, F, I); } while (0)
-#if MTS_SPEC_N == 3
-    if (use_flat) LAUNCH_C(true, NI_VOLPATH);
-    else
-#endif
-    if (sc.integrator.type == MTS_INTEGRATOR_PATH) {
-        if (flat) LAUNCH_C(true, NI_PATH);                         // one flat loop over path segments with regeneration (path_pixel_flat)
-        else LAUNCH_C(false, NI_PATH);
-    }
-    else if (sc.integrator.type == MTS_INTEGRATOR_VOLPATH) LAUNCH_C(false, NI_VOLPATH);
-    else if (sc.integrator.use_spectral_mis) LAUNCH_C(false, NI_VOLPATHMIS);
-    else LAUNCH_C(false, NI_VOLPATHMIS_NOSPEC);
-#undef LAUNCH_C
-#undef LAUNCH
-    (void) use_flat;
+// ---- the render launchers: one per translation unit (launch.h), each choosing among the kernels of its unit by a.variant
+typedef void (*WgKernel)(DScene, const DBlock *, uint32_t, uint32_t, uint32_t, float *, float *, uint32_t, unsigned long long *,
+                         const uint32_t *, const uint32_t *, uint32_t);
+typedef void (*LaneKernel)(DScene, const DBlock *, uint32_t, uint32_t, uint32_t, float *, unsigned long long *, const uint32_t *);
+#define MTS_BY_COUNT(kernel, ...) (a.count ? kernel<true, __VA_ARGS__> : kernel<false, __VA_ARGS__>)
+// the regrouping kernels: `wg` paths per workgroup served by `nt` threads; the cold records of the launch's paths are `stride` apart
+static hipError_t launch_wg(const RenderArgs &a, uint64_t threads, uint32_t wg, uint32_t nt, WgKernel k) {
+    const uint32_t grid = (uint32_t) ((threads + wg - 1) / wg), stride = grid * wg;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(nt), 0, a.stream, *a.sc, a.blocks, a.n_blocks, a.block_size, a.sample_count, a.film, a.workspace, stride,
+                       a.counters, a.stop_flag, a.tiles, a.n_tiles);
     return hipGetLastError();
 }
-#endif // MTS_LEAN
+// the per-lane kernels: one thread per pixel
+static hipError_t launch_lane(const RenderArgs &a, uint64_t threads, LaneKernel k) {
+    hipLaunchKernelGGL(k, dim3((uint32_t) ((threads + 255) / 256)), dim3(256), 0, a.stream, *a.sc, a.blocks, a.n_blocks, a.block_size, a.sample_count,
+                       a.film, a.counters, a.stop_flag);
+    return hipGetLastError();
+}
+
+hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
+    if (a.n_blocks == 0) return hipSuccess;
+    // cost-sorted tiles (regrouping kernels only): the launch covers n_tiles slots of 16 paths instead of the blocks' concatenated Morton orders
+    const uint64_t threads = a.tiles != nullptr ? (uint64_t) a.n_tiles * MTS_TILE_PIXELS : (uint64_t) a.n_blocks * a.block_size * a.block_size;
+    if (a.tiles != nullptr && a.variant < 10000) return hipErrorInvalidConfiguration;
+    if (threads + 1024 >= ((uint64_t) 1 << 32)) return hipErrorInvalidValue;      // thread and path indices are 32 bit (mts_render launches in chunks)
+    const int integ = a.sc->integrator.type;
+    const bool volpath = integ == MTS_INTEGRATOR_VOLPATH, mis = integ == MTS_INTEGRATOR_VOLPATHMIS, spec_mis = a.sc->integrator.use_spectral_mis != 0;
+#if defined(MTS_LEAN_PATH)    // kernels_lean_p.hip / _ps.hip: `path` as the flat loop with regeneration, nothing else
+    (void) volpath; (void) mis; (void) spec_mis;
+    if (a.variant == 1 && integ == MTS_INTEGRATOR_PATH) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_PATH));
+    return hipErrorInvalidConfiguration;
+#elif defined(MTS_LEAN)       // the other lean units: the regrouping machines of `volpath` and of `volpathmis` with spectral MIS, nothing else
+    if (a.sc->sensor.wavefront) return hipErrorInvalidConfiguration;
+#if MTS_SPEC_N != 3           // the spectral variant's machines: 256-path workgroups
+    // register budget of three waves per SIMD (three 256-path workgroups per CU): with the spectral grid lookups inline the allocator needs the bound
+    if (a.variant == 10256 && volpath) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 3));
+    if (a.variant == 10256 && mis && spec_mis) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256));
+#else
+    if (a.variant == 11024 && volpath) return launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4));
+#if defined(MTS_LEAN_MIS_768)   // the 512 paths served by 768 threads: three waves per SIMD want <= 168 VGPRs, which this unit's kernel meets (C3M 375 -> 393)
+    if (a.variant == 10512 && mis && spec_mis) return launch_wg(a, threads, 512, 768, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 768));
+#else
+    if (a.variant == 10512 && mis && spec_mis) return launch_wg(a, threads, 512, 512, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 512));
+#endif
+#endif
+    return hipErrorInvalidConfiguration;
+#else                         // the general kernels
+#if MTS_SPEC_N == 3
+    if (a.variant >= 10000 && volpath) {                      // asynchronous regrouping, variant = 10000 + paths per workgroup
+        if (a.sc->sensor.wavefront)                           // gpu_* streams: the instantiation that recomputes the generator's increment (wg_block, WF)
+            return a.variant == 11024 ? launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4, true)) : hipErrorInvalidConfiguration;
+        if (a.variant == 11024) return launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4));
+        if (a.variant == 10256) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 4));
+        return hipErrorInvalidConfiguration;
+    }
+    if (a.variant >= 10000 && mis) {                          // the same machinery, 512 or 256 paths per workgroup
+        if (a.variant == 10512)
+            return launch_wg(a, threads, 512, 512, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 512) : MTS_BY_COUNT(render_kernel_wga_mis, false, 512, 512));
+        if (a.variant == 10256)
+            return launch_wg(a, threads, 256, 256, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256) : MTS_BY_COUNT(render_kernel_wga_mis, false, 256, 256));
+        return hipErrorInvalidConfiguration;
+    }
+    if (a.variant != 0 && volpath) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_VOLPATH));     // the flat state machine per lane
+#else
+    // four-wide state: `volpath` 42 hot dwords per path; `volpathmis` 69 with spectral MIS (round 4: the path's matrices are parked during
+    // walks), 53 without -- 256 paths per workgroup, two or three workgroups per CU
+    if (a.variant >= 10000 && volpath)
+        return a.variant == 10256 ? launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 2)) : hipErrorInvalidConfiguration;
+    if (a.variant >= 10000 && mis)
+        return a.variant == 10256 ? launch_wg(a, threads, 256, 256, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256) : MTS_BY_COUNT(render_kernel_wga_mis, false, 256, 256))
+                                  : hipErrorInvalidConfiguration;
+#endif
+    if (integ == MTS_INTEGRATOR_PATH)                         // flat: one loop over path segments with regeneration (path_pixel_flat)
+        return launch_lane(a, threads, a.variant != 0 ? MTS_BY_COUNT(render_kernel, true, NI_PATH) : MTS_BY_COUNT(render_kernel, false, NI_PATH));
+    if (volpath) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, false, NI_VOLPATH));
+    return launch_lane(a, threads, spec_mis ? MTS_BY_COUNT(render_kernel, false, NI_VOLPATHMIS) : MTS_BY_COUNT(render_kernel, false, NI_VOLPATHMIS_NOSPEC));
+#endif
+}
+#undef MTS_BY_COUNT
 
 #if MTS_SPEC_N == 3 && !defined(MTS_LEAN)
 

@@ -279,9 +279,6 @@ PM_HD float pm_log(float x) {
 #if defined(PM_USE_LIBM) && !defined(__HIPCC__)
     return logf(x);   // oracle/Makefile, liboracle_libm.so: glibc itself, the pin of this header
 #endif
-#if defined(EXP_FASTMATH) && defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_logf(x) * 0.6931471805599453f;   // measurement only: breaks parity
-#endif
 #if defined(PM_CORRECTLY_ROUNDED)
     return pm_log_cr(x);
 #endif
@@ -323,9 +320,6 @@ PM_HD double pm_exp2_tail(uint64_t ki, double r, double c0, double c1, double c2
 PM_HD float pm_exp(float x) {
 #if defined(PM_USE_LIBM) && !defined(__HIPCC__)
     return expf(x);   // oracle/Makefile, liboracle_libm.so: glibc itself, the pin of this header
-#endif
-#if defined(EXP_FASTMATH) && defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);   // measurement only: breaks parity
 #endif
 #if defined(PM_CORRECTLY_ROUNDED)
     return pm_exp_cr(x);

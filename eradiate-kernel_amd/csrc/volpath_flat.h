@@ -13,7 +13,8 @@
 //   2. volpath_workgroup_async: the hot state of a workgroup's paths lives in LDS (struct of arrays), one LDS
 //      ring of path ids per block class; a wave claims 64 paths that wait for the same block, runs it with
 //      every lane active, and appends the paths to the rings of their next blocks.  No barriers, no sort.
-//      (A barrier-synchronised counting-sort driver was measured at half the speed and removed.)
+//      (A barrier-synchronised counting-sort driver was measured at half the speed and removed; so was a lane-affine driver
+//      with mask claims instead of rings: 365 vs 546 Msamples/s on C3)
 //
 // The random draws happen in exactly the order of the scalar_rgb variant (SURVEY.md 8(a')); results are
 // bit-identical to the nested formulation in integrator_dev.h and to the CPU restatement.
@@ -124,9 +125,6 @@ DEV GridCell grid_cell(const DVolume &v, F3 p_world) {
     return c;
 }
 DEV float grid_fetch1(const MTS_GLOBAL_AS float *__restrict__ D, const GridCell &c) {
-#if defined(EXP_NOGATHER)
-    return trilerp(0.5f, 0.6f, 0.7f, 0.8f, 0.9f, 1.0f, 1.1f, 1.2f, c.w0, c.w1) + 1e-9f * (float) (c.r00 + c.x0 + c.r11 + c.x1 + c.r01 + c.r10);
-#endif
     return trilerp(D[c.r00 + c.x0], D[c.r00 + c.x1], D[c.r10 + c.x0], D[c.r10 + c.x1],
                    D[c.r01 + c.x0], D[c.r01 + c.x1], D[c.r11 + c.x0], D[c.r11 + c.x1], c.w0, c.w1);
 }
@@ -140,14 +138,8 @@ typedef mts_float4 __attribute__((aligned(8))) mts_float4_a8;
 DEV void grid_fetch_pair(const MTS_GLOBAL_AS float *__restrict__ P, const GridCell &c, int nx, bool columns_equal, float &sigma_t, float &albedo) {
     const int xb = min(c.x0, nx - 2);
     const bool hi0 = c.x0 != xb, hi1 = c.x1 != xb;           // take the second voxel of the pair
-#if defined(EXP_GATHER_LOCAL)                                // measurement only (breaks parity): every gather inside the first 4 KiB of the grid, i.e.
-#define MTS_GL(i) ((i) & 511)                                // L1-resident -- how much of a tracking step is the L2 latency of its lookups?
-    mts_float4 q00 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * MTS_GL(c.r00 + xb)), q01 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * MTS_GL(c.r01 + xb)), q10 = q00, q11 = q01;
-    if (!columns_equal) { q10 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * MTS_GL(c.r10 + xb)); q11 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * MTS_GL(c.r11 + xb)); }
-#else
     mts_float4 q00 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * (c.r00 + xb)), q01 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * (c.r01 + xb)), q10 = q00, q11 = q01;
     if (!columns_equal) { q10 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * (c.r10 + xb)); q11 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * (c.r11 + xb)); }
-#endif
     sigma_t = trilerp(hi0 ? q00.z : q00.x, hi1 ? q00.z : q00.x, hi0 ? q10.z : q10.x, hi1 ? q10.z : q10.x,
                       hi0 ? q01.z : q01.x, hi1 ? q01.z : q01.x, hi0 ? q11.z : q11.x, hi1 ? q11.z : q11.x, c.w0, c.w1);
     albedo = trilerp(hi0 ? q00.w : q00.y, hi1 ? q00.w : q00.y, hi0 ? q10.w : q10.y, hi1 ? q10.w : q10.y,
@@ -360,11 +352,7 @@ struct ColdStoreT {
 };
 // What a path needs from its surroundings
 typedef ColdStoreT<float *> ColdStore;                       // generic pointer (the per-lane driver parks cold state in LDS)
-#if defined(EXP_COLD_SOA)
-typedef ColdStoreT<MTS_GLOBAL_AS float *> ColdStoreHbm;
-#else
 typedef ColdStoreT<MTS_GLOBAL_AS float *, true> ColdStoreHbm;
-#endif
 // (workgroup driver: cold state in HBM, addressed with GLOBAL instructions)
 template <class Cold>
 struct PathEnvT {
@@ -1006,12 +994,8 @@ template <int WG>
 DEV bool wg_env(const WgArgs &a, uint32_t wg_base, uint32_t pid, PathEnvT<ColdStoreHbm> &e) {     // pixel owned by path `pid`; false: outside the block
     const uint32_t ppb = a.block_size * a.block_size;       // a multiple of WG (checked by the launcher)
     e.sample_count = a.sample_count; e.film = as_global(a.film);
-#if defined(EXP_COLD_SOA)
-    e.cold.base = as_global(a.cold_g) + wg_base + pid; e.cold.stride = a.cold_stride;
-#else
     e.cold.base = as_global(a.cold_g) + (size_t) (wg_base + pid) * MTS_COLD_RECORD; e.cold.stride = 1;
     __builtin_assume(((uintptr_t) e.cold.base & 127u) == 0);       // hipMalloc'ed base, 128-byte records: lets neighbouring fields share one wide access
-#endif
     e.park = as_global(a.cold_g) + ((size_t) a.cold_stride + wg_base + pid) * MTS_COLD_RECORD;      // behind the cold records (volpathmis launches allocate it)
     e.lx = e.ly = 0; e.index = 0;
     if (a.tiles != nullptr) {                               // cost-sorted tiles: the block is per lane (vector loads; only NEW and the start need them)
@@ -1059,15 +1043,6 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
     typedef ClassFields<C> CF;
     PathState p;
     if (COUNT && C == B_MED) MTS_SEG_BEGIN(*cnt);
-#if defined(EXP_COLD_TOUCH)
-    // A walk's step may end the walk, and the end reads the path's cold record (parked at the start of the walk, ~10^5 cycles ago: by now in
-    // the Infinity Cache or in HBM) in a tail that the whole wave waits for.  One dword of the record is requested here, a block's worth of
-    // work before it is needed, so that the tail's loads find the line in the cache.  Hand-issued: the compiler would sink a plain load to
-    // its use.  The register is only read behind the s_waitcnt below.
-    uint32_t cold_touch = 0;
-    if (C == B_MEDW || C == B_WSURF)
-        asm volatile("global_load_dword %0, %1, off" : "=v"(cold_touch) : "v"((const MTS_GLOBAL_AS float *) (e.cold.base + C_SD)) : "memory");
-#endif
     hs.template load_m<CF::load>(p);
     if (WF && C != B_INT) p.rng.inc = wavefront_increment(a.sc.sensor, e.blk, e.lx, e.ly, __float_as_uint(e.cold.f(C_SAMPLE)));
     if (COUNT && C == B_MED) MTS_SEG(*cnt, 0);
@@ -1098,9 +1073,6 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
         if (!(C == B_MED || C == B_MEDW) || cls != C || rounds >= 16) break;
         if (__popcll(__ballot(true)) < (C == B_MEDW ? MTS_REPEAT_MIN_W : MTS_REPEAT_MIN)) break;
     }
-#if defined(EXP_COLD_TOUCH)
-    if (C == B_MEDW || C == B_WSURF) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); asm volatile("" :: "v"(cold_touch)); }
-#endif
     bool chained = false;
     if ((MTS_CHAIN & 4) && C == B_MEDW && cls == B_WSURF) {    // the walk left the medium: its surface step(s) run here, on the lanes that have one
         hs.template load_add<G_ALL & ~CF::load>(p);
@@ -1441,193 +1413,6 @@ DEV void volpath_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt
     __syncthreads();                                          // every wave has left the loop: the path state is final
     if (__atomic_load_n(&q_ctl[2 * B_COUNT], __ATOMIC_RELAXED) != STOP_NONE) wg_flush_unfinished<WG, NT>(kernarg, hot_lds, H_PACKED, wg_base);
 }
-
-// ---------------------------------------------------------------------------------------------------------
-// Driver 3: lane-affine regrouping.  As driver 2 a wave runs ONE block class at a time with the hot state in LDS, but a path is bound
-// to a lane: path `pid` is only ever executed by lane (pid mod 64) of whichever wave takes it.  That one rule pays three times:
-//   * LDS banks: field k of path p lives at word k * WG + p, i.e. in bank p mod 32 for the dword accesses (MI355X_MICROARCH.md,
-//     "LDS").  With the rings a wave's lanes hold arbitrary ids -- 32 random ids on 32 banks are a ~3.5-way conflict, the measured
-//     SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.67 of round 2.  Here lane L holds an id = L mod 64: every state access of every
-//     block is conflict-free.
-//   * No rings: what waits for class c on lane L is a 16-bit mask (bit j = path L + 64 j).  Push = one atomic OR into the lane's own
-//     word (64 lanes, 64 addresses, 32 banks x 2 groups: one LDS pass, where the ring tails serialised 64 same-address atomics);
-//     claim = the wave reads its 64 mask records, votes for the class that serves most lanes (eight ballots), and every lane clears
-//     one bit of its own word with an atomic AND.  No head / tail counters, no compare-and-swap that one lane wins for the wave
-//     (61 % of those were lost), no slot hand-over and hence no wait that could stall.
-//   * Waves do not queue behind one shared counter: sixteen waves that want the same class take different bits (each wave starts
-//     its search at slot (wave id) mod 16), a lost bit is retried from the value the atomic returned.
-// The price is that a lane can only be filled from its own <= 16 paths: a class with n waiting paths serves 64 (1 - exp(-n / 64))
-// lanes on average instead of min(n, 64).
-// q_mask[k][L]: classes 2k (low half) and 2k + 1 (high half) of lane L.  q_ctl[0] counts finished paths, q_ctl[1] is the stop word.
-// Stopping needs no second exit: a raised stop word makes the vote come out empty, which is the (rare) path that already looks at
-// the finished count.  After a stop the workgroup adds the accumulators of its unfinished pixels to the film, as the reference puts
-// a partially rendered block on the film (integrator.cpp:120-130, 213-216).
-template <bool COUNT, int WG, int NT, class M /* machine: HOT dwords per path, PACKED_AT, init(), block() */>
-DEV void workgroup_lanes(const MTS_CONST_AS void *kernarg, Counters &cnt) {
-    constexpr int PPL = WG / 64;                              // paths per lane
-    static_assert(WG % 64 == 0 && NT % 64 == 0 && NT <= WG && PPL <= 16 && B_DONE == 8, "whole waves, 16-bit masks, eight classes in four words");
-    __shared__ uint32_t hot_lds[M::HOT * WG];
-    __shared__ uint32_t q_mask[4][64];
-    __shared__ uint32_t q_ctl[4];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wg_base = blockIdx.x * WG;
-    if (tid < 256u) (&q_mask[0][0])[tid] = 0u;
-    if (tid < 4u) q_ctl[tid] = 0u;
-    pm_tables_to_lds(tid);
-    __syncthreads();
-#pragma unroll 1
-    for (uint32_t pid0 = tid; pid0 < (uint32_t) WG; pid0 += NT) {   // ---- initialise the paths (integrator.cpp:198) and queue them
-        const int cls = M::init(kernarg, hot_lds, wg_base, pid0, &cnt);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        const uint32_t j = pid0 >> 6;
-        if (cls != B_DONE) atomicOr(&q_mask[cls >> 1][lane], 1u << (j + 16u * ((uint32_t) cls & 1u)));
-        const unsigned long long dm = __builtin_amdgcn_ballot_w64(cls == B_DONE);
-        if (dm != 0ull && lane == (uint32_t) __builtin_ctzll(dm)) atomicAdd(&q_ctl[0], (uint32_t) __popcll(dm));
-    }
-    const uint32_t rot = (tid >> 6) & 15u;                    // where this wave starts looking in a mask
-#if defined(MTSAMD_BLOCKSTATS)
-    long long bs_t0 = clock64(); unsigned long long bs_loc[45] = {};                      // laid out like g_blockstats
-#endif
-    uint32_t poll_ticks = (tid >> 6) * 2048u, idle_naps = 0, idle_t0 = 0;  // poll_ticks paces the reads of the host's stop word (see driver 2)
-#pragma unroll 1
-    for (;;) {
-        int sel = 0; bool finished = false, mine = false; uint32_t j = 0;
-#pragma unroll 1
-        for (;;) {                                            // ---- the claim: snapshot, vote, one atomic AND per lane
-            const uint32_t m0 = __atomic_load_n(&q_mask[0][lane], __ATOMIC_RELAXED), m1 = __atomic_load_n(&q_mask[1][lane], __ATOMIC_RELAXED),
-                           m2 = __atomic_load_n(&q_mask[2][lane], __ATOMIC_RELAXED), m3 = __atomic_load_n(&q_mask[3][lane], __ATOMIC_RELAXED);
-            const uint32_t stop = (uint32_t) __builtin_amdgcn_readfirstlane((int) __atomic_load_n(&q_ctl[1], __ATOMIC_RELAXED));
-            uint32_t best = 0;
-#define MTS_VOTE(c, expr) do { const uint32_t v_ = (uint32_t) __popcll(__builtin_amdgcn_ballot_w64((expr) != 0u)); if (v_ > best) { best = v_; sel = (c); } } while (0)
-            MTS_VOTE(0, m0 & 0xFFFFu); MTS_VOTE(1, m0 >> 16); MTS_VOTE(2, m1 & 0xFFFFu); MTS_VOTE(3, m1 >> 16);
-            MTS_VOTE(4, m2 & 0xFFFFu); MTS_VOTE(5, m2 >> 16); MTS_VOTE(6, m3 & 0xFFFFu); MTS_VOTE(7, m3 >> 16);
-#undef MTS_VOTE
-            if (stop != STOP_NONE) best = 0;
-            if (best == 0) {
-                // nothing waits: every path has finished, or is being executed by another wave, or the workgroup was stopped
-                if (stop != STOP_NONE || (uint32_t) __builtin_amdgcn_readfirstlane((int) __atomic_load_n(&q_ctl[0], __ATOMIC_RELAXED)) == (uint32_t) WG) { finished = true; break; }
-                if ((poll_ticks += 1u) >= 32768u) {           // Integrator::should_stop(): see driver 2 for the pacing
-                    poll_ticks = 0;
-                    if (lane == 0 && __hip_atomic_load(cload_k<WgArgs>(kernarg).stop_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)
-                        atomicCAS(&q_ctl[1], (uint32_t) STOP_NONE, (uint32_t) STOP_CANCEL);
-                }
-                if (wga_idle_expired(idle_naps, idle_t0, MTS_IDLE_TICKS)) {   // a path was lost: report instead of waiting for ever
-                    if (lane == 0 && atomicCAS(&q_ctl[1], (uint32_t) STOP_NONE, (uint32_t) STOP_STALL) == STOP_NONE) {
-                        unsigned long long *counters = cload_k<WgArgs>(kernarg).counters;
-                        if (atomicCAS(counters + MTS_DIAG_BASE, 0ull, 3ull) == 0ull) {
-                            counters[MTS_DIAG_BASE + 1] = 0ull; counters[MTS_DIAG_BASE + 2] = 0ull; counters[MTS_DIAG_BASE + 3] = 0ull;
-                            counters[MTS_DIAG_BASE + 4] = __atomic_load_n(&q_ctl[0], __ATOMIC_RELAXED); counters[MTS_DIAG_BASE + 5] = blockIdx.x;
-                        }
-                    }
-                }
-                __builtin_amdgcn_s_sleep(2);
-#if defined(MTSAMD_BLOCKSTATS)
-                if (COUNT) { long long t = clock64(); bs_loc[42] += (unsigned long long) (t - bs_t0); bs_t0 = t; }
-#endif
-                continue;
-            }
-            idle_naps = 0;
-#if defined(MTSAMD_BLOCKSTATS)
-            if (COUNT) bs_loc[10] += 1ull;                    // claim attempts
-#endif
-            const uint32_t w = sel < 4 ? (sel < 2 ? m0 : m1) : (sel < 6 ? m2 : m3), sh = 16u * ((uint32_t) sel & 1u);
-            uint32_t f = (w >> sh) & 0xFFFFu;
-            uint32_t *word = &q_mask[sel >> 1][lane];
-#pragma nounroll
-            while (__builtin_amdgcn_ballot_w64(f != 0u) != 0ull) {      // one round unless another wave took the same bit
-                if (f != 0u) {
-                    const uint32_t fr = f & (0xFFFFu << rot), src = fr != 0u ? fr : f;
-                    j = (uint32_t) __builtin_ctz(src);
-                    const uint32_t bit = 1u << (j + sh);
-                    const uint32_t old = atomicAnd(word, ~bit);
-                    if (old & bit) { mine = true; f = 0u; }
-                    else f = (old >> sh) & 0xFFFFu;
-                }
-#if defined(MTSAMD_BLOCKSTATS)
-                if (COUNT) bs_loc[11] += 1ull;                // rounds of the per-lane take
-#endif
-            }
-            if (__builtin_amdgcn_ballot_w64(mine) != 0ull) break;
-        }
-        if (finished) break;
-        const uint32_t pid = lane + 64u * j;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#if defined(MTSAMD_BLOCKSTATS)
-        if (COUNT) { bs_loc[sel] += 1ull; bs_loc[12 + sel] += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(mine));
-                     long long t = clock64(); bs_loc[44] += (unsigned long long) (t - bs_t0); bs_t0 = t; }
-#endif
-        int cls = B_DONE;
-        if (mine) cls = M::block(sel, kernarg, hot_lds, wg_base, pid, &cnt);
-#if defined(MTSAMD_BLOCKSTATS)
-        if (COUNT) { long long t = clock64(); bs_loc[24 + sel] += (unsigned long long) (t - bs_t0); bs_t0 = t; }
-#endif
-        if (sel == B_NEW && (poll_ticks += 256u) >= 32768u) {
-            poll_ticks = 0;
-            if (lane == 0 && __hip_atomic_load(cload_k<WgArgs>(kernarg).stop_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)
-                atomicCAS(&q_ctl[1], (uint32_t) STOP_NONE, (uint32_t) STOP_CANCEL);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (mine && cls != B_DONE) atomicOr(&q_mask[cls >> 1][lane], 1u << (j + 16u * ((uint32_t) cls & 1u)));
-        const unsigned long long dm = __builtin_amdgcn_ballot_w64(mine && cls == B_DONE);
-        if (dm != 0ull && lane == (uint32_t) __builtin_ctzll(dm)) atomicAdd(&q_ctl[0], (uint32_t) __popcll(dm));
-#if defined(MTSAMD_BLOCKSTATS)
-        if (COUNT) { long long t = clock64(); bs_loc[43] += (unsigned long long) (t - bs_t0); bs_t0 = t; }
-#endif
-    }
-#if defined(MTSAMD_BLOCKSTATS)
-    if (COUNT) {
-        long long t = clock64(); bs_loc[44] += (unsigned long long) (t - bs_t0);
-        for (int k = 0; k < 6; ++k) bs_loc[36 + k] = cnt.seg[k];
-        if (lane == 0) for (int k = 0; k < 45; ++k) atomicAdd(&g_blockstats[k], bs_loc[k]);
-    }
-#endif
-    // ---- stopped (cancel / timeout / stall): the samples the unfinished pixels have accumulated go to the film
-    __syncthreads();
-    if (__atomic_load_n(&q_ctl[1], __ATOMIC_RELAXED) != STOP_NONE) wg_flush_unfinished<WG, NT>(kernarg, hot_lds, M::PACKED_AT, wg_base);
-}
-
-// The volpath machine on driver 3
-template <bool COUNT, int WG>
-struct VolpathLanes {
-    static constexpr int HOT = H_COUNT, PACKED_AT = H_PACKED;
-    DEV static int init(const MTS_CONST_AS void *kernarg, uint32_t *hot_lds, uint32_t wg_base, uint32_t pid0, Counters *cnt) {
-        const WgArgs a = cload_k<WgArgs>(kernarg);
-        VolpathMachine<COUNT> vm(a.sc, *cnt);
-        PathEnvT<ColdStoreHbm> e; PathState p;
-        HotStore<WG> hs; hs.base = hot_lds + pid0;
-        const bool ok = wg_env<WG>(a, wg_base, pid0, e);
-        p.rng.state = 0; p.rng.inc = 0;
-        p.ray = make_ray(f3s(0.f), f3(0.f, 0.f, 1.f), 0.f, 0.f); p.si.t = pm_inf(); p.si.p = f3s(0.f); p.si.uv.x = p.si.uv.y = 0.f; p.si.shape = -1; p.si.prim = 0;
-        p.medium = -1; p.thr = p.res = p.trans = spec_s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;
-#if MTS_SPEC_N != 3
-        p.wl = spec_s(0.f);
-#endif
-        p.st = S_DONE;
-        if (ok) {
-            const uint32_t ppb = a.block_size * a.block_size;
-            p.rng.seed(a.sc.sensor.seed + (uint64_t) e.blk.id * ppb + e.index, PCG32_DEFAULT_STREAM);     // sampler.cpp:83-96
-            for (int k = 0; k < 5; ++k) e.cold.f(C_ACC + k) = 0.f;
-            e.cold.f(C_SAMPLE) = __uint_as_float(0u);
-            vm.begin_sample(p, e);
-            vm.top(p, e);
-        }
-        const int cls = vm.classify(p);
-        hs.store(p, cls);
-        return cls;
-    }
-    DEV static int block(int sel, const MTS_CONST_AS void *kernarg, uint32_t *hot_lds, uint32_t wg_base, uint32_t pid, Counters *cnt) {
-        switch (sel) {                                          // wave-uniform
-            case B_INT: return wg_block<COUNT, WG, B_INT>(kernarg, hot_lds, wg_base, pid, cnt);
-            case B_MED: return wg_block<COUNT, WG, B_MED>(kernarg, hot_lds, wg_base, pid, cnt);
-            case B_MEDW: return wg_block<COUNT, WG, B_MEDW>(kernarg, hot_lds, wg_base, pid, cnt);
-            case B_SCATTER: return wg_block<COUNT, WG, B_SCATTER>(kernarg, hot_lds, wg_base, pid, cnt);
-            case B_WSURF: return wg_block<COUNT, WG, B_WSURF>(kernarg, hot_lds, wg_base, pid, cnt);
-            case B_SURF: return wg_block<COUNT, WG, B_SURF>(kernarg, hot_lds, wg_base, pid, cnt);
-            case B_PHASE: return wg_block<COUNT, WG, B_PHASE>(kernarg, hot_lds, wg_base, pid, cnt);
-            default: return wg_block<COUNT, WG, B_NEW>(kernarg, hot_lds, wg_base, pid, cnt);
-        }
-    }
-};
 
 } // inline namespace
 } // namespace mtsamd
