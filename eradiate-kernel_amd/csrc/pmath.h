@@ -13,7 +13,8 @@
 //       also what aarch64 builds give;
 //   cbrtf : the classic flt-32 routine (s_cbrtf.c, glibc <= 2.40; compiled without FMA: it has no multiarch variant).
 // The SAME source gives the SAME bits when compiled by gcc for x86-64 (-mfma -ffp-contract=off) and by hipcc for gfx950
-// (-ffp-contract=off; fp32 / fp64 division and sqrt are IEEE correctly rounded on both), and -- measured, tests/test_pmath.py
+// (-ffp-contract=off; fp32 / fp64 division and sqrt are IEEE correctly rounded on both) -- measured on every fp32 argument of the
+// unary functions, both table placements, and 1.6 * 10^9 pairs of pow by tests/test_gpu_pmath.py -- and -- measured, tests/test_pmath.py
 // and tools/pmath_vs_glibc.cpp -- the same bits as glibc 2.35 itself for EVERY fp32 argument of logf, expf (|x| < 88.73),
 // sinf / cosf (|x| < 120; beyond that the correctly rounded routine below), cbrtf, and for 10^8 random arguments of powf.  So a
 // build of the restatement on glibc (oracle/liboracle_libm.so) renders the same film, bit for bit, as the build on this header.
@@ -58,6 +59,35 @@ PM_HD float pm_rcp(float x) {
 }
 PM_HD float pm_rsqrt(float x) { return pm_rcp(__builtin_sqrtf(x)); }
 PM_HD float pm_abs(float x) { return pm_from_bits(pm_bits(x) & 0x7fffffffu); }
+
+// x / d by a divisor whose reciprocal is at hand -- the majorant of a heterogeneous medium, a constant of its record, divided by two
+// or three times per tracking step (volpath_flat.h, volpathmis_flat.h).  pm_invariant_rcp(d) is rd = RN(1 / d) when d admits the
+// shortcut and 0 otherwise; the host computes it once per medium (scene_host.cpp).  pm_div_by_invariant: q = x rd, then two
+// Markstein corrections q += RN(x - q d) rd with the remainders exact by fma -- the IEEE quotient, bit for bit, in five multiply-adds
+// instead of v_div_scale x 2, v_rcp, six fma, v_div_fmas, v_div_fixup.  The argument needs every intermediate far from both ends of
+// the exponent range under flush-to-zero: a normal divisor whose significand is not all ones (the one case the correction does not
+// cover), d and rd in [2^-60, 2^61), and |x| in [2^-62, 2^62) -- q then lies in (2^-123, 2^122) and no remainder is flushed.  Every
+// other dividend (zeros, denormals, tiny or huge values, inf, NaN) and rd == 0 take the plain division: below 2^-101 flushed
+// remainders, and quotients that round up to FLT_MIN, made the shortcut differ from x / d, and from 2^68 on x rd overflowed.
+// Pinned against x / d under FTZ | DAZ on every admitted divisor exponent and every dividend binade
+// (tests/test_pmath.py::test_div_by_invariant_*, the predicate by test_invariant_rcp_admits_exactly_its_range), on the device
+// against the device's own x / d for all 2^32 dividends of 64 divisors (tests/test_gpu_pmath.py::test_div_by_invariant_on_the_device),
+// and in films by tests/test_gpu_numeric_edges.py.
+PM_HD float pm_invariant_rcp(float d) {
+    const uint32_t b = pm_bits(d), e = (b >> 23) & 0xffu;
+    const float rd = 1.0f / d;
+    const uint32_t er = (pm_bits(rd) >> 23) & 0xffu;
+    return (d > 0.f && e >= 67u && e <= 187u && er >= 67u && er <= 187u && (b & 0x7fffffu) != 0x7fffffu) ? rd : 0.f;
+}
+PM_HD float pm_div_by_invariant(float x, float d, float rd) {
+    if (rd == 0.f || pm_bits(x) * 2u - 0x41000000u >= 0x7c000000u) return x / d;   // |x| outside [2^-62, 2^62): 2|x|'s bits - 2^-62's
+    float q = x * rd;
+    float r = pm_fma(-q, d, x);
+    q = pm_fma(r, rd, q);
+    r = pm_fma(-q, d, x);
+    q = pm_fma(r, rd, q);
+    return q;
+}
 PM_HD float pm_min(float a, float b) { return b < a ? b : a; }   // std::min semantics
 PM_HD float pm_max(float a, float b) { return a < b ? b : a; }   // std::max semantics
 PM_HD float pm_safe_sqrt(float x) { return __builtin_sqrtf(pm_max(x, 0.0f)); }
@@ -141,7 +171,8 @@ PM_HD float pm_exp_cr(float x) {
 }
 
 // Simultaneous sine / cosine, correctly rounded for |x| < 1.6e6 (j * pio2_hi is exact below 2^20 quadrants; all call sites pass
-// 2*pi*u or a concentric-disk angle); beyond that the reduction loses accuracy, deterministically.
+// 2*pi*u or a concentric-disk angle); beyond that the reduction loses accuracy, deterministically and with the same bits on host and
+// device (tests/test_gpu_pmath.py: every fp32 argument).
 PM_HD void pm_sincos_cr(float x, float *s_out, float *c_out) {
     double xd = (double) x;
     double fj = __builtin_floor(pm_fma_d(xd, 0.63661977236758134308, 0.5));
@@ -163,7 +194,8 @@ PM_HD void pm_sincos_cr(float x, float *s_out, float *c_out) {
     cp = pm_fma_d(cp, z, -0x1.fffffffffff67p-2);
     cp = pm_fma_d(cp, z, 0x1.fffffffffffffp-1);
     float c = (float) cp;
-    int j = (int) fj;
+    const double j4 = fj - 4.0 * __builtin_floor(fj * 0.25);      // fj mod 4, exact: (int) fj is undefined beyond 2^31 (x86 gives
+    int j = j4 >= 0.0 && j4 < 4.0 ? (int) j4 : 0;                  // INT_MIN, gfx950 saturates); non-finite x: NaN results either way
     float ss = (j & 1) ? c : s;
     float cc = (j & 1) ? s : c;
     if (j & 2) ss = -ss;
@@ -199,9 +231,9 @@ PM_HD float pm_cbrt_cr(float x) {
 // x^y for x >= 0 (std::pow semantics for the cases the RPV model can produce; /root/reference/src/bsdfs/rpv.cpp:85-167):
 // exp(y log x) with both in fp64.
 PM_HD float pm_pow_cr(float x, float y) {
-    if (y == 0.0f) return 1.0f;
+    if ((pm_bits(y) & 0x7fffffffu) < 0x00800000u) return 1.0f;   // y == 0 under DAZ, by the bits (the device compiled the float test without the flush)
     if (!(x == x) || !(y == y)) return pm_nan();
-    if (x < 0.0f) return pm_nan();
+    if (pm_bits(x) > 0x807fffffu) return pm_nan();               // x < 0 under DAZ (-0 and negative denormals are zero)
     if (pm_bits(x) < 0x00800000u)                       // +0 / denormal
         return y > 0.0f ? 0.0f : pm_inf();
     if (pm_bits(x) == 0x7f800000u) return y > 0.0f ? pm_inf() : 0.0f;
@@ -423,9 +455,9 @@ PM_HD float pm_pow(float x, float y) {
 #if defined(PM_CORRECTLY_ROUNDED)
     return pm_pow_cr(x, y);
 #endif
-    if (y == 0.0f) return 1.0f;
+    if ((pm_bits(y) & 0x7fffffffu) < 0x00800000u) return 1.0f;   // y == 0 under DAZ, by the bits (the device compiled the float test without the flush)
     if (!(x == x) || !(y == y)) return pm_nan();
-    if (x < 0.0f) return pm_nan();
+    if (pm_bits(x) > 0x807fffffu) return pm_nan();               // x < 0 under DAZ (-0 and negative denormals are zero)
     uint32_t ix = pm_bits(x);
     if (ix < 0x00800000u)                               // +0 / denormal
         return y > 0.0f ? 0.0f : pm_inf();

@@ -397,15 +397,10 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
             const DVolume &st = hs.volumes[m.sigma_t_volume];
             if (!st.has_max) throw std::runtime_error("max() not implemented (constvolume sigma_t in heterogeneous medium)");
             dm.max_density = dm.scale * st.max;
-            {   // the kernels divide by the majorant two or three times per tracking step: with the correctly rounded reciprocal at hand an
-                // IEEE-exact quotient is five multiply-adds instead of the ~11-instruction division sequence (div_by_invariant,
-                // volpath_flat.h).  Usable when both are normal numbers well inside the exponent range and the significand of the
-                // divisor is not all ones (the one case Markstein's correction step does not cover).
-                const uint32_t b = pm_bits(dm.max_density), e = (b >> 23) & 0xffu;
-                const float rd = 1.0f / dm.max_density;
-                const uint32_t er = (pm_bits(rd) >> 23) & 0xffu;
-                dm.inv_max_density = (dm.max_density > 0.f && e >= 67u && e <= 187u && er >= 67u && er <= 187u && (b & 0x7fffffu) != 0x7fffffu) ? rd : 0.f;
-            }
+            // the kernels divide by the majorant two or three times per tracking step: with its correctly rounded reciprocal at hand an
+            // IEEE-exact quotient is five multiply-adds instead of the ~11-instruction division sequence (pm_div_by_invariant, pmath.h;
+            // the predicate that admits the majorant is pm_invariant_rcp, shared with the tests).
+            dm.inv_max_density = pm_invariant_rcp(dm.max_density);
             dm.aabb = st.bbox;
         } else if (m.type != MTS_MEDIUM_HOMOGENEOUS) throw std::runtime_error("unknown medium type");
         {   // kernel fast paths that do not change a single bit of the result

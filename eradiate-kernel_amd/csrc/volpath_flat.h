@@ -69,21 +69,10 @@ enum : uint32_t { FL_ALIVE = 1, FL_VALID_RAY = 2, FL_SPEC_CHAIN = 4, FL_NEEDS_IN
 // (heterogeneous.cpp:46: combined - sigma_t, homogeneous.cpp:44: 0).
 struct MedStep { float t, mint; F3 p; Spec sigma_t, sigma_s, combined; uint32_t info; float inv_combined /* DMedium::inv_max_density */; };
 
-// x / d for a divisor whose correctly rounded reciprocal rd = RN(1 / d) is at hand (the majorant of a heterogeneous medium: a constant
-// of the medium record): q = x rd, two Markstein corrections q += RN(x - q d) rd with the remainders exact by fma.  The first makes q
-// faithful, the second correctly rounded -- the IEEE quotient, bit for bit (the host excludes divisors with an all-ones significand
-// and exponents near the ends of the range, scene_host.cpp; checked against x / d on 4 * 10^10 quotients, tests/test_pmath.py has the
-// sampled version).  Five multiply-adds instead of v_div_scale x 2, v_rcp, six fma, v_div_fmas, v_div_fixup.  rd == 0: plain division.
-// The sign of a zero quotient is the dividend's (d > 0).
-DEV float div_by_invariant(float x, float d, float rd) {
-    if (rd == 0.f) return x / d;
-    float q = x * rd;
-    float r = pm_fma(-q, d, x);
-    q = pm_fma(r, rd, q);
-    r = pm_fma(-q, d, x);
-    q = pm_fma(r, rd, q);
-    return pm_from_bits(pm_bits(q) | (pm_bits(x) & 0x80000000u));
-}
+// x / d by the majorant through rd = DMedium::inv_max_density: pm_div_by_invariant (pmath.h), the IEEE quotient bit for bit
+// (tests/test_pmath.py::test_div_by_invariant_*, tests/test_gpu_pmath.py::test_div_by_invariant_*; film level:
+// tests/test_gpu_numeric_edges.py).  rd == 0: plain division.
+DEV float div_by_invariant(float x, float d, float rd) { return pm_div_by_invariant(x, d, rd); }
 DEV Spec div_by_invariant(Spec x, Spec d, float rd) {          // every channel of d holds the same value when rd != 0
     if (rd == 0.f) return x / d;
 #if MTS_SPEC_N == 3

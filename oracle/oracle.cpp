@@ -2080,16 +2080,84 @@ int oracle_bbox_ops(int n_points, const float *points, int n_boxes, const float 
     bsphere[0] = c.x; bsphere[1] = c.y; bsphere[2] = c.z; bsphere[3] = norm(c - b.max);
     return 0;
 }
-float oracle_math(int fn, float x, float y) {
+// 12..15: the IEEE operations and the majorant division of pmath.h whose bits depend on the floating-point environment -- evaluated
+// under the render workers' MXCSR (FTZ | DAZ, render() above) like everything in this file that renders.
+static float math_fn(int fn, float x, float y) {
     switch (fn) { case 0: return pm_log(x); case 1: return pm_exp(x); case 2: { float s, c; pm_sincos(x, &s, &c); return s; }
                   case 3: { float s, c; pm_sincos(x, &s, &c); return c; } case 4: return pm_cbrt(x); case 5: return pm_pow(x, y);
                   // the correctly rounded routines (pmath.h: -DPM_CORRECTLY_ROUNDED, and the |x| >= 120 tail of pm_sincos)
                   case 6: return pm_log_cr(x); case 7: return pm_exp_cr(x); case 8: { float s, c; pm_sincos_cr(x, &s, &c); return s; }
-                  case 9: { float s, c; pm_sincos_cr(x, &s, &c); return c; } case 10: return pm_cbrt_cr(x); case 11: return pm_pow_cr(x, y); }
+                  case 9: { float s, c; pm_sincos_cr(x, &s, &c); return c; } case 10: return pm_cbrt_cr(x); case 11: return pm_pow_cr(x, y);
+                  case 12: return pm_sqrt(x); case 13: return pm_rcp(x); case 14: return pm_rsqrt(x);
+                  case 15: return pm_div_by_invariant(x, y, pm_invariant_rcp(y)); }        // x / y by the majorant y (volpath_flat.h)
     return 0.f;
 }
+struct FtzDaz {                                              // scoped MXCSR | FTZ | DAZ, as render()'s workers
+    unsigned saved; FtzDaz() : saved(_mm_getcsr()) { _mm_setcsr(saved | 0x8040); } ~FtzDaz() { _mm_setcsr(saved); }
+};
+float oracle_math(int fn, float x, float y) {
+    if (fn >= 12) { FtzDaz env; return math_fn(fn, x, y); }
+    return math_fn(fn, x, y);
+}
 void oracle_math_n(int fn, int64_t n, const float *x, const float *y, float *out) {
-    for (int64_t i = 0; i < n; ++i) out[i] = oracle_math(fn, x[i], y ? y[i] : 0.f);
+    if (fn >= 12) { FtzDaz env; for (int64_t i = 0; i < n; ++i) out[i] = math_fn(fn, x[i], y ? y[i] : 0.f); return; }
+    for (int64_t i = 0; i < n; ++i) out[i] = math_fn(fn, x[i], y ? y[i] : 0.f);
+}
+// pm_invariant_rcp (pmath.h): the host's predicate for the majorant division, as scene_host.cpp applies it.
+float oracle_invariant_rcp(float d) { return pm_invariant_rcp(d); }
+
+// The device sweeps of tests/test_gpu_pmath.py: `got` holds the device's values of function `fn` (the ids of oracle_math; y: the second
+// argument, the divisor of 15) for the n consecutive bit patterns first_bits, first_bits + 1, ...; the host's value of each under
+// FTZ | DAZ is compared bit for bit (two NaNs are equal).  Returns the number of mismatches; the first max_bad bit patterns, in
+// order, go to bad.  At most 16 threads, each on a contiguous share.
+int64_t oracle_math_sweep(int fn, uint32_t first_bits, int64_t n, float y, const float *got, uint32_t *bad, int max_bad, int threads) {
+    threads = threads < 1 ? 1 : threads > 16 ? 16 : threads;
+    if (n < (int64_t) threads * 65536) threads = 1;
+    std::vector<int64_t> count(threads, 0);
+    std::vector<std::vector<uint32_t>> first(threads);
+    auto work = [&](int t) {
+        FtzDaz env;
+        const int64_t lo = n * t / threads, hi = n * (t + 1) / threads;
+        int64_t c = 0;
+        for (int64_t i = lo; i < hi; ++i) {
+            const uint32_t bits = first_bits + (uint32_t) i;
+            const uint32_t h = pm_bits(math_fn(fn, pm_from_bits(bits), y)), g = pm_bits(got[i]);
+            if (h == g || ((h & 0x7fffffffu) > 0x7f800000u && (g & 0x7fffffffu) > 0x7f800000u)) continue;
+            if ((int64_t) first[t].size() < max_bad) first[t].push_back(bits);
+            ++c;
+        }
+        count[t] = c;
+    };
+    if (threads == 1) work(0);
+    else { std::vector<std::thread> th; for (int t = 0; t < threads; ++t) th.emplace_back(work, t); for (auto &t : th) t.join(); }
+    int64_t total = 0; int k = 0;
+    for (int t = 0; t < threads; ++t) {
+        total += count[t];
+        for (uint32_t b : first[t]) if (k < max_bad) bad[k++] = b;
+    }
+    return total;
+}
+
+// IEEE fp32 operations under the render workers' MXCSR (FTZ | DAZ): op 0 a * b, 1 a + b, 2 fma(a, b, c), 3 a / b, 4 sqrt(a),
+// 5 (float) ((double) a * (double) b) -- the f64 -> f32 conversion of an exact product, 6 a < b, 7 a == b (1 or 0).  tests/test_gpu_pmath.py holds the device's
+// results at the flush boundary against these.
+void oracle_fp32_op_n(int op, int64_t n, const float *a, const float *b, const float *c, float *out) {
+    FtzDaz env;
+    for (int64_t i = 0; i < n; ++i) {
+        volatile float x = a[i], y = b ? b[i] : 0.f, z = c ? c[i] : 0.f;
+        float r = 0.f;
+        switch (op) {
+            case 0: r = x * y; break;
+            case 1: r = x + y; break;
+            case 2: r = __builtin_fmaf(x, y, z); break;
+            case 3: r = x / y; break;
+            case 4: r = __builtin_sqrtf(x); break;
+            case 5: { volatile double p = (double) x * (double) y; r = (float) p; break; }
+            case 6: r = x < y ? 1.f : 0.f; break;
+            case 7: r = x == y ? 1.f : 0.f; break;
+        }
+        out[i] = r;
+    }
 }
 
 } // extern "C"

@@ -54,6 +54,10 @@ def lib():
         L.oracle_emitter_sample_direction.argtypes = [C.c_void_p, fp, C.c_float, C.c_float, fp, fp, fp, fp]
         L.oracle_math.argtypes = [C.c_int, C.c_float, C.c_float]; L.oracle_math.restype = C.c_float
         L.oracle_math_n.argtypes = [C.c_int, C.c_int64, fp, fp, fp]; L.oracle_math_n.restype = None
+        L.oracle_invariant_rcp.argtypes = [C.c_float]; L.oracle_invariant_rcp.restype = C.c_float
+        L.oracle_math_sweep.argtypes = [C.c_int, C.c_uint32, C.c_int64, C.c_float, C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_int]
+        L.oracle_math_sweep.restype = C.c_int64
+        L.oracle_fp32_op_n.argtypes = [C.c_int, C.c_int64, fp, fp, fp, fp]; L.oracle_fp32_op_n.restype = None
         _lib = L
     return _lib
 

@@ -154,3 +154,112 @@ def test_special_values(base):
     assert L.oracle_math(POWf, 0.0, -1.0) == np.inf and L.oracle_math(POWf, np.inf, -1.0) == 0.0 and L.oracle_math(POWf, 1.0, 5.5) == 1.0
     assert L.oracle_math(POWf, 0.5, 200.0) == 0.0 and L.oracle_math(POWf, 2.0, 200.0) == np.inf
     assert np.isnan(L.oracle_math(POWf, -1.0, 0.5))
+
+
+# ---- pm_div_by_invariant (pmath.h): x / d through rd = pm_invariant_rcp(d), the division by the majorant in every tracking step of
+# volpath / volpathmis.  The oracle divides; the kernels must give the same bits for every dividend a render can produce.
+SQRT, RCP, RSQRT, DIVINV = 12, 13, 14, 15
+OP_MUL, OP_ADD, OP_FMA, OP_DIV, OP_SQRT, OP_F64 = range(6)
+FLT_MIN_BITS = 0x00800000
+
+
+def f32(bits):
+    return np.asarray(bits, np.uint32).view(np.float32)
+
+
+def fp32_op(op, a, b=None, c=None):
+    """IEEE fp32 operation under FTZ | DAZ (the render workers' MXCSR), through oracle_fp32_op_n."""
+    a = np.ascontiguousarray(a, np.float32)
+    b = np.zeros_like(a) if b is None else np.ascontiguousarray(b, np.float32)
+    c = np.zeros_like(a) if c is None else np.ascontiguousarray(c, np.float32)
+    out = np.empty_like(a)
+    ob.lib().oracle_fp32_op_n(op, a.size, ob._p(a), ob._p(b), ob._p(c), ob._p(out))
+    return out
+
+
+def admitted_divisors(rng, n_random=8):
+    """Every biased exponent the predicate can admit (67..187) x significands 0, 1, 0x400000, 0x7ffffe and n_random seeded ones;
+    the ones pm_invariant_rcp admits."""
+    e = np.arange(67, 188, dtype=np.uint32)
+    m = np.concatenate([np.array([0, 1, 0x400000, 0x7ffffe], np.uint32)[None, :].repeat(e.size, 0),
+                        rng.integers(0, 0x7fffff, (e.size, n_random), dtype=np.uint32)], 1)
+    d = f32((e[:, None] << 23) | m).ravel()
+    L = ob.lib()
+    return np.array([x for x in d if L.oracle_invariant_rcp(float(x)) != 0], np.float32)
+
+
+def dividends(rng, d, per_binade=48):
+    """For one divisor: every binade of x (denormals included), both signs, +-0 / inf / NaN, and a dense set whose quotient lands in
+    [2^-128, 2^-123] -- around FLT_MIN, where a flushed remainder or a quotient that rounds up to FLT_MIN breaks the corrections --
+    with the neighbours of RN(FLT_MIN d)."""
+    e = np.arange(0, 255, dtype=np.uint32).repeat(per_binade)
+    m = rng.integers(0, 0x800000, e.size, dtype=np.uint32)
+    m[::per_binade] = 0
+    m[1::per_binade] = 0x7fffff
+    x = f32((e << 23) | m)
+    q = f32(rng.integers(0x00400000, 0x02000000, 4096, dtype=np.uint32))          # [2^-128, 2^-123)
+    band = fp32_op(OP_MUL, q, np.full(q.size, d, np.float32))
+    near = (fp32_op(OP_MUL, f32([FLT_MIN_BITS]), np.float32([d])).view(np.uint32) + np.arange(-64, 65, dtype=np.int64)).astype(np.uint32)
+    special = f32([0, 1, 0x7fffff, 0x7f800000, 0x7fc00000, 0x7f7fffff])
+    x = np.concatenate([x, band, f32(near), special])
+    return np.concatenate([x, -x])
+
+
+def div_mismatches(x, d):
+    got = evalf(DIVINV, x, np.full(x.size, d, np.float32))
+    want = fp32_op(OP_DIV, x, np.full(x.size, d, np.float32))
+    gb, wb = got.view(np.uint32), want.view(np.uint32)
+    nan = ((gb & 0x7fffffff) > 0x7f800000) & ((wb & 0x7fffffff) > 0x7f800000)
+    return x[(gb != wb) & ~nan], got[(gb != wb) & ~nan], want[(gb != wb) & ~nan]
+
+
+def test_div_by_invariant_is_the_division_over_the_admitted_range():
+    """Every admitted divisor exponent x every dividend binade, the band of quotients around FLT_MIN, denormal / zero / non-finite
+    dividends: bit for bit x / d under FTZ | DAZ (the oracle's division)."""
+    rng = np.random.default_rng(1234)
+    ds = admitted_divisors(rng)
+    assert ds.size > 121 * 8
+    for d in ds:
+        x, got, want = div_mismatches(dividends(rng, d), d)
+        assert x.size == 0, ("d = %a: %d mismatches" % (float(d), x.size),
+                             ["x %08x got %08x want %08x" % t for t in zip(x.view(np.uint32)[:8], got.view(np.uint32)[:8], want.view(np.uint32)[:8])])
+
+
+@pytest.mark.parametrize("d_bits", [0x3f800000, 0x3f800001, 0x3fc00000, 0x3fffff7e, 0x21800000, 0x5d7ffffe])   # 1, 1+ulp, 1.5, ~2, 2^-60, ~2^60
+def test_div_by_invariant_on_a_full_binade_of_dividends(d_bits):
+    d = f32([d_bits])[0]
+    assert ob.lib().oracle_invariant_rcp(float(d)) != 0
+    x = f32((np.uint32(127) << 23) | np.arange(0x800000, dtype=np.uint32))
+    x = np.concatenate([x, x * np.float32(2.0 ** -100), x * np.float32(2.0 ** 61)])    # [1, 2), the low end, the high end of the window
+    x, got, want = div_mismatches(x, d)
+    assert x.size == 0, ["x %08x got %08x want %08x" % t for t in zip(x.view(np.uint32)[:8], got.view(np.uint32)[:8], want.view(np.uint32)[:8])]
+
+
+def test_invariant_rcp_admits_exactly_its_range():
+    """The predicate (pm_invariant_rcp, shared by scene_host.cpp and the tests) at its edges: biased exponents 66 / 67 and 187 / 188,
+    the all-ones significand, non-positive and non-finite divisors."""
+    L = ob.lib()
+    rcp = lambda bits: L.oracle_invariant_rcp(float(f32([bits])[0]))
+    assert rcp(66 << 23) == 0 and rcp((66 << 23) | 0x400000) == 0
+    assert rcp(67 << 23) == 2.0 ** 60 and rcp((67 << 23) | 0x400000) != 0
+    assert rcp(187 << 23) == 2.0 ** -60                    # d = 2^60: rd = 2^-60 is biased 67
+    assert rcp((187 << 23) | 1) == 0                       # rd below 2^-60: biased 66
+    assert rcp(188 << 23) == 0
+    for e in (67, 127, 150, 186):
+        assert rcp((e << 23) | 0x7fffff) == 0 and rcp((e << 23) | 0x7ffffe) != 0
+    for bits in (0, 0x80000000, 0xbf800000, 0x7f800000, 0x7fc00000, 0x00000001, 0x007fffff):
+        assert rcp(bits) == 0
+    assert rcp(0x3fc00000) == np.float32(1 / np.float32(1.5))
+    assert L.oracle_math(SQRT, 2.0, 0) == np.float32(np.sqrt(np.float32(2))) and L.oracle_math(RCP, 4.0, 0) == 0.25
+    assert L.oracle_math(RSQRT, 4.0, 0) == 0.5 and L.oracle_math(DIVINV, 3.0, 1.5) == 2.0
+
+
+def test_fp32_ops_flush_like_the_render_workers():
+    """oracle_fp32_op_n runs under FTZ | DAZ: denormal operands count as zero, tiny results flush; a result that rounds UP to FLT_MIN
+    is FLT_MIN (x86 detects tininess after rounding)."""
+    tiny = f32([0x00000001, 0x007fffff])
+    assert (fp32_op(OP_ADD, tiny, np.float32([0, 0])) == 0).all()
+    assert (fp32_op(OP_MUL, f32([FLT_MIN_BITS]), np.float32([0.5])) == 0).all()
+    assert fp32_op(OP_MUL, f32([0x3f7ffffe]), f32([0x00800001])).view(np.uint32)[0] == FLT_MIN_BITS
+    assert fp32_op(OP_DIV, f32([0x00800001]), f32([0x3f800001])).view(np.uint32)[0] == FLT_MIN_BITS
+    assert fp32_op(OP_F64, f32([FLT_MIN_BITS]), np.float32([0.75])).view(np.uint32)[0] == 0
