@@ -1019,6 +1019,18 @@ def test_retired_kernel_switches_are_rejected(gpu_rgb, monkeypatch):
             scene.integrator().render(scene, scene.sensors()[0])
 
 
+def test_malformed_render_switches_are_rejected(gpu_rgb, monkeypatch):
+    """The render switches are read once, before anything is planned or launched: a value outside the accepted ones is an error, not a
+    silent fall-back to a default (csrc/render_plan.cpp: read_render_switches)."""
+    scene = gpu_rgb.load_dict(scenes.c3_heterogeneous(8, 8, 4, res=8))
+    for name, value, message in (("MTSAMD_LPT", "4", "MTSAMD_LPT must be one of 0, 1, 2, 3"), ("MTSAMD_LEAN", "yes", "MTSAMD_LEAN must be one of 0, 1, 2")):
+        monkeypatch.setenv(name, value)
+        with pytest.raises(RuntimeError, match=message):
+            scene.integrator().render(scene, scene.sensors()[0])
+        monkeypatch.delenv(name)
+    assert scene.integrator().render(scene, scene.sensors()[0]) is True
+
+
 @pytest.mark.parametrize("integrator,kernel", [("volpath", None), ("volpathmis", None), ("volpath", "flat"), ("volpath", "nested")])
 def test_stopped_render_keeps_the_finished_samples(gpu_rgb, monkeypatch, integrator, kernel):
     """A render cut short by the integrator's `timeout` returns the samples finished so far: the reference puts the partially rendered
