@@ -13,6 +13,7 @@
 #include "integrator_dev.h"
 #include "volpath_flat.h"
 #include "volpathmis_flat.h"
+#include "ring_driver.h"
 #if defined(MTS_LEAN)               // kernels_lean_*.hip: the regrouping kernels once more, for scenes that keep the promises of MTS_TRAITS
 #define MTS_LAUNCHER_CAT2(a, b) a##b
 #define MTS_LAUNCHER_CAT(a, b) MTS_LAUNCHER_CAT2(a, b)
@@ -26,6 +27,13 @@
 
 namespace mtsamd {
 inline namespace MTS_VARIANT_NS {
+
+// a thread's loop counters -> counters[0..2] of the launch (counting kernel variants)
+DEV void flush_counters(unsigned long long *counters, const Counters &cnt) {
+    atomicAdd(counters + 0, (unsigned long long) cnt.n_iter);
+    atomicAdd(counters + 1, (unsigned long long) cnt.n_lookup);
+    atomicAdd(counters + 2, (unsigned long long) cnt.n_nee_step);
+}
 
 #if !defined(MTS_LEAN) || defined(MTS_LEAN_PATH)
 // librender/integrator.cpp:233-288 + librender/imageblock.cpp:79-172, fused: the sample is splatted
@@ -260,16 +268,12 @@ __global__ void __launch_bounds__(256, (FLAT && INTEG != NI_PATH) ? 1 : (INTEG =
         float *dst = film + film_channels * ((size_t) (blk.oy + (int) ly - sc.sensor.crop_y) * sc.sensor.crop_w + (blk.ox + (int) lx - sc.sensor.crop_x));
         for (int k = 0; k < 5; ++k) atomicAdd(dst + k, acc[k]);
     }
-    if (COUNT) {
-        atomicAdd(counters + 0, (unsigned long long) cnt.n_iter);
-        atomicAdd(counters + 1, (unsigned long long) cnt.n_lookup);
-        atomicAdd(counters + 2, (unsigned long long) cnt.n_nee_step);
-    }
+    if (COUNT) flush_counters(counters, cnt);
 }
 
 #endif // !MTS_LEAN || MTS_LEAN_PATH
 
-// Asynchronous-regrouping variant of the volpath render kernel (volpath_flat.h, driver 2).  The parameter list must stay in
+// Asynchronous-regrouping variant of the volpath render kernel (ring_driver.h on the blocks of volpath_flat.h).  The parameter list must stay in
 // sync with WgArgs: the block functions re-read it from the kernarg segment with scalar loads.  WG paths are served by NT threads;
 // WPE = waves per SIMD the register budget is sized for (512 / WPE VGPRs).
 template <bool COUNT, int WG, int NT, int WPE, bool WF = false>
@@ -278,12 +282,8 @@ __global__ void __launch_bounds__(NT, WPE) render_kernel_wga(DScene sc, const DB
                                                            unsigned long long *counters, const uint32_t *stop_flag,
                                                            const uint32_t *tiles, uint32_t n_tiles) {
     Counters cnt = {};
-    volpath_workgroup_async<COUNT, WG, NT, WF>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
-    if (COUNT) {
-        atomicAdd(counters + 0, (unsigned long long) cnt.n_iter);
-        atomicAdd(counters + 1, (unsigned long long) cnt.n_lookup);
-        atomicAdd(counters + 2, (unsigned long long) cnt.n_nee_step);
-    }
+    ring_workgroup_async<VolpathRing<COUNT, WG, WF>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+    if (COUNT) flush_counters(counters, cnt);
 }
 static_assert(sizeof(WgArgs) % 4 == 0, "WgArgs mirrors the kernel parameters");
 
@@ -294,12 +294,8 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis(D
                                                                unsigned long long *counters, const uint32_t *stop_flag,
                                                                const uint32_t *tiles, uint32_t n_tiles) {
     Counters cnt = {};
-    volpathmis_workgroup_async<COUNT, SPEC, WG, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
-    if (COUNT) {
-        atomicAdd(counters + 0, (unsigned long long) cnt.n_iter);
-        atomicAdd(counters + 1, (unsigned long long) cnt.n_lookup);
-        atomicAdd(counters + 2, (unsigned long long) cnt.n_nee_step);
-    }
+    ring_workgroup_async<VolpathMisRing<COUNT, SPEC, WG>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+    if (COUNT) flush_counters(counters, cnt);
 }
 
 #if MTS_SPEC_N == 3 && !defined(MTS_LEAN)

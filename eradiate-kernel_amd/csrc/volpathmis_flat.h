@@ -1,11 +1,11 @@
-// volpathmis_flat.h -- volpathmis (integrators/volpathmis.cpp:86-445) on the regrouping machinery of volpath_flat.h.
+// volpathmis_flat.h -- volpathmis (integrators/volpathmis.cpp:86-445) on the regrouping machinery of volpath_flat.h and ring_driver.h.
 //
 // The spectral-MIS volumetric path tracer carries probability-ratio matrices instead of a throughput: p_over_f / p_over_f_nee along
 // the path (volpathmis.cpp:117-118), and two more, started from p_over_f, along every emitter-sampling walk (sample_emitter,
 // :330-445).  As in volpath_flat.h the three nested loops become one state machine -- a path is (mode, state) and advances one block
 // at a time: INTERSECT, MEDIUM step of the path, MEDIUM step of a walk, SCATTER (emitter sampling at a medium interaction), walk
 // SURFACE, path SURFACE + BSDF, PHASE, NEW sample -- and the workgroup regroups its paths by the block they wait for through the LDS
-// rings of volpath_flat.h (same protocol: wga_push, wga_tag_wait, wga_raise_stop).
+// rings of ring_driver.h, the driver it shares with volpath (VolpathMisRing at the end of this file).
 // Hot state (round 4): TWO matrix slots per path, not four.  The path's pair (p_over_f, p_over_f_nee) is only read and written
 // outside a walk, the walk's pair (p_over_f_uni, p_over_f_nee of sample_emitter) only inside one, and a walk starts from a copy of
 // p_over_f (:345-346): start_walk PARKS the path's pair in a second 128-byte cold record (PathEnvT::park, HBM), the two slots then
@@ -598,11 +598,8 @@ struct MisHotStore {
 // One block of class C for the path `pid` (the class is wave-uniform, the blocks are inlined as in volpath_flat.h)
 template <bool COUNT, bool SPEC, int WG, int C>
 static __device__ __forceinline__ int mis_block(const MTS_CONST_AS void *kernarg_, uint32_t *hot_lds, uint32_t wg_base_, uint32_t pid, Counters *cnt) {
-    const uint64_t ka = (uint64_t) (uintptr_t) kernarg_;
-    uint32_t ka_lo = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) ka), ka_hi = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) (ka >> 32));
-    asm volatile("" : "+s"(ka_lo), "+s"(ka_hi));             // opaque: scene loads stay inside this block
-    const MTS_CONST_AS void *kernarg = (const MTS_CONST_AS void *) (uintptr_t) ((uint64_t) ka_lo | ((uint64_t) ka_hi << 32));
-    const uint32_t wg_base = (uint32_t) __builtin_amdgcn_readfirstlane((int) wg_base_);
+    uint32_t wg_base;
+    const MTS_CONST_AS void *kernarg = block_uniforms(kernarg_, wg_base_, wg_base);
     const WgArgs a = cload_k<WgArgs>(kernarg);
     VolpathMisMachine<COUNT, SPEC> vm(a.sc, *cnt);
     PathEnvT<ColdStoreHbm> e; wg_env<WG>(a, wg_base, pid, e);
@@ -635,140 +632,24 @@ static __device__ __forceinline__ int mis_block(const MTS_CONST_AS void *kernarg
     return cls;
 }
 
-// The asynchronous-regrouping driver of volpath_flat.h (volpath_workgroup_async) for the MIS machine: same rings, same claim, same
-// hand-over and stop protocol; it is a second copy rather than a shared template so that the tuned volpath kernel keeps its code.
-template <bool COUNT, bool SPEC, int WG /* paths */, int NT /* threads */>
-DEV void volpathmis_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt) {
-    constexpr int NQ = B_DONE;
-    typedef MisHotStore<WG, SPEC> Hot;
-    static_assert((WG & (WG - 1)) == 0 && NT % 64 == 0 && WG % 64 == 0 && NT <= 2 * WG, "whole waves, power-of-two rings");
-    __shared__ uint32_t hot_lds[Hot::M_COUNT * WG];
-    __shared__ uint16_t q_ids[NQ][WG];
-    __shared__ __attribute__((aligned(8))) uint32_t q_ctl[2 * B_COUNT + 2];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wg_base = blockIdx.x * WG;
-#pragma unroll 1
-    for (int c = 0; c < NQ; ++c) {
-#pragma unroll 1
-        for (uint32_t i = tid; i < (uint32_t) WG; i += NT) q_ids[c][i] = 0xFFFFu;
-    }
-    if (tid < 2u * B_COUNT + 2u) q_ctl[tid] = 0;
-    pm_tables_to_lds(tid);
-    __syncthreads();
-#pragma unroll 1
-    for (uint32_t pid0 = tid; pid0 < (uint32_t) WG; pid0 += NT) {   // ---- initialise the paths (integrator.cpp:198) and queue them
-        const WgArgs a = cload_k<WgArgs>(kernarg);
-        VolpathMisMachine<COUNT, SPEC> vm(a.sc, cnt);
-        PathEnvT<ColdStoreHbm> e; MisPathState<SPEC> p;
-        Hot hs; hs.base = hot_lds + pid0;
-        const bool ok = wg_env<WG>(a, wg_base, pid0, e);
-        p.rng.state = 0; p.rng.inc = 0;
-        p.ray = make_ray(f3s(0.f), f3(0.f, 0.f, 1.f), 0.f, 0.f); p.si.t = pm_inf(); p.si.p = f3s(0.f); p.si.uv.x = p.si.uv.y = 0.f; p.si.shape = -1; p.si.prim = 0;
+// What the ring driver (ring_driver.h) needs to know of `volpathmis`
+template <bool COUNT_, bool SPEC, int WG_>
+struct VolpathMisRing {
+    static constexpr bool COUNT = COUNT_;
+    static constexpr int WG = WG_, HOT_DWORDS = MisHotStore<WG_, SPEC>::M_COUNT, PACKED = MisHotStore<WG_, SPEC>::M_PACKED;
+    typedef MisPathState<SPEC> State;
+    typedef MisHotStore<WG_, SPEC> Hot;
+    typedef VolpathMisMachine<COUNT_, SPEC> Machine;
+    template <int NT> DEV static void check_shape() { static_assert(NT <= 2 * WG_, "up to two threads per path (768 on 512: a third wave per SIMD)"); }
+    DEV static void init_idle(State &p) {
         p.medium = -1; p.res = spec_s(0.f); p.lsp = f3s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;
 #if MTS_SPEC_N != 3
         p.wl = spec_s(0.f);
 #endif
         p.pf = p.pn = p.wn = p.wu = mw_full<SPEC>(1.f);
-        p.st = S_DONE;
-        if (ok) {
-            const uint32_t ppb = a.block_size * a.block_size;
-            p.rng.seed(a.sc.sensor.seed + (uint64_t) e.blk.id * ppb + e.index, PCG32_DEFAULT_STREAM);
-            for (int k = 0; k < 5; ++k) e.cold.f(C_ACC + k) = 0.f;
-            e.cold.f(C_SAMPLE) = __uint_as_float(0u);
-            vm.begin_sample(p, e);
-            vm.top(p, e);
-        }
-        const int cls = vm.classify(p);
-        hs.store(p, cls);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        wga_push<WG>(cls, pid0, true, q_ids, q_ctl);
     }
-    uint32_t poll_ticks = (tid >> 6) * 2048u, idle_naps = 0, idle_t0 = 0;
-    uint32_t idle_limit = MTS_IDLE_TICKS; bool drop_one = false;
-    if (COUNT) {                                              // error-path test hook (volpath_flat.h, MTS_INJECT_SLOT)
-        const uint32_t inj = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) cload_k<WgArgs>(kernarg).counters[MTS_INJECT_SLOT]);
-        if (inj != 0u) { idle_limit = inj; drop_one = blockIdx.x == 0u && tid < 64u; }
-    }
-    const bool record_cost = __builtin_amdgcn_readfirstlane((int) (uint32_t) cload_k<WgArgs>(kernarg).counters[MTS_COST_FLAG]) != 0;   // calibration launch (volpath_flat.h)
-    const long long cost_t0 = record_cost ? clock64() : 0ll;
-#pragma unroll 1
-    for (;;) {
-      uint32_t n = 0, h = 0, spec_slot = 0xFFFFu; int sel = 0; bool finished = false;
-#pragma unroll 1
-      for (;;) {                                                // the claim: snapshot, vote, compare-and-swap (see volpath_flat.h)
-        uint32_t hd = 0, avail = 0;
-        if (lane < (uint32_t) B_COUNT) {
-            hd = __atomic_load_n(&q_ctl[2 * lane], __ATOMIC_RELAXED);
-            const uint32_t tl = __atomic_load_n(&q_ctl[2 * lane + 1], __ATOMIC_RELAXED);
-            avail = tl - hd;
-            if (avail > (uint32_t) WG) avail = 0;
-        }
-        uint32_t key = lane < (uint32_t) NQ ? ((avail << 4) | (15u - lane)) : 0u;
-        key = max(key, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) key, 0x111 /* row_shr:1 */, 0xf, 0xf, true));
-        key = max(key, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) key, 0x112 /* row_shr:2 */, 0xf, 0xf, true));
-        key = max(key, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) key, 0x114 /* row_shr:4 */, 0xf, 0xf, true));
-        const uint32_t top_key = (uint32_t) __builtin_amdgcn_readlane((int) key, 7);
-        const uint32_t best = top_key >> 4; sel = 15 - (int) (top_key & 15u);
-        if (best == 0) {
-            if ((uint32_t) __builtin_amdgcn_readlane((int) avail, B_DONE) == (uint32_t) WG || __atomic_load_n(&q_ctl[2 * B_COUNT], __ATOMIC_RELAXED) != STOP_NONE) { finished = true; break; }
-            if ((poll_ticks += 1u) >= 32768u) {
-                poll_ticks = 0;
-                if (lane == 0 && __hip_atomic_load(cload_k<WgArgs>(kernarg).stop_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)
-                    (void) wga_raise_stop<WG>(q_ctl, STOP_CANCEL);
-            }
-            if (wga_idle_expired(idle_naps, idle_t0, idle_limit)) wga_stall<WG>(3u, B_DONE, 0u, q_ctl, cload_k<WgArgs>(kernarg).counters);   // a lost path: report, do not hang
-            __builtin_amdgcn_s_sleep(2);
-            continue;
-        }
-        idle_naps = 0;
-        n = best < 64u ? best : 64u;
-        h = (uint32_t) __builtin_amdgcn_readlane((int) hd, sel);
-        uint32_t won = 0;
-        if (lane < n) spec_slot = __atomic_load_n(&q_ids[sel][(h + lane) & (uint32_t) (WG - 1)], __ATOMIC_RELAXED);     // tagged slots: read with the claim (volpath_flat.h)
-        if (lane == 0) won = atomicCAS(&q_ctl[2 * sel], h, h + n) == h ? 1u : 0u;
-        if (__builtin_amdgcn_readfirstlane((int) won)) break;
-      }
-      if (finished) break;
-        uint32_t pid = 0xFFFFu;
-        bool mine = lane < n;
-        {
-            uint16_t *slot = &q_ids[sel][(h + lane) & (uint32_t) (WG - 1)];
-            const bool ready = mine && RingSlot<WG>::matches(spec_slot, h + lane);
-            if (ready) pid = RingSlot<WG>::id(spec_slot);
-            if (__builtin_amdgcn_ballot_w64(mine && !ready) != 0ull) {
-                const uint32_t got = wga_tag_wait<WG>(mine && !ready, slot, q_ctl, cload_k<WgArgs>(kernarg).counters, sel, h + lane);
-                if (mine && !ready) pid = got;
-                mine = mine && pid != 0xFFFFu;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        int cls = B_DONE;
-        if (mine) {
-            switch (sel) {                                      // wave-uniform
-                case B_INT: cls = mis_block<COUNT, SPEC, WG, B_INT>(kernarg, hot_lds, wg_base, pid, &cnt); break;
-                case B_MED: cls = mis_block<COUNT, SPEC, WG, B_MED>(kernarg, hot_lds, wg_base, pid, &cnt); break;
-                case B_MEDW: cls = mis_block<COUNT, SPEC, WG, B_MEDW>(kernarg, hot_lds, wg_base, pid, &cnt); break;
-                case B_SCATTER: cls = mis_block<COUNT, SPEC, WG, B_SCATTER>(kernarg, hot_lds, wg_base, pid, &cnt); break;
-                case B_WSURF: cls = mis_block<COUNT, SPEC, WG, B_WSURF>(kernarg, hot_lds, wg_base, pid, &cnt); break;
-                case B_SURF: cls = mis_block<COUNT, SPEC, WG, B_SURF>(kernarg, hot_lds, wg_base, pid, &cnt); break;
-                case B_PHASE: cls = mis_block<COUNT, SPEC, WG, B_PHASE>(kernarg, hot_lds, wg_base, pid, &cnt); break;
-                default: cls = mis_block<COUNT, SPEC, WG, B_NEW>(kernarg, hot_lds, wg_base, pid, &cnt); break;
-            }
-        }
-        if (sel == B_NEW && (poll_ticks += 256u) >= 32768u) {
-            poll_ticks = 0;
-            if (lane == 0 && __hip_atomic_load(cload_k<WgArgs>(kernarg).stop_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)
-                (void) wga_raise_stop<WG>(q_ctl, STOP_CANCEL);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (COUNT && drop_one && cls != B_DONE) { mine = mine && lane != 0u; drop_one = false; }      // the injected lost hand-over (test hook)
-        if (record_cost && mine && cls == B_DONE)
-            atomicAdd(cload_k<WgArgs>(kernarg).counters + MTS_COST_BASE + (wg_base + pid) / MTS_TILE_PIXELS, (unsigned long long) (clock64() - cost_t0));
-        wga_push<WG>(cls, pid, mine, q_ids, q_ctl);
-    }
-    __syncthreads();                                          // stopped: the unfinished pixels' samples go to the film (volpath_flat.h)
-    if (__atomic_load_n(&q_ctl[2 * B_COUNT], __ATOMIC_RELAXED) != STOP_NONE) wg_flush_unfinished<WG, NT>(kernarg, hot_lds, Hot::M_PACKED, wg_base);
-}
+    template <int C> static constexpr auto block = &mis_block<COUNT_, SPEC, WG_, C>;
+};
 
 } // inline namespace
 } // namespace mtsamd

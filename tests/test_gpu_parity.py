@@ -905,7 +905,7 @@ def test_sigint_cancels_a_running_render(gpu_rgb):
 def test_lost_path_is_reported(gpu_rgb, monkeypatch):
     """The error path of the ring drivers: a path whose hand-over is lost leaves the finished count short; the idle
     wait is bounded by elapsed time and mts_render raises with diagnostic code 3 instead of hanging.  The loss is injected through the
-    counting kernel variant (volpath_flat.h, MTS_INJECT_SLOT): one lane of workgroup 0 skips one push; idle bound 0.2 s."""
+    counting kernel variant (ring_driver.h, MTS_INJECT_SLOT): one lane of workgroup 0 skips one push; idle bound 0.2 s."""
     import time
     monkeypatch.setenv("MTSAMD_TEST_INJECT_LOST_PATH", str(20000000))          # ticks of the 100 MHz clock
     for integrator in ("volpath", "volpathmis"):
