@@ -280,7 +280,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
     RenderCache &rc = scene->cache;
     float *d_film = film;
     if (!opts.film_on_device) d_film = (float *) rc.get(BUF_FILM, film_floats * sizeof(float));
-    constexpr int N_COUNTERS = 16;                                   // [0..2] loop counters, [4..9] ring-stall record (volpath_flat.h, MTS_DIAG_BASE), [15] cost-recording flag
+    constexpr int N_COUNTERS = 16;                                   // [0..2] loop counters, [4..9] ring-stall record (ring_driver.h, MTS_DIAG_BASE), [15] cost-recording flag
     // [16 + s]: cost of tile slot s of a calibration launch (16 pixels per tile: block_size^2 / 16 slots per block of the first chunk)
     const uint32_t tiles_per_block = block_size * block_size / 16u;
     unsigned long long *d_counters = (unsigned long long *) rc.get(BUF_COUNTERS, (N_COUNTERS + std::max<size_t>(1, plan.chunks[0].size()) * (tiles_per_block + 1u)) * sizeof(unsigned long long));
@@ -291,7 +291,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
         HIP_CHECK(hipMemsetAsync(d_target, 0, plan.n_slots * film_floats * sizeof(float), stream));
     }
     HIP_CHECK(hipMemsetAsync(d_counters, 0, N_COUNTERS * sizeof(unsigned long long), stream));
-    if (sw.inject_lost_path != 0 && opts.collect_counters)          // test hook of the ring drivers' error path (volpath_flat.h, MTS_INJECT_SLOT): idle bound in ticks
+    if (sw.inject_lost_path != 0 && opts.collect_counters)          // test hook of the ring drivers' error path (ring_driver.h, MTS_INJECT_SLOT): idle bound in ticks
         HIP_CHECK(hipMemcpyAsync(d_counters + 14, &sw.inject_lost_path, sizeof(uint64_t), hipMemcpyHostToDevice, stream));
     rc.events();
     double kernel_ms = 0.0, calibration_ms = 0.0; int launches = 0, calibration_launches = 0, last_variant = 0; bool timed_out = false;
@@ -303,7 +303,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
         if (timeout > 0.f && std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count() > timeout) { timed_out = true; return true; }
         return false;
     };
-    auto throw_on_ring_stall = [](const unsigned long long *c) {    // counters[4..9]: a bounded ring wait gave up (volpath_flat.h): an error, never a hang
+    auto throw_on_ring_stall = [](const unsigned long long *c) {    // counters[4..9]: a bounded ring wait gave up (ring_driver.h): an error, never a hang
         if (c[4] != 0)
             throw std::runtime_error("render kernel: " + std::string(c[4] == 3 ? "lost path (nothing waiting, finished paths = tail" : c[4] == 1 ? "ring stall (consumer" : "ring stall (producer") + ", ring " + std::to_string(c[5]) +
                                      ", index " + std::to_string(c[6]) + ", head " + std::to_string(c[7]) + ", tail " + std::to_string(c[8]) +

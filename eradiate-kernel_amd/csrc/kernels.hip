@@ -260,12 +260,7 @@ __global__ void __launch_bounds__(256, (FLAT && INTEG != NI_PATH) ? 1 : (INTEG =
             if (sc.sensor.wavefront) seed_wavefront_sample(rng, sc.sensor, blk, lx, ly, j);       // gpu_* streams: one per (pixel, sample)
             render_sample<COUNT, INTEG>(sc, rng, blk, lx, ly, film, acc, cnt);
         }
-#if MTS_SPEC_N == 3
-        const size_t film_channels = 5;
-#else
-        const size_t film_channels = (size_t) sc.film_channels;  // X, Y, Z, A, W (+ the bins' AOV channels)
-#endif
-        float *dst = film + film_channels * ((size_t) (blk.oy + (int) ly - sc.sensor.crop_y) * sc.sensor.crop_w + (blk.ox + (int) lx - sc.sensor.crop_x));
+        float *dst = film_entry(sc, blk, lx, ly, as_global(film));
         for (int k = 0; k < 5; ++k) atomicAdd(dst + k, acc[k]);
     }
     if (COUNT) flush_counters(counters, cnt);

@@ -128,7 +128,7 @@ DEV void wg_flush_unfinished(const MTS_CONST_AS void *kernarg, const uint32_t *h
         if ((hot_lds[packed_at * WG + pid] & 15u) == S_DONE) continue;
         PathEnvT<ColdStoreHbm> e;
         if (!wg_env<WG>(a, wg_base, pid, e)) continue;
-        float *own = (float *) (e.film + MTS_FILM_STRIDE(a.sc) * ((size_t) (e.blk.oy + (int) e.ly - a.sc.sensor.crop_y) * a.sc.sensor.crop_w + (e.blk.ox + (int) e.lx - a.sc.sensor.crop_x)));
+        float *own = film_entry(a.sc, e.blk, e.lx, e.ly, e.film);
         for (int k = 0; k < 5; ++k) atomicAdd(own + k, e.cold.f(C_ACC + k));
     }
 }

@@ -286,6 +286,11 @@ DEV void splat_sample_t(const DScene &sc, const DBlock &blk, uint32_t lx, uint32
 
 #endif // MTS_SPEC_N == 3 (the spectral build splats through splat_values_t, integrator_dev.h)
 
+// block -> film (hdrfilm.cpp:207-211): the film entry of pixel (lx, ly) of a block, which its accumulators X, Y, Z, A, W join by atomics
+DEV float *film_entry(const DScene &sc, const DBlock &blk, uint32_t lx, uint32_t ly, MTS_GLOBAL_AS float *film) {
+    return (float *) (film + MTS_FILM_STRIDE(sc) * ((size_t) (blk.oy + (int) ly - sc.sensor.crop_y) * sc.sensor.crop_w + (blk.ox + (int) lx - sc.sensor.crop_x)));
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Per-path state.  "Hot" fields are touched by every tracking step; "cold" fields (ColdStore) only once per
 // sample or per NEE / direct-light walk.
@@ -353,26 +358,109 @@ struct PathEnvT {
 enum { B_INT = 0, B_MED /* free-flight step of the main path */, B_SCATTER, B_WSURF, B_SURF, B_PHASE, B_NEW,
        B_MEDW /* free-flight step of an NEE / direct-light walk */, B_DONE, B_COUNT };
 
-template <bool COUNT>
-struct VolpathMachine {
+// What a MEDIUM block reads of MedStep::info.  constexpr accessors: a lean unit's promises (MTS_TRAITS) are constants the front end folds,
+// as in the #if ladders this replaces (three plain bools: 1086 differing assembly lines in lean unit a).
+struct MediumKind {
+    uint32_t info;
+    constexpr bool spectral() const { return (MTS_TRAITS & MT_MEDIA) ? true : (info & MI_SPECTRAL) != 0; }
+    constexpr bool homogeneous() const { return (MTS_TRAITS & MT_MEDIA) ? false : (MTS_TRAITS & MT_HOMOG) ? true : (info & MI_HOMOGENEOUS) != 0; }
+    constexpr bool grey() const { return (MTS_TRAITS & MT_MEDIA) ? MTS_SPEC_N == 3 : (info & MI_GREY) != 0; }
+};
+// What the two ring machines share (VolpathMachine below, VolpathMisMachine of volpathmis_flat.h), as a CRTP base: M supplies
+// begin_sample, P is its path state.  DIRB: the machine has direct-light walks, whose start (S_DIRB) waits for an intersection too.
+template <class M, class P, bool DIRB>
+struct RingMachine {
     const DScene &sc;
     Counters &cnt;
-    DEV VolpathMachine(const DScene &sc_, Counters &cnt_) : sc(sc_), cnt(cnt_) {}
+    DEV RingMachine(const DScene &sc_, Counters &cnt_) : sc(sc_), cnt(cnt_) {}
     // wavelength context of a path (empty in the rgb build)
 #if MTS_SPEC_N == 3
-    DEV SpecCtx ctx(const PathState &) const { return SpecCtx(); }
+    DEV SpecCtx ctx(const P &) const { return SpecCtx(); }
 #else
-    DEV SpecCtx ctx(const PathState &p) const { SpecCtx cx = make_ctx(sc); cx.wl = p.wl; return cx; }
+    DEV SpecCtx ctx(const P &p) const { SpecCtx cx = make_ctx(sc); cx.wl = p.wl; return cx; }
 #endif
 
     // A freshly spawned ray that cannot reach the scene's bounding box is resolved on the spot (the first
     // test of ShapeKDTree::ray_intersect_scalar, kdtree.h:2095-2098); everything else queues for INTERSECT.
-    DEV void queue_intersection(PathState &p) const {
+    DEV void queue_intersection(P &p) const {
         float bmint, bmaxt;
         bbox_ray_intersect(sc.bbox, p.ray, bmint, bmaxt);
         p.si.t = pm_inf();                                     // si.shape etc. are only read behind hit_valid()
         if (pm_max(p.ray.mint, bmint) <= bmaxt) p.flags |= FL_NEEDS_INT; else p.flags &= ~FL_NEEDS_INT;
     }
+    // the end of an emitter-sampling walk, second half: the parked main path comes back from the cold record
+    template <class E> DEV void resume_main(P &p, const E &e) const {
+        p.mode = M_MAIN; p.medium = __float_as_int(e.cold.f(C_SMED));
+        F3 d = e.cold.get3(C_SD);
+        p.ray.d = d; p.ray.d_rcp = vrcp(d);
+        if (p.flags & FL_FROM_MEDIUM) { p.ray.o = e.cold.get3(C_SO); p.st = S_PHASE; }
+        else { p.si = e.cold.get_hit(); p.st = S_BSDF; }
+    }
+    DEV static bool wants_int(const P &p) { return (p.st == S_MED || p.st == S_SURF || (DIRB && p.st == S_DIRB)) && (p.flags & FL_NEEDS_INT); }
+    // block this path waits for (valid once top() has run)
+    DEV static int classify(const P &p) {
+        if (p.st == S_DONE) return B_DONE;
+        if (wants_int(p)) return B_INT;
+        if (p.st == S_MED) return p.mode == M_MAIN ? B_MED : B_MEDW;
+        if (p.st == S_SCATTER) return B_SCATTER;
+        if (p.st == S_SURF) return p.mode == M_MAIN ? B_SURF : B_WSURF;
+        if (p.st == S_BSDF) return B_SURF;
+        if (p.st == S_PHASE) return B_PHASE;
+        return B_NEW;
+    }
+    // ================================================================= INTERSECT, the core (volpath.cpp:109,182,241,298,339,395,425)
+    DEV bool intersect(P &p) const {
+        if (!wants_int(p)) return false;
+        p.si = ray_intersect(sc, p.ray);
+        p.flags &= ~FL_NEEDS_INT;
+        return true;
+    }
+    // ================================================================= NEW: finish a sample, start the next (integrator.cpp:265-288)
+    // (The per-lane kernels keep their own result -> XYZ -> splat lines, kernels.hip.  One function for them and this block, taking a record:
+    // v_spectral_lean_p::render_kernel<false, true, 0> 560 -> 576 B of scratch, <true, true, 0> 245 -> 253 SGPR spills and 560 -> 576 B.
+    // One for the per-lane kernels alone, taking scalars: <false, true, 0> 255 -> 257 SGPR spills, 560 -> 576 B.)
+    template <class E> DEV void blk_new(P &p, const E &e) const {
+        if (p.st != S_NEW) return;
+        F2 position_sample; position_sample.x = e.cold.f(C_POS); position_sample.y = e.cold.f(C_POS + 1);
+        float acc[5];                                          // summed in sample order like the block entry (imageblock.cpp:163-168)
+        for (int k = 0; k < 5; ++k) acc[k] = e.cold.f(C_ACC + k);
+#if MTS_SPEC_N == 3
+        splat_sample_t<false>(sc, e.blk, e.lx, e.ly, position_sample, f3s(e.cold.f(C_RAYW)) * p.res, (p.flags & FL_VALID_RAY) != 0, e.film, acc);
+#else
+        {
+            float wav_weight; (void) sample_wavelengths(0.f, wav_weight);
+            const Spec ww = sc.srf >= 0 ? srf_weights_of(sc, p.wl) : spec_s(wav_weight);
+            const Spec L = (ww * e.cold.f(C_RAYW)) * p.res;             // ray_weight = wav_weight (x the sensor's grey weight), integrator.cpp:265
+            float xyz[3];
+            spectrum_to_xyz(sc.cie, L, p.wl, xyz);                      // integrator.cpp:266-269
+            const float v[5] = { xyz[0], xyz[1], xyz[2], (p.flags & FL_VALID_RAY) != 0 ? 1.f : 0.f, 1.f };
+            if (sc.bin_count == 0) splat_values_t<false>(sc, e.blk, e.lx, e.ly, position_sample, v, e.film, acc);
+            else splat_values_bins(sc, e.blk, e.lx, e.ly, position_sample, v, p.res, p.wl, e.film, acc);
+        }
+#endif
+        const uint32_t sample_idx = __float_as_uint(e.cold.f(C_SAMPLE)) + 1u;
+        if (sample_idx == e.sample_count) {                    // block -> film (hdrfilm.cpp:207-211)
+            float *own = film_entry(sc, e.blk, e.lx, e.ly, e.film);
+            for (int k = 0; k < 5; ++k) atomicAdd(own + k, acc[k]);
+            p.st = S_DONE;
+        } else {
+            for (int k = 0; k < 5; ++k) e.cold.f(C_ACC + k) = acc[k];
+            e.cold.f(C_SAMPLE) = __uint_as_float(sample_idx);
+            static_cast<const M &>(*this).begin_sample(p, e);
+        }
+    }
+};
+
+template <bool COUNT>
+struct VolpathMachine : RingMachine<VolpathMachine<COUNT>, PathState, true> {
+    typedef RingMachine<VolpathMachine<COUNT>, PathState, true> Base;
+    using Base::sc; using Base::cnt; using Base::ctx; using Base::queue_intersection; using Base::wants_int;
+    DEV VolpathMachine(const DScene &sc_, Counters &cnt_) : Base(sc_, cnt_) {}
+    // The head of a sample (the draws up to the camera ray) stays written out here, in VolpathMisMachine::begin_sample and in render_sample
+    // and path_pixel_flat (kernels.hip).  As one function returning a record, called from the four, 24 of the 72 kernels need more:
+    // scratch of the spectral ring kernels 28 -> 60 B (v_spectral_lean::render_kernel_wga<false, 256, 256, 3>) and 496 -> 528 B (v_spectral::),
+    // spilled VGPRs of the flat `path` kernels 98 -> 138 (v_rgb::render_kernel<false, true, 0>) and 40 -> 105 (v_spectral::).  Filling
+    // references, or as a member of RingMachine holding these very lines, it still changed the ring kernels of lean unit a.
     template <class E> DEV void begin_sample(PathState &p, const E &e) const {      // integrator.cpp:242-264, volpath.cpp:48-71
         const DSensor &se = sc.sensor;
         const float px = (float) (e.lx + (uint32_t) e.blk.ox), py = (float) (e.ly + (uint32_t) e.blk.oy);
@@ -415,11 +503,7 @@ struct VolpathMachine {
     template <class E> DEV void end_nee(PathState &p, const E &e) const {
         Spec emitted = p.trans * e.cold.get_spec(C_EMIT);
         p.res = p.res + e.cold.get_spec(C_CW) * emitted;
-        p.mode = M_MAIN; p.medium = __float_as_int(e.cold.f(C_SMED));
-        F3 d = e.cold.get3(C_SD);
-        p.ray.d = d; p.ray.d_rcp = vrcp(d);
-        if (p.flags & FL_FROM_MEDIUM) { p.ray.o = e.cold.get3(C_SO); p.st = S_PHASE; }
-        else { p.si = e.cold.get_hit(); p.st = S_BSDF; }
+        this->resume_main(p, e);
     }
     // direct-light walk finished (volpath.cpp:464 + :246-252): MIS-weighted emitter hit, resume the main path
     template <class E> DEV void end_direct(PathState &p, const E &e, Spec emitter_val, float emitter_pdf) const {
@@ -453,57 +537,9 @@ struct VolpathMachine {
             p.st = p.medium >= 0 ? S_MED : S_SURF;
         }
     }
-    DEV static bool wants_int(const PathState &p) { return (p.st == S_MED || p.st == S_SURF || p.st == S_DIRB) && (p.flags & FL_NEEDS_INT); }
-    // block this path waits for (valid once top() has run)
-    DEV static int classify(const PathState &p) {
-        if (p.st == S_DONE) return B_DONE;
-        if (wants_int(p)) return B_INT;
-        if (p.st == S_MED) return p.mode == M_MAIN ? B_MED : B_MEDW;
-        if (p.st == S_SCATTER) return B_SCATTER;
-        if (p.st == S_SURF) return p.mode == M_MAIN ? B_SURF : B_WSURF;
-        if (p.st == S_BSDF) return B_SURF;
-        if (p.st == S_PHASE) return B_PHASE;
-        return B_NEW;
-    }
-
-    // ================================================================= NEW: finish a sample, start the next (integrator.cpp:265-288)
-    template <class E> DEV void blk_new(PathState &p, const E &e) const {
-        if (p.st != S_NEW) return;
-        const DSensor &se = sc.sensor;
-        F2 position_sample; position_sample.x = e.cold.f(C_POS); position_sample.y = e.cold.f(C_POS + 1);
-        float acc[5];                                          // summed in sample order like the block entry (imageblock.cpp:163-168)
-        for (int k = 0; k < 5; ++k) acc[k] = e.cold.f(C_ACC + k);
-#if MTS_SPEC_N == 3
-        splat_sample_t<false>(sc, e.blk, e.lx, e.ly, position_sample, f3s(e.cold.f(C_RAYW)) * p.res, (p.flags & FL_VALID_RAY) != 0, e.film, acc);
-#else
-        {
-            float wav_weight; (void) sample_wavelengths(0.f, wav_weight);
-            const Spec ww = sc.srf >= 0 ? srf_weights_of(sc, p.wl) : spec_s(wav_weight);
-            const Spec L = (ww * e.cold.f(C_RAYW)) * p.res;             // ray_weight = wav_weight (x the sensor's grey weight), integrator.cpp:265
-            float xyz[3];
-            spectrum_to_xyz(sc.cie, L, p.wl, xyz);                      // integrator.cpp:266-269
-            const float v[5] = { xyz[0], xyz[1], xyz[2], (p.flags & FL_VALID_RAY) != 0 ? 1.f : 0.f, 1.f };
-            if (sc.bin_count == 0) splat_values_t<false>(sc, e.blk, e.lx, e.ly, position_sample, v, e.film, acc);
-            else splat_values_bins(sc, e.blk, e.lx, e.ly, position_sample, v, p.res, p.wl, e.film, acc);
-        }
-#endif
-        const uint32_t sample_idx = __float_as_uint(e.cold.f(C_SAMPLE)) + 1u;
-        if (sample_idx == e.sample_count) {                    // block -> film (hdrfilm.cpp:207-211)
-            float *own = (float *) (e.film + MTS_FILM_STRIDE(sc) * ((size_t) (e.blk.oy + (int) e.ly - se.crop_y) * se.crop_w + (e.blk.ox + (int) e.lx - se.crop_x)));
-            for (int k = 0; k < 5; ++k) atomicAdd(own + k, acc[k]);
-            p.st = S_DONE;
-        } else {
-            for (int k = 0; k < 5; ++k) e.cold.f(C_ACC + k) = acc[k];
-            e.cold.f(C_SAMPLE) = __uint_as_float(sample_idx);
-            begin_sample(p, e);
-        }
-    }
     // ================================================================= INTERSECT (volpath.cpp:109,182,241,298,339,395,425)
     template <class E> DEV void blk_int(PathState &p, const E &e) const {
-        if (!wants_int(p)) return;
-        p.si = ray_intersect(sc, p.ray);
-        p.flags &= ~FL_NEEDS_INT;
-        start_direct(p, e);
+        if (this->intersect(p)) start_direct(p, e);
     }
     template <class E> DEV void start_direct(PathState &p, const E &e) const {      // volpath.cpp:239-245: the direct-light walk runs on a copy
         if (p.st != S_DIRB || (p.flags & FL_NEEDS_INT)) return;
@@ -525,13 +561,8 @@ struct VolpathMachine {
             mi = medium_step<COUNT>(sc, cload(sc.media + mu), p.ray, u, p.channel, MODEK == 0 ? true : (MODEK == 1 ? false : p.mode == M_MAIN), cnt MTS_CX);
         WATERFALL_END
         if (p.si.t < mi.t) mi.t = pm_inf();                    // volpath.cpp:112 / :300 / :397
-#if MTS_TRAITS & MT_MEDIA
-        const bool spectral = true, homogeneous = false, grey = MTS_SPEC_N == 3;
-#elif MTS_TRAITS & MT_HOMOG
-        const bool spectral = (mi.info & MI_SPECTRAL) != 0, homogeneous = true, grey = (mi.info & MI_GREY) != 0;
-#else
-        const bool spectral = (mi.info & MI_SPECTRAL) != 0, homogeneous = (mi.info & MI_HOMOGENEOUS) != 0, grey = (mi.info & MI_GREY) != 0;
-#endif
+        const MediumKind mk = { mi.info };
+        const bool spectral = mk.spectral(), homogeneous = mk.homogeneous(), grey = mk.grey();
         const Spec sigma_n = homogeneous ? spec_s(0.f) : mi.combined - mi.sigma_t;
         const uint32_t channel = p.channel;
         const bool is_main = MODEK == 0 ? true : (MODEK == 1 ? false : p.mode == M_MAIN), is_nee = MODEK == 0 ? false : p.mode == M_NEE;
@@ -764,7 +795,7 @@ struct VolpathMachine {
     }
     template <bool DEFER = false, bool SPLIT = false, class E> DEV void run(PathState &p, const E &e, int sel) const {
         switch (sel) {
-            case B_NEW: blk_new(p, e); break;
+            case B_NEW: this->blk_new(p, e); break;
             case B_INT: blk_int(p, e); break;
             case B_MED: if (SPLIT) blk_med<DEFER, 0>(p, e); else blk_med<DEFER, -1>(p, e); break;
             case B_MEDW: if (SPLIT) blk_med<DEFER, 1>(p, e); else blk_med<DEFER, -1>(p, e); break;
@@ -814,7 +845,7 @@ DEV void volpath_pixel_flat(const DScene &sc, Pcg32 &rng, const DBlock &blk, uin
         vm.run(p, e, sel);
     }
     if (p.st != S_DONE) {                                     // stopped (should_stop()): the finished samples of this pixel go to the film, integrator.cpp:120-130
-        float *own = (float *) (e.film + 5 * ((size_t) (blk.oy + (int) ly - sc.sensor.crop_y) * sc.sensor.crop_w + (blk.ox + (int) lx - sc.sensor.crop_x)));
+        float *own = film_entry(sc, blk, lx, ly, e.film);
         for (int k = 0; k < 5; ++k) atomicAdd(own + k, e.cold.f(C_ACC + k));
     }
 #if defined(MTSAMD_BLOCKSTATS)
@@ -879,8 +910,11 @@ template <> struct ClassFields<B_PHASE> {
                               store = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_THR | (MTS_FUSE_INT ? G_SIX : 0u);
     static constexpr bool defer = true; };
 
-template <int WG>
-struct HotStore {
+// The front of a ring machine's hot store, shared by HotStore below and MisHotStore (volpathmis_flat.h): the LDS accessors, the packed
+// dword, and the eight field groups G_RNG .. G_MED over the sixteen-dword layout H_RNG .. H_PACKED.  SIX: where the machine keeps the
+// rest of the hit (behind its own fields).  The packed dword is stored / unpacked by the derived store, where its own order has it.
+template <int WG, int SIX>
+struct HotFront {
     uint32_t *base;                                          // &lds[0][path]
     DEV uint32_t &u(int k) const { return base[k * WG]; }
     DEV float f(int k) const { return __uint_as_float(base[k * WG]); }
@@ -894,23 +928,45 @@ struct HotStore {
     DEV void put_spec(int k, Spec v) const { putf(k, v.x); putf(k + 1, v.y); putf(k + 2, v.z); putf(k + 3, v.w); }
     DEV Spec get_spec(int k) const { return spec4(f(k), f(k + 1), f(k + 2), f(k + 3)); }
 #endif
-    DEV static uint32_t pack(const PathState &p, int cls) {
+    template <class P> DEV static uint32_t pack(const P &p, int cls) {
         return p.st | (p.mode << 4) | (p.channel << 6) | (p.flags << 8) | ((uint32_t) cls << 13) | ((p.depth < 32767u ? p.depth : 32767u) << 17);
     }
     DEV static int cls_of(uint32_t packed) { return (int) (packed >> 13) & 15; }
-    DEV static void unpack(uint32_t pk, PathState &p) {
+    template <class P> DEV static void unpack(uint32_t pk, P &p) {
         p.st = pk & 15u; p.mode = (pk >> 4) & 3u; p.channel = (pk >> 6) & 3u; p.flags = (pk >> 8) & 31u; p.depth = pk >> 17;
     }
     // field groups: a block loads / stores only what it can read / write (ClassFields below)
-    template <uint32_t M> DEV void store_m(const PathState &p, int cls) const {
+    template <uint32_t M, class P> DEV void store_front(const P &p) const {
         if (M & G_RNG) { u(H_RNG) = (uint32_t) p.rng.state; u(H_RNG + 1) = (uint32_t) (p.rng.state >> 32); }
         if (M & G_O) put3(H_O, p.ray.o);
         if (M & G_D) { put3(H_D, p.ray.d); put3(H_DRCP, p.ray.d_rcp); }
         if (M & G_MINT) putf(H_MINT, p.ray.mint);
         if (M & G_MAXT) putf(H_MAXT, p.ray.maxt);
         if (M & G_SIT) putf(H_SIT, p.si.t);
-        if (M & G_SIX) { put3(H_SIX, p.si.p); putf(H_SIX + 3, p.si.uv.x); putf(H_SIX + 4, p.si.uv.y); u(H_SIX + 5) = (uint32_t) p.si.shape; u(H_SIX + 6) = (uint32_t) p.si.prim; }
+        if (M & G_SIX) { put3(SIX, p.si.p); putf(SIX + 3, p.si.uv.x); putf(SIX + 4, p.si.uv.y); u(SIX + 5) = (uint32_t) p.si.shape; u(SIX + 6) = (uint32_t) p.si.prim; }
         if (M & G_MED) u(H_MEDIUM) = (uint32_t) p.medium;
+    }
+    // ... and loads them; a block that does not load a group finds idle values in its place.  (As conditional loads over idle values,
+    // the form of load_add: lean unit a's volpath kernels 122 -> 121 and 128 -> 127 VGPRs, 23000 differing assembly lines.)
+    template <uint32_t M, class P> DEV void load_front(P &p) const {
+        p.rng.state = 0; p.rng.inc = (PCG32_DEFAULT_STREAM << 1u) | 1u;
+        if (M & G_RNG) p.rng.state = (uint64_t) u(H_RNG) | ((uint64_t) u(H_RNG + 1) << 32);
+        p.ray.o = (M & G_O) ? get3(H_O) : f3s(0.f);
+        p.ray.d = (M & G_D) ? get3(H_D) : f3s(0.f); p.ray.d_rcp = (M & G_D) ? get3(H_DRCP) : f3s(0.f);
+        p.ray.mint = (M & G_MINT) ? f(H_MINT) : 0.f; p.ray.maxt = (M & G_MAXT) ? f(H_MAXT) : 0.f;
+        p.si.t = (M & G_SIT) ? f(H_SIT) : pm_inf();
+        p.si.p = f3s(0.f); p.si.uv.x = p.si.uv.y = 0.f; p.si.shape = -1; p.si.prim = 0;
+        if (M & G_SIX) { p.si.p = get3(SIX); p.si.uv.x = f(SIX + 3); p.si.uv.y = f(SIX + 4); p.si.shape = (int) u(SIX + 5); p.si.prim = (int) u(SIX + 6); }
+        p.medium = (M & G_MED) ? (int) u(H_MEDIUM) : -1;
+    }
+};
+
+template <int WG>
+struct HotStore : HotFront<WG, H_SIX> {
+    typedef HotFront<WG, H_SIX> Front;
+    using Front::u; using Front::f; using Front::putf; using Front::get3; using Front::put_spec; using Front::get_spec;
+    template <uint32_t M> DEV void store_m(const PathState &p, int cls) const {
+        this->template store_front<M>(p);
         if (M & G_THR) put_spec(H_THR, p.thr);
         if (M & G_RES) put_spec(H_RES, p.res);
         if (M & G_ETA) putf(H_ETA, p.eta);
@@ -920,25 +976,17 @@ struct HotStore {
 #endif
         if (M & G_WA) putf(H_WA, p.wa);
         if (M & G_WB) putf(H_WB, p.wb);
-        u(H_PACKED) = pack(p, cls);
+        u(H_PACKED) = Front::pack(p, cls);
     }
     template <uint32_t M> DEV void load_m(PathState &p) const {
-        p.rng.state = 0; p.rng.inc = (PCG32_DEFAULT_STREAM << 1u) | 1u;
-        if (M & G_RNG) p.rng.state = (uint64_t) u(H_RNG) | ((uint64_t) u(H_RNG + 1) << 32);
-        p.ray.o = (M & G_O) ? get3(H_O) : f3s(0.f);
-        p.ray.d = (M & G_D) ? get3(H_D) : f3s(0.f); p.ray.d_rcp = (M & G_D) ? get3(H_DRCP) : f3s(0.f);
-        p.ray.mint = (M & G_MINT) ? f(H_MINT) : 0.f; p.ray.maxt = (M & G_MAXT) ? f(H_MAXT) : 0.f;
-        p.si.t = (M & G_SIT) ? f(H_SIT) : pm_inf();
-        p.si.p = f3s(0.f); p.si.uv.x = p.si.uv.y = 0.f; p.si.shape = -1; p.si.prim = 0;
-        if (M & G_SIX) { p.si.p = get3(H_SIX); p.si.uv.x = f(H_SIX + 3); p.si.uv.y = f(H_SIX + 4); p.si.shape = (int) u(H_SIX + 5); p.si.prim = (int) u(H_SIX + 6); }
-        p.medium = (M & G_MED) ? (int) u(H_MEDIUM) : -1;
+        this->template load_front<M>(p);
         p.thr = (M & G_THR) ? get_spec(H_THR) : spec_s(0.f); p.res = (M & G_RES) ? get_spec(H_RES) : spec_s(0.f);
         p.eta = (M & G_ETA) ? f(H_ETA) : 1.f;
         p.trans = (M & G_TRANS) ? get_spec(H_TRANS) : spec_s(0.f); p.wa = (M & G_WA) ? f(H_WA) : 0.f; p.wb = (M & G_WB) ? f(H_WB) : 0.f;
 #if MTS_SPEC_N != 3
         p.wl = (M & G_WL) ? get_spec(H_WL) : spec_s(0.f);
 #endif
-        unpack(u(H_PACKED), p);
+        Front::unpack(u(H_PACKED), p);
     }
     // the fields of M on top of a state that already holds the others (st / mode / flags / depth stay as the registers have them)
     template <uint32_t M> DEV void load_add(PathState &p) const {

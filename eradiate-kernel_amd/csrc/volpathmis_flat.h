@@ -44,24 +44,12 @@ struct MisPathState {
 };
 
 template <bool COUNT, bool SPEC>
-struct VolpathMisMachine {
+struct VolpathMisMachine : RingMachine<VolpathMisMachine<COUNT, SPEC>, MisPathState<SPEC>, false> {
     typedef MisPathState<SPEC> P;
     typedef MisWeights<SPEC> W;
-    const DScene &sc;
-    Counters &cnt;
-    DEV VolpathMisMachine(const DScene &sc_, Counters &cnt_) : sc(sc_), cnt(cnt_) {}
-#if MTS_SPEC_N == 3
-    DEV SpecCtx ctx(const P &) const { return SpecCtx(); }
-#else
-    DEV SpecCtx ctx(const P &p) const { SpecCtx cx = make_ctx(sc); cx.wl = p.wl; return cx; }
-#endif
-
-    DEV void queue_intersection(P &p) const {                  // as VolpathMachine::queue_intersection
-        float bmint, bmaxt;
-        bbox_ray_intersect(sc.bbox, p.ray, bmint, bmaxt);
-        p.si.t = pm_inf();
-        if (pm_max(p.ray.mint, bmint) <= bmaxt) p.flags |= FL_NEEDS_INT; else p.flags &= ~FL_NEEDS_INT;
-    }
+    typedef RingMachine<VolpathMisMachine<COUNT, SPEC>, P, false> Base;
+    using Base::sc; using Base::cnt; using Base::ctx; using Base::queue_intersection;
+    DEV VolpathMisMachine(const DScene &sc_, Counters &cnt_) : Base(sc_, cnt_) {}
     // the parked pair: one 128-byte record per path behind the cold records, written and read by one lane as whole lines
     template <class E> DEV static void park_put(const E &e, const W &a, const W &b) {
         constexpr int NR = SPEC ? MTS_SPEC_N : 1;
@@ -134,11 +122,7 @@ struct VolpathMisMachine {
         update_weights(p.wu, pdfv, fval, p.channel, true);
         p.res = p.res + mis_weight_w(p.wn, p.wu) * emitted;
         park_get(e, p.pf, p.pn);                               // ... and comes back
-        p.mode = M_MAIN; p.medium = __float_as_int(e.cold.f(C_SMED));
-        F3 d = e.cold.get3(C_SD);
-        p.ray.d = d; p.ray.d_rcp = vrcp(d);
-        if (p.flags & FL_FROM_MEDIUM) { p.ray.o = e.cold.get3(C_SO); p.st = S_PHASE; }
-        else { p.si = e.cold.get_hit(); p.st = S_BSDF; }
+        this->resume_main(p, e);
     }
     // A block that runs on a partial state (MisClassFields) leaves the end of a walk to finish(), which runs on the full state
     template <bool DEFER, class E> DEV void nee_done(P &p, const E &e) const { if (DEFER) p.st = S_ENDNEE; else end_nee(p, e); }
@@ -165,56 +149,8 @@ struct VolpathMisMachine {
             else { if (COUNT) cnt.n_nee_step++; p.st = p.medium >= 0 ? S_MED : S_SURF; }
         }
     }
-    DEV static bool wants_int(const P &p) { return (p.st == S_MED || p.st == S_SURF) && (p.flags & FL_NEEDS_INT); }
-    DEV static int classify(const P &p) {
-        if (p.st == S_DONE) return B_DONE;
-        if (wants_int(p)) return B_INT;
-        if (p.st == S_MED) return p.mode == M_MAIN ? B_MED : B_MEDW;
-        if (p.st == S_SCATTER) return B_SCATTER;
-        if (p.st == S_SURF) return p.mode == M_MAIN ? B_SURF : B_WSURF;
-        if (p.st == S_BSDF) return B_SURF;
-        if (p.st == S_PHASE) return B_PHASE;
-        return B_NEW;
-    }
-
-    // ================================================================= NEW (integrator.cpp:265-288)
-    template <class E> DEV void blk_new(P &p, const E &e) const {
-        if (p.st != S_NEW) return;
-        const DSensor &se = sc.sensor;
-        F2 position_sample; position_sample.x = e.cold.f(C_POS); position_sample.y = e.cold.f(C_POS + 1);
-        float acc[5];
-        for (int k = 0; k < 5; ++k) acc[k] = e.cold.f(C_ACC + k);
-#if MTS_SPEC_N == 3
-        splat_sample_t<false>(sc, e.blk, e.lx, e.ly, position_sample, f3s(e.cold.f(C_RAYW)) * p.res, (p.flags & FL_VALID_RAY) != 0, e.film, acc);
-#else
-        {
-            float wav_weight; (void) sample_wavelengths(0.f, wav_weight);
-            const Spec ww = sc.srf >= 0 ? srf_weights_of(sc, p.wl) : spec_s(wav_weight);      // a sensor response function: weights recovered from the wavelengths (volpath_flat.h)
-            const Spec L = (ww * e.cold.f(C_RAYW)) * p.res;             // ray_weight = wav_weight (x the sensor's grey weight), integrator.cpp:265
-            float xyz[3];
-            spectrum_to_xyz(sc.cie, L, p.wl, xyz);                      // integrator.cpp:266-269
-            const float v[5] = { xyz[0], xyz[1], xyz[2], (p.flags & FL_VALID_RAY) != 0 ? 1.f : 0.f, 1.f };
-            if (sc.bin_count == 0) splat_values_t<false>(sc, e.blk, e.lx, e.ly, position_sample, v, e.film, acc);
-            else splat_values_bins(sc, e.blk, e.lx, e.ly, position_sample, v, p.res, p.wl, e.film, acc);      // nbins / bins around volpathmis (round 4)
-        }
-#endif
-        const uint32_t sample_idx = __float_as_uint(e.cold.f(C_SAMPLE)) + 1u;
-        if (sample_idx == e.sample_count) {
-            float *own = (float *) (e.film + MTS_FILM_STRIDE(sc) * ((size_t) (e.blk.oy + (int) e.ly - se.crop_y) * se.crop_w + (e.blk.ox + (int) e.lx - se.crop_x)));
-            for (int k = 0; k < 5; ++k) atomicAdd(own + k, acc[k]);
-            p.st = S_DONE;
-        } else {
-            for (int k = 0; k < 5; ++k) e.cold.f(C_ACC + k) = acc[k];
-            e.cold.f(C_SAMPLE) = __uint_as_float(sample_idx);
-            begin_sample(p, e);
-        }
-    }
     // ================================================================= INTERSECT
-    template <class E> DEV void blk_int(P &p, const E &) const {
-        if (!wants_int(p)) return;
-        p.si = ray_intersect(sc, p.ray);
-        p.flags &= ~FL_NEEDS_INT;
-    }
+    template <class E> DEV void blk_int(P &p, const E &) const { this->intersect(p); }
     // ================================================================= MEDIUM step of the path (volpathmis.cpp:165-245)
     template <class E> DEV void blk_med(P &p, const E &) const {
         if (p.st != S_MED || p.mode != M_MAIN || (p.flags & FL_NEEDS_INT)) return;
@@ -226,13 +162,8 @@ struct VolpathMisMachine {
             mi = medium_step<COUNT>(sc, cload(sc.media + mu), p.ray, u, channel, true, cnt MTS_CX);
         WATERFALL_END
         if (p.si.t < mi.t) mi.t = pm_inf();
-#if MTS_TRAITS & MT_MEDIA
-        const bool spectral = true, homogeneous = false, grey = MTS_SPEC_N == 3;
-#elif MTS_TRAITS & MT_HOMOG
-        const bool spectral = (mi.info & MI_SPECTRAL) != 0, homogeneous = true, grey = (mi.info & MI_GREY) != 0;
-#else
-        const bool spectral = (mi.info & MI_SPECTRAL) != 0, homogeneous = (mi.info & MI_HOMOGENEOUS) != 0, grey = (mi.info & MI_GREY) != 0;
-#endif
+        const MediumKind mk = { mi.info };
+        const bool spectral = mk.spectral(), homogeneous = mk.homogeneous(), grey = mk.grey();
         const Spec sigma_n = homogeneous ? spec_s(0.f) : mi.combined - mi.sigma_t;
         if (spectral) {
             float t = pm_min(mi.t, p.si.t) - mi.mint;                                  // medium.cpp:77-89
@@ -319,13 +250,8 @@ struct VolpathMisMachine {
             mi = medium_step<COUNT>(sc, cload(sc.media + mu), p.ray, u, channel, false, cnt MTS_CX);
         WATERFALL_END
         if (p.si.t < mi.t) mi.t = pm_inf();
-#if MTS_TRAITS & MT_MEDIA
-        const bool spectral = true, homogeneous = false, grey = MTS_SPEC_N == 3;
-#elif MTS_TRAITS & MT_HOMOG
-        const bool spectral = (mi.info & MI_SPECTRAL) != 0, homogeneous = true, grey = (mi.info & MI_GREY) != 0;
-#else
-        const bool spectral = (mi.info & MI_SPECTRAL) != 0, homogeneous = (mi.info & MI_HOMOGENEOUS) != 0, grey = (mi.info & MI_GREY) != 0;
-#endif
+        const MediumKind mk = { mi.info };
+        const bool spectral = mk.spectral(), homogeneous = mk.homogeneous(), grey = mk.grey();
         const Spec sigma_n = homogeneous ? spec_s(0.f) : mi.combined - mi.sigma_t;
         const float remaining_dist = p.ray.maxt;
         if (spectral) {
@@ -477,7 +403,7 @@ struct VolpathMisMachine {
     }
     template <bool DEFER, class E> DEV void run(P &p, const E &e, int sel) const {
         switch (sel) {
-            case B_NEW: blk_new(p, e); break;
+            case B_NEW: this->blk_new(p, e); break;
             case B_INT: blk_int(p, e); break;
             case B_MED: blk_med(p, e); break;
             case B_MEDW: blk_medw<DEFER>(p, e); break;
@@ -492,7 +418,7 @@ struct VolpathMisMachine {
 
 // Hot state in LDS, struct of arrays over the workgroup's paths (as HotStore of volpath_flat.h).  A block loads / stores only the field
 // groups its class can read / write (MisClassFields); at two waves per SIMD the register budget of 256 VGPRs holds the whole state.
-enum : uint32_t { K_RNG = 1, K_O = 2, K_D = 4 /* d and 1/d */, K_MINT = 8, K_MAXT = 16, K_SIT = 32, K_SIX = 64 /* rest of si */, K_MED = 128,
+enum : uint32_t { K_RNG = G_RNG, K_O = G_O, K_D = G_D, K_MINT = G_MINT, K_MAXT = G_MAXT, K_SIT = G_SIT, K_SIX = G_SIX, K_MED = G_MED,   // HotFront's groups
                   K_PF = 256, K_PN = 512, K_WN = 1024, K_WU = 2048, K_RES = 4096, K_LSP = 8192, K_ETA = 16384, K_WA = 32768, K_WB = 65536,
 #if MTS_SPEC_N == 3
                   K_WL = 0, K_ALL = 131071 };
@@ -521,74 +447,47 @@ template <> struct MisClassFields<B_PHASE> {
                               store = K_RNG | K_O | K_D | K_MINT | K_MAXT | K_SIT | K_PF | K_PN;
     static constexpr bool defer = true; };
 
+// MisHotStore's own dwords, behind HotFront's sixteen (H_RNG .. H_PACKED)
+enum { MH_WA = 16, MH_WB = 17, MH_ETA = 18, MH_RES = 19, MH_LSP = MH_RES + MTS_SPEC_DW, MH_SIX = MH_LSP + 3,
+#if MTS_SPEC_N == 3
+       MH_W = 32 };
+#else
+       MH_WL = MH_SIX + 7, MH_W = MH_WL + 4 };                      // 37
+#endif
 template <int WG, bool SPEC>
-struct MisHotStore {
+struct MisHotStore : HotFront<WG, MH_SIX> {
+    typedef HotFront<WG, MH_SIX> Front;
+    using Front::u; using Front::f; using Front::putf; using Front::put3; using Front::get3; using Front::put_spec; using Front::get_spec;
     static constexpr int NW = SPEC ? MTS_SPEC_N * MTS_SPEC_N : MTS_SPEC_N;      // floats per weight matrix
-    enum { M_RNG = 0, M_O = 2, M_D = 5, M_DRCP = 8, M_MINT = 11, M_MAXT = 12, M_SIT = 13, M_MEDIUM = 14, M_PACKED = 15, M_WA = 16, M_WB = 17,
-           M_ETA = 18, M_RES = 19, M_LSP = M_RES + MTS_SPEC_DW, M_SIX = M_LSP + 3,
-#if MTS_SPEC_N == 3
-           M_W = 32,
-#else
-           M_WL = M_SIX + 7, M_W = M_WL + 4,                    // 37
-#endif
-           M_COUNT = M_W + 2 * NW };            // two matrix slots: A = p_over_f or the walk's p_over_f_uni, B = p_over_f_nee of the path or of the walk
-    uint32_t *base;
-    DEV uint32_t &u(int k) const { return base[k * WG]; }
-    DEV float f(int k) const { return __uint_as_float(base[k * WG]); }
-    DEV void putf(int k, float v) const { base[k * WG] = __float_as_uint(v); }
-    DEV void put3(int k, F3 v) const { putf(k, v.x); putf(k + 1, v.y); putf(k + 2, v.z); }
-    DEV F3 get3(int k) const { return f3(f(k), f(k + 1), f(k + 2)); }
-#if MTS_SPEC_N == 3
-    DEV void put_spec(int k, Spec v) const { put3(k, v); }
-    DEV Spec get_spec(int k) const { return get3(k); }
-#else
-    DEV void put_spec(int k, Spec v) const { putf(k, v.x); putf(k + 1, v.y); putf(k + 2, v.z); putf(k + 3, v.w); }
-    DEV Spec get_spec(int k) const { return spec4(f(k), f(k + 1), f(k + 2), f(k + 3)); }
-#endif
+    enum { MH_COUNT = MH_W + 2 * NW };            // two matrix slots: A = p_over_f or the walk's p_over_f_uni, B = p_over_f_nee of the path or of the walk
     DEV void putw(int k, const MisWeights<SPEC> &w) const { for (int i = 0; i < NW / MTS_SPEC_N; ++i) put_spec(k + MTS_SPEC_N * i, w.r[i]); }
     DEV MisWeights<SPEC> getw(int k) const { MisWeights<SPEC> w; for (int i = 0; i < NW / MTS_SPEC_N; ++i) w.r[i] = get_spec(k + MTS_SPEC_N * i); return w; }
     template <uint32_t M> DEV void store_m(const MisPathState<SPEC> &p, int cls) const {
-        if (M & K_RNG) { u(M_RNG) = (uint32_t) p.rng.state; u(M_RNG + 1) = (uint32_t) (p.rng.state >> 32); }
-        if (M & K_O) put3(M_O, p.ray.o);
-        if (M & K_D) { put3(M_D, p.ray.d); put3(M_DRCP, p.ray.d_rcp); }
-        if (M & K_MINT) putf(M_MINT, p.ray.mint);
-        if (M & K_MAXT) putf(M_MAXT, p.ray.maxt);
-        if (M & K_SIT) putf(M_SIT, p.si.t);
-        if (M & K_SIX) { put3(M_SIX, p.si.p); putf(M_SIX + 3, p.si.uv.x); putf(M_SIX + 4, p.si.uv.y); u(M_SIX + 5) = (uint32_t) p.si.shape; u(M_SIX + 6) = (uint32_t) p.si.prim; }
-        if (M & K_MED) u(M_MEDIUM) = (uint32_t) p.medium;
-        u(M_PACKED) = p.st | (p.mode << 4) | (p.channel << 6) | (p.flags << 8) | ((uint32_t) cls << 13) | ((p.depth < 32767u ? p.depth : 32767u) << 17);
-        if (M & K_WA) putf(M_WA, p.wa);
-        if (M & K_WB) putf(M_WB, p.wb);
-        if (M & K_ETA) putf(M_ETA, p.eta);
-        if (M & K_RES) put_spec(M_RES, p.res);
-        if (M & K_LSP) put3(M_LSP, p.lsp);
+        this->template store_front<M>(p);
+        u(H_PACKED) = Front::pack(p, cls);
+        if (M & K_WA) putf(MH_WA, p.wa);
+        if (M & K_WB) putf(MH_WB, p.wb);
+        if (M & K_ETA) putf(MH_ETA, p.eta);
+        if (M & K_RES) put_spec(MH_RES, p.res);
+        if (M & K_LSP) put3(MH_LSP, p.lsp);
 #if MTS_SPEC_N != 3
-        if (M & K_WL) put_spec(M_WL, p.wl);
+        if (M & K_WL) put_spec(MH_WL, p.wl);
 #endif
         // slot A / slot B: the path's pair outside a walk, the walk's pair inside one (a block that can hold either -- K_ALL -- picks by mode)
         constexpr bool path_a = (M & K_PF) != 0, walk_a = (M & K_WU) != 0, path_b = (M & K_PN) != 0, walk_b = (M & K_WN) != 0;
-        if (path_a && walk_a) putw(M_W, p.mode == M_MAIN ? p.pf : p.wu); else if (path_a) putw(M_W, p.pf); else if (walk_a) putw(M_W, p.wu);
-        if (path_b && walk_b) putw(M_W + NW, p.mode == M_MAIN ? p.pn : p.wn); else if (path_b) putw(M_W + NW, p.pn); else if (walk_b) putw(M_W + NW, p.wn);
+        if (path_a && walk_a) putw(MH_W, p.mode == M_MAIN ? p.pf : p.wu); else if (path_a) putw(MH_W, p.pf); else if (walk_a) putw(MH_W, p.wu);
+        if (path_b && walk_b) putw(MH_W + NW, p.mode == M_MAIN ? p.pn : p.wn); else if (path_b) putw(MH_W + NW, p.pn); else if (walk_b) putw(MH_W + NW, p.wn);
     }
     template <uint32_t M> DEV void load_m(MisPathState<SPEC> &p) const {
-        p.rng.state = 0; p.rng.inc = (PCG32_DEFAULT_STREAM << 1u) | 1u;
-        if (M & K_RNG) p.rng.state = (uint64_t) u(M_RNG) | ((uint64_t) u(M_RNG + 1) << 32);
-        p.ray.o = (M & K_O) ? get3(M_O) : f3s(0.f);
-        p.ray.d = (M & K_D) ? get3(M_D) : f3s(0.f); p.ray.d_rcp = (M & K_D) ? get3(M_DRCP) : f3s(0.f);
-        p.ray.mint = (M & K_MINT) ? f(M_MINT) : 0.f; p.ray.maxt = (M & K_MAXT) ? f(M_MAXT) : 0.f;
-        p.si.t = (M & K_SIT) ? f(M_SIT) : pm_inf();
-        p.si.p = f3s(0.f); p.si.uv.x = p.si.uv.y = 0.f; p.si.shape = -1; p.si.prim = 0;
-        if (M & K_SIX) { p.si.p = get3(M_SIX); p.si.uv.x = f(M_SIX + 3); p.si.uv.y = f(M_SIX + 4); p.si.shape = (int) u(M_SIX + 5); p.si.prim = (int) u(M_SIX + 6); }
-        p.medium = (M & K_MED) ? (int) u(M_MEDIUM) : -1;
-        const uint32_t pk = u(M_PACKED);
-        p.st = pk & 15u; p.mode = (pk >> 4) & 3u; p.channel = (pk >> 6) & 3u; p.flags = (pk >> 8) & 31u; p.depth = pk >> 17;
-        p.wa = (M & K_WA) ? f(M_WA) : 0.f; p.wb = (M & K_WB) ? f(M_WB) : 0.f; p.eta = (M & K_ETA) ? f(M_ETA) : 1.f;
-        p.res = (M & K_RES) ? get_spec(M_RES) : spec_s(0.f); p.lsp = (M & K_LSP) ? get3(M_LSP) : f3s(0.f);
+        this->template load_front<M>(p);
+        Front::unpack(u(H_PACKED), p);
+        p.wa = (M & K_WA) ? f(MH_WA) : 0.f; p.wb = (M & K_WB) ? f(MH_WB) : 0.f; p.eta = (M & K_ETA) ? f(MH_ETA) : 1.f;
+        p.res = (M & K_RES) ? get_spec(MH_RES) : spec_s(0.f); p.lsp = (M & K_LSP) ? get3(MH_LSP) : f3s(0.f);
 #if MTS_SPEC_N != 3
-        p.wl = (M & K_WL) ? get_spec(M_WL) : spec_s(0.f);
+        p.wl = (M & K_WL) ? get_spec(MH_WL) : spec_s(0.f);
 #endif
         // a block that may meet either pair (K_ALL) reads the two slots once; which pair they are follows from the mode, the other is never read
-        const MisWeights<SPEC> slot_a = (M & (K_PF | K_WU)) ? getw(M_W) : mw_full<SPEC>(1.f), slot_b = (M & (K_PN | K_WN)) ? getw(M_W + NW) : mw_full<SPEC>(1.f);
+        const MisWeights<SPEC> slot_a = (M & (K_PF | K_WU)) ? getw(MH_W) : mw_full<SPEC>(1.f), slot_b = (M & (K_PN | K_WN)) ? getw(MH_W + NW) : mw_full<SPEC>(1.f);
         p.pf = slot_a; p.wu = slot_a; p.pn = slot_b; p.wn = slot_b;
     }
     DEV void store(const MisPathState<SPEC> &p, int cls) const { store_m<K_ALL>(p, cls); }
@@ -636,7 +535,7 @@ static __device__ __forceinline__ int mis_block(const MTS_CONST_AS void *kernarg
 template <bool COUNT_, bool SPEC, int WG_>
 struct VolpathMisRing {
     static constexpr bool COUNT = COUNT_;
-    static constexpr int WG = WG_, HOT_DWORDS = MisHotStore<WG_, SPEC>::M_COUNT, PACKED = MisHotStore<WG_, SPEC>::M_PACKED;
+    static constexpr int WG = WG_, HOT_DWORDS = MisHotStore<WG_, SPEC>::MH_COUNT, PACKED = H_PACKED;
     typedef MisPathState<SPEC> State;
     typedef MisHotStore<WG_, SPEC> Hot;
     typedef VolpathMisMachine<COUNT_, SPEC> Machine;

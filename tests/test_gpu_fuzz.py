@@ -115,8 +115,12 @@ def test_random_scene(gpu_rgb, monkeypatch, seed, bvh):
     o = ob.OracleScene(d); ref = o.render(); so = o.last_stats
     if d["sensor"]["film"]["rfilter"]["type"] == "gaussian":          # neighbouring pixels are reached by atomics in arbitrary order
         assert np.allclose(gpu, ref, rtol=2e-4, atol=1e-6)
-    elif d["sensor"]["sampler"].get("wavefront"):                      # a small film's samples are spread over several workgroup entries: partial sums meet by atomics
-        assert np.allclose(gpu, ref, rtol=2e-5, atol=1e-7) and np.array_equal(gpu[..., 4], ref[..., 4])
+    elif d["sensor"]["sampler"].get("wavefront"):
+        # a small film's samples are spread over several workgroup entries per block: every entry sums its share of a pixel's samples
+        # into a film slot of its own and the slots are added in sample order (capi.cpp: launch_film_sum_slots) -- the oracle's terms
+        # in another association.  Any summation tree of n non-negative fp32 terms is within (n - 1) 2^-24 of the exact sum, so two differ
+        # by at most 2 (n - 1) 2^-24 relative: 6e-7 for the 6 samples a pixel has here at most
+        assert np.allclose(gpu, ref, rtol=1e-6, atol=1e-7) and np.array_equal(gpu[..., 4], ref[..., 4])
     else:
         assert np.array_equal(gpu, ref), (seed, float(np.abs(gpu - ref).max()))
     assert (st["n_iter"], st["n_lookup"], st["n_nee_step"]) == (so["n_iter"], so["n_lookup"], so["n_nee_step"])
@@ -195,8 +199,8 @@ def test_random_scene_spectral(gpu_spectral, seed):
     o = ob.OracleScene(d, spectral=True); ref = o.render(); so = o.last_stats
     if d["sensor"]["film"]["rfilter"]["type"] == "gaussian":
         assert np.allclose(gpu, ref, rtol=2e-4, atol=1e-6)
-    elif d["sensor"]["sampler"].get("wavefront"):
-        assert np.allclose(gpu, ref, rtol=2e-5, atol=1e-7) and np.array_equal(gpu[..., 4], ref[..., 4])
+    elif d["sensor"]["sampler"].get("wavefront"):                      # slots added in sample order: the bound of test_random_scene
+        assert np.allclose(gpu, ref, rtol=1e-6, atol=1e-7) and np.array_equal(gpu[..., 4], ref[..., 4])
     else:
         assert np.array_equal(gpu, ref), (seed, float(np.abs(gpu - ref).max()))
     assert (st["n_iter"], st["n_lookup"], st["n_nee_step"]) == (so["n_iter"], so["n_lookup"], so["n_nee_step"])

@@ -1255,6 +1255,16 @@ def gpu_spectral(pkg):
     pkg.set_variant("gpu_rgb")
 
 
+def _spectral_cornell(width, height, spp):
+    d = scenes.c1_cornell(width, height, spp)
+    for k, v in d.items():
+        if isinstance(v, dict) and "bsdf" in v:
+            rgb = v["bsdf"]["reflectance"]["value"]
+            v["bsdf"]["reflectance"] = {"type": "regular", "lambda_min": 400., "lambda_max": 700., "values": [rgb[2], rgb[1], rgb[0]]}
+    d["light"]["emitter"]["radiance"] = {"type": "d65", "scale": 3.0}
+    return d
+
+
 def _spectral_cases():
     rng = np.random.default_rng(3)
     def slab(spp=8, **kw):
@@ -1277,13 +1287,7 @@ def _spectral_cases():
     del d["sun"]["irradiance"]                                                                # default: D65
     d["ground"]["bsdf"] = {"type": "rpv", "rho_0": {"type": "uniform", "value": 0.2}, "k": 0.7, "g": -0.1}
     cases["grid_spectral_d65_rpv"] = d
-    d = scenes.c1_cornell(32, 32, 8)
-    for k, v in d.items():
-        if isinstance(v, dict) and "bsdf" in v:
-            rgb = v["bsdf"]["reflectance"]["value"]
-            v["bsdf"]["reflectance"] = {"type": "regular", "lambda_min": 400., "lambda_max": 700., "values": [rgb[2], rgb[1], rgb[0]]}
-    d["light"]["emitter"]["radiance"] = {"type": "d65", "scale": 3.0}
-    cases["cornell_path"] = d
+    cases["cornell_path"] = _spectral_cornell(32, 32, 8)
     d = scenes.c4_atmosphere(16, 16, 8, layers=8)
     d["sun"]["irradiance"] = {"type": "uniform", "value": 1.0}
     cases["c4_atmosphere"] = d
@@ -1471,6 +1475,102 @@ def test_bins_on_the_regrouping_machine(gpu_spectral, monkeypatch, wrap, kernel,
     assert raw.shape[2] == channels and ref[..., 5:].max() > 0
     assert_parity(raw, ref)
     assert (st["n_iter"], st["n_lookup"], st["n_nee_step"]) == (o.last_stats["n_iter"], o.last_stats["n_lookup"], o.last_stats["n_nee_step"])
+
+
+def _sample_head_scenes(spectral, integrator):
+    """The scenes of test_every_formulation_draws_the_same_sample_head under one integrator, each with an open shutter (the time draw)."""
+    if spectral:
+        box = _spectral_cornell(24, 24, 8)                                               # a sensor response function and bins: the weights and the AOV channels
+        box["sensor"]["srf"] = {"type": "discrete", "wavelengths": "450, 550, 650, 750", "values": "0.5, 1.0, 0.75, 0.25"}
+        made = {"c5s": scenes.c5_atmosphere_spectral(24, 24, 8, layers=8), "cornell_srf_bins": box}
+        if integrator != "path":                                                         # the same on a scene with a medium: the ring machines' NEW block
+            grid = _spectral_cases()["grid_spectral_d65_rpv"]                            # (test_bins_on_the_regrouping_machine); the box has none and runs per lane
+            grid["sensor"]["srf"] = dict(box["sensor"]["srf"])
+            made["grid_srf_bins"] = grid
+    else:
+        made = {"c4": scenes.c4_atmosphere(24, 24, 8, layers=8),                         # a distant sensor: the aperture draw
+                "c3": scenes.c3_heterogeneous(40, 24, 8, res=16),                        # partial blocks (black under `path`, which knows no media)
+                "cornell": scenes.c1_cornell(24, 24, 8)}
+        if integrator == "path":
+            made["cornell_40x24"] = scenes.c1_cornell(40, 24, 8)                         # partial blocks with a film that is not black
+    for name, d in made.items():
+        d["sensor"] = dict(d["sensor"], shutter_open=1.0, shutter_close=1.5)
+        d["integrator"] = dict(d["integrator"], type=integrator)
+        if integrator == "volpathmis" and not spectral:
+            d["integrator"]["use_spectral_mis"] = True
+        if name.endswith("_srf_bins"):
+            d["integrator"] = {"type": "bins", "bins": "a:400:500, b:500:600, c:600:800", "integrator": d["integrator"]}
+    return made
+
+
+def _sample_head_variant(spectral, integrator, kernel, name):
+    """mts_stats.kernel_variant modulo the lean unit (capi.cpp: choose_kernel): 0 nested per lane, 1 flat per lane, 10000 + paths per workgroup."""
+    if kernel == "nested":
+        return 0
+    if integrator == "path" or kernel == "flat":
+        return 1
+    if kernel == "wga256":
+        return 10256
+    if name.startswith("cornell"):                                                       # no medium: the volumetric integrators run per lane
+        return 0
+    return 10256 if spectral else 10512 if integrator == "volpathmis" else 11024
+
+
+_SAMPLE_HEAD_REFS = {}
+
+
+def _sample_head_refs(spectral, integrator):
+    """The oracle's films and loop counters for those scenes, rendered once per (variant, integrator).  With the shutter closed the
+    film must differ, or the time draw would not be exercised."""
+    key = (spectral, integrator)
+    if key not in _SAMPLE_HEAD_REFS:
+        refs = {}
+        for name, d in _sample_head_scenes(spectral, integrator).items():
+            o = ob.OracleScene(d, spectral=spectral)
+            ref = o.render(); so = o.last_stats
+            counters = (so["n_iter"], so["n_lookup"], so["n_nee_step"])
+            closed = dict(d); closed["sensor"] = dict(d["sensor"], shutter_close=1.0)
+            oc = ob.OracleScene(closed, spectral=spectral)
+            ref_closed = oc.render()
+            black = integrator == "path" and name == "c3"
+            assert (ref[..., :3].max() > 0) != black, name
+            assert black or not np.array_equal(ref, ref_closed), name            # (nothing of the black film depends on a draw after the first)
+            ref.setflags(write=False)
+            refs[name] = (ref, counters)
+        _SAMPLE_HEAD_REFS[key] = refs
+    return _SAMPLE_HEAD_REFS[key]
+
+
+@pytest.mark.parametrize("variant,integrator,kernel", [
+    ("rgb", "volpath", None), ("rgb", "volpath", "wga256"), ("rgb", "volpath", "flat"), ("rgb", "volpath", "nested"),
+    ("rgb", "volpathmis", None), ("rgb", "volpathmis", "nested"), ("rgb", "path", None), ("rgb", "path", "nested"),
+    ("spectral", "volpath", None), ("spectral", "volpath", "nested"), ("spectral", "volpathmis", None), ("spectral", "volpathmis", "nested"),
+    ("spectral", "path", None), ("spectral", "path", "nested")])
+def test_every_formulation_draws_the_same_sample_head(pkg, gpu_rgb, monkeypatch, variant, integrator, kernel):
+    """The head of a sample (integrator.cpp:242-264: film position, aperture, time, wavelengths, camera ray) and its tail (result -> XYZ ->
+    splat) are written out once per formulation -- render_sample and path_pixel_flat (kernels.hip), the two ring machines, whose NEW
+    block is shared (volpath_flat.h: RingMachine::blk_new) -- and an edit of one of them alone breaks parity without a build error.
+    Every formulation, rgb and spectral, runs on the kernel it names and gives the oracle's film -- the bins' AOV channels included --
+    and loop counters bit for bit with the aperture draw (distant sensor), the time draw (open shutter), a sensor response function
+    and partial blocks in play."""
+    if kernel:
+        monkeypatch.setenv("MTSAMD_KERNEL", kernel)
+    spectral = variant == "spectral"
+    refs = _sample_head_refs(spectral, integrator)
+    before = pkg.variant()                                                               # the module's spectral tests run with theirs set once
+    pkg.set_variant("gpu_spectral" if spectral else "gpu_rgb")
+    try:
+        for name, d in _sample_head_scenes(spectral, integrator).items():
+            gpu, st = gpu_render(pkg, d, collect_counters=True)
+            ref, counters = refs[name]
+            assert st["kernel_variant"] % 100000 == _sample_head_variant(spectral, integrator, kernel, name), (name, st["kernel_variant"])
+            assert gpu.shape == ref.shape, (name, gpu.shape, ref.shape)
+            if name.endswith("_srf_bins"):
+                assert ref.shape[2] == 5 + 2 * 3 and ref[..., 5:].max() > 0, name
+            assert np.array_equal(gpu, ref), (name, int((gpu != ref).sum()), float(np.abs(gpu - ref).max()))
+            assert (st["n_iter"], st["n_lookup"], st["n_nee_step"]) == counters, name
+    finally:
+        pkg.set_variant(before)
 
 
 def test_device_film_buffer_must_hold_the_aov_channels(gpu_spectral):
