@@ -2,7 +2,7 @@
 //
 // -DMTSAMD_HOST_ONLY (tests/test_host_sanitizers.py: the host pass alone, built with AddressSanitizer + UndefinedBehaviorSanitizer):
 // everything that validates and flattens caller-owned records runs as in the product -- mts_scene_create up to the upload, mts_render
-// up to the first device call (options, passes, spiral, shard filter, film capacity) -- and every entry point that would touch the GPU
+// up to the first device call (options, passes, spiral, shard filter, film capacity, kernel choice) -- and every entry point that would touch the GPU
 // reports "host-only build" instead.
 //
 // mts_render mirrors SamplingIntegrator::render (/root/reference/src/librender/integrator.cpp:51-179): the pass / block bookkeeping
@@ -186,67 +186,31 @@ int mts_sigint_scope_exit(void) {
     return 0;
 }
 
-#if !defined(MTSAMD_HOST_ONLY)
-// The render kernel of a scene, the one place that uses MTSAMD_KERNEL and MTSAMD_LEAN.  mts_stats.kernel_variant = variant + 100000 * unit.
-// variant: 0 = nested per lane, 1 = flat per lane, 10000 + P = the regrouping machine with P paths per workgroup.
-// unit: 0 = the general kernels (kernels.hip, kernels_spectral.hip), else the lean translation unit of RENDER_LAUNCHERS: the regrouping
-// machines of `volpath` and `volpathmis` (or `path`'s flat loop) compiled WITHOUT what this scene cannot contain (integrator_dev.h:
-// MTS_TRAITS) -- the leanest unit whose promises the scene keeps.
-struct KernelChoice { int variant, unit; };
-static KernelChoice choose_kernel(const HostScene &hs, uint32_t block_size, const RenderSwitches &sw) {
-    const DSensor &se = hs.scene.sensor;
-    const bool path = hs.integrator.type == MTS_INTEGRATOR_PATH, vol = hs.integrator.type == MTS_INTEGRATOR_VOLPATH;
-    const bool mis = hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS, spectral = hs.integrator.spectral;
-    // MTSAMD_KERNEL = nested | flat | wga256 | wga1024 (default: asynchronous regrouping, 1024 paths served by 1024 threads)
-    int variant = sw.kernel >= 0 ? sw.kernel : 11024;
-    // without media there are no tracking walks to regroup: the per-lane kernels win (cornell box 512 x 512 x 256, volpath: rings 992,
-    // per lane 1242 Msamples/s; `path` per lane: 2342, as one flat loop with regeneration 2910)
-    if (sw.kernel < 0 && hs.media.empty() && !path) variant = 0;
-    if (path) variant = variant != 0 ? 1 : 0;                   // per lane: flat loop with regeneration (every variant), or nested (MTSAMD_KERNEL=nested)
-    if (variant >= 10000) {                                     // variant = 10000 + paths per workgroup
-        uint32_t wg = (uint32_t) (variant - 10000);
-        if (mis) wg = std::min(wg, 512u);                       // four weight matrices per path: 512 paths fill the LDS
-        if (spectral) wg = std::min(wg, 256u);                  // four-wide spectra: 42 hot dwords per path; three 256-path workgroups per CU (12 waves) beat one of 512 (8 waves) by 10 %
-        // a workgroup of the regrouping kernels sits in ONE spiral block: blocks smaller than its path count get the largest
-        // workgroup that divides them (16 x 16 -> 256 paths); only blocks below 256 pixels fall back to the per-lane kernel
-        while (wg > 256 && (block_size * block_size) % wg != 0) wg /= 2;
-        variant = (block_size * block_size) % wg != 0 ? 1 : 10000 + (int) wg;
-    }
-    if (spectral && variant == 1 && !path) variant = 0;         // the spectral build's per-lane flat kernel is `path`'s
-    // AOV channels (nbins / bins) and a sensor response function: `volpath` and (round 4) `volpathmis` carry them on the regrouping
-    // machines (their NEW blocks) and `path` in its flat loop (kernels.hip: path_pixel_flat); a discrete response function with repeated
-    // wavelengths keeps the volumetric integrators per lane
-    if ((hs.scene.bin_count > 0 || hs.scene.srf >= 0) && !(variant == 1 && path) && !(variant >= 10000 && !path && hs.srf_lookup_by_wavelength)) variant = 0;
-    // Wavefront (gpu_*) streams carry their own PCG32 increment per (pixel, sample).  The regrouping machine of rgb / mono `volpath` keeps
-    // only the generator's 64-bit state in LDS and recomputes the increment on every load (round 4: wg_block's WF instantiation, 1024-path
-    // workgroups); everything else runs per lane, where the generator lives in registers: `volpath` as the flat state machine, the
-    // others nested
-    if (se.wavefront && variant >= 10000 && !(variant == 11024 && vol && !spectral)) variant = vol && !spectral ? 1 : 0;
-    int unit = 0;
-#if !defined(MTSAMD_BLOCKSTATS)                                 // the diagnostic build compiles no lean unit
-    if (sw.lean != 0) {                                         // 0: never a lean unit; 2: the b unit on a scene that qualifies for a
-        auto keeps = [&](int promises) { return (hs.traits & promises) == promises; };      // dscene.h: MT_UNIT_*
-        const bool spec_mis = mis && hs.integrator.use_spectral_mis;
-        const bool machine = spectral ? (variant == 10256 && (vol || spec_mis)) : ((variant == 11024 && vol) || (variant == 10512 && spec_mis));
-        if (machine && !se.wavefront) {
-            if (spectral) { if (keeps(MT_UNIT_B)) unit = 3; }                // kernels_lean_s.hip
-            else if (keeps(MT_UNIT_A)) unit = sw.lean == 2 ? 2 : 1;          // every promise: no call left
-            else if (keeps(MT_UNIT_B)) unit = 2;                             // rpv and grids behind volume_eval() allowed
-            else if (keeps(MT_UNIT_C)) unit = 7;                             // ... and a BVH
-            else if (keeps(MT_UNIT_H)) unit = 6;                             // homogeneous media
-        }
-        // `path` as the flat loop: kernels_lean_p.hip / _ps.hip want a walked primitive list, no spheres, no rpv
-        if (variant == 1 && path && keeps(MT_UNIT_P_NEEDS)) unit = spectral ? 5 : 4;
-    }
-#endif
-    return { variant, unit };
+// What choose_kernel (render_plan.cpp; DESIGN.md section 4, "kernel table") reads of a scene
+static KernelFacts facts_of(const HostScene &hs) { return { hs.integrator.type, hs.integrator.spectral != 0, hs.integrator.use_spectral_mis != 0, !hs.media.empty(), hs.scene.bin_count > 0, hs.scene.srf >= 0, hs.srf_lookup_by_wavelength, hs.scene.sensor.wavefront != 0, hs.traits }; }
+
+// Not part of the ABI either: mts_stats.kernel_variant as mts_render would report it for this description under the environment's
+// switches.  Host only (tests/test_abi.py::test_kernel_choice).
+int mts_debug_kernel_choice(const mts_scene_desc *desc, int32_t *kernel_variant) {
+    API_TRY
+    if (!kernel_variant) throw std::runtime_error("mts_debug_kernel_choice: kernel_variant is NULL");
+    HostScene *hs = build_host_scene(desc);
+    try {
+        const KernelChoice kc = choose_kernel(facts_of(*hs), plan_block_size(hs->integrator.block_size), read_render_switches());
+        *kernel_variant = kv::stat(kc.variant, kc.unit);
+    } catch (...) { free_host_scene(hs); throw; }
+    free_host_scene(hs);
+    API_CATCH
 }
-// the launcher of each unit number (unit 0: launch_render, or launch_render_spectral for a scene of the spectral variant)
+
+#if !defined(MTSAMD_HOST_ONLY)
+// the launcher of each unit (UNIT_GENERAL: launch_render, or launch_render_spectral for a scene of the spectral variant)
 #if defined(MTSAMD_BLOCKSTATS)
-static const RenderLauncher RENDER_LAUNCHERS[1] = { launch_render };
+static const RenderLauncher RENDER_LAUNCHERS[] = { launch_render };
 #else
-static const RenderLauncher RENDER_LAUNCHERS[8] = { launch_render, launch_render_lean_a, launch_render_lean_b, launch_render_lean_s,
-                                                    launch_render_lean_p, launch_render_lean_ps, launch_render_lean_h, launch_render_lean_c };
+static const RenderLauncher RENDER_LAUNCHERS[] = { launch_render, launch_render_lean_a, launch_render_lean_b, launch_render_lean_s,
+                                                   launch_render_lean_p, launch_render_lean_ps, launch_render_lean_h, launch_render_lean_c };
+static_assert(sizeof(RENDER_LAUNCHERS) / sizeof(RENDER_LAUNCHERS[0]) == UNIT_COUNT, "one launcher per KernelUnit, in the enum's order");
 #endif
 #endif
 
@@ -273,8 +237,10 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
     if (opts.film_capacity > 0 && (uint64_t) opts.film_capacity < (uint64_t) film_floats)
         throw std::runtime_error("mts_render: the film buffer holds " + std::to_string(opts.film_capacity) + " floats, this scene writes " + std::to_string(film_floats) +
                                  " (crop_width x crop_height x " + std::to_string(hs.scene.film_channels) + " channels: X, Y, Z, A, W + two per spectral bin)");
+    const KernelChoice kc = choose_kernel(facts_of(hs), block_size, sw);
+    const int variant = kc.variant;
 #if defined(MTSAMD_HOST_ONLY)
-    (void) stream; (void) t0; (void) stats; (void) block_size;
+    (void) stream; (void) t0; (void) stats; (void) variant;
     HOST_ONLY_STOP("mts_render");
 #else
     RenderCache &rc = scene->cache;
@@ -310,10 +276,8 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
                                      ", workgroup " + std::to_string(c[9]) + ")");
     };
     try {
-        const KernelChoice kc = choose_kernel(hs, block_size, sw);
-        const int variant = kc.variant;
-        last_variant = variant + 100000 * kc.unit;
-        const RenderLauncher launcher = kc.unit == 0 && hs.integrator.spectral ? launch_render_spectral : RENDER_LAUNCHERS[kc.unit];
+        last_variant = kv::stat(variant, kc.unit);
+        const RenderLauncher launcher = kc.unit == UNIT_GENERAL && hs.integrator.spectral ? launch_render_spectral : RENDER_LAUNCHERS[kc.unit];
 
         // one launch over `blocks` with `spp` samples per pixel, watched for cancel() / the timeout (which reach the kernel through the stop word).
         // `tiles`: the cost-sorted tile table of the regrouping kernels (volpath_flat.h, WgArgs::tiles), or empty: one workgroup per
@@ -376,7 +340,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
         for (std::vector<DBlock> &blocks : plan.chunks) {
             if (should_stop()) break;
             if (blocks.empty()) continue;
-            const std::vector<uint32_t> tiles = cost_index.empty() ? std::vector<uint32_t>() : schedule_chunk(blocks, cost_index, tile_cost, block_size, lpt.use_tiles, (uint32_t) (variant % 10000));
+            const std::vector<uint32_t> tiles = cost_index.empty() ? std::vector<uint32_t>() : schedule_chunk(blocks, cost_index, tile_cost, block_size, lpt.use_tiles, (uint32_t) kv::ring_paths(variant));
             launch(blocks, (uint32_t) plan.launch_spp, tiles);
         }
         if (plan.pass_slots) HIP_CHECK(launch_film_sum_slots(d_film, d_target, film_floats, (uint32_t) plan.n_slots, stream));

@@ -129,7 +129,7 @@ struct DVolumeSp { int32_t value_sp; int32_t spectral_grid; float lambda_min, la
 struct DIntegrator { int32_t type, max_depth, rr_depth, hide_emitters, use_spectral_mis, monochrome; };
 
 // One spiral block (librender/spiral.cpp:27-72) assigned to this launch
-// Scene traits (integrator_dev.h: MTS_TRAITS; scene_host.cpp: scene_traits; capi.cpp: the choice of the lean translation unit).
+// Scene traits (integrator_dev.h: MTS_TRAITS; scene_host.cpp: scene_traits; render_plan.cpp: KERNEL_UNITS, the choice of the lean translation unit).
 #define MT_MEDIA 1              // every medium: heterogeneous with spectral extinction and -- rgb / mono: grey, on a pair grid (DMedium::pair_grid);
                                 // spectral variant: two gridvolume_spectral grids sharing geometry and interval (DMedium::shared_grid == 2)
 #define MT_NO_BVH 2             // the primitive list is walked (no BVH)

@@ -1,0 +1,22 @@
+// kernel_names.h -- the names of a render kernel ("kernel table"), for the host planning code (render_plan.h) and the
+// launchers of the device units (launch.h) alike.  Constants only: it includes nothing.
+#pragma once
+
+namespace mtsamd {
+
+// A VARIANT is a kernel formulation: nested per-lane loops, the flat per-lane state machine, or the regrouping machine on LDS rings with
+// P paths per workgroup.  A UNIT is the translation unit the kernel comes from: the general kernels (kernels.hip, kernels_spectral.hip)
+// or a lean unit (kernels_lean_*.hip), the same kernels compiled without what a scene cannot contain.  mts_stats.kernel_variant carries
+// both.  The values are ABI: they never change.
+namespace kv {
+constexpr int NESTED = 0, FLAT = 1, RING_BASE = 10000, UNIT_STRIDE = 100000;
+constexpr int ring(int paths) { return RING_BASE + paths; }
+constexpr bool is_ring(int variant) { return variant >= RING_BASE; }
+constexpr int ring_paths(int variant) { return variant - RING_BASE; }
+constexpr int stat(int variant, int unit) { return variant + UNIT_STRIDE * unit; }        // mts_stats.kernel_variant
+constexpr int stat_variant(int kernel_variant) { return kernel_variant % UNIT_STRIDE; }
+constexpr int stat_unit(int kernel_variant) { return kernel_variant / UNIT_STRIDE; }
+} // namespace kv
+enum KernelUnit : int { UNIT_GENERAL = 0, UNIT_A = 1, UNIT_B = 2, UNIT_S = 3, UNIT_P = 4, UNIT_PS = 5, UNIT_H = 6, UNIT_C = 7, UNIT_COUNT = 8 };
+
+} // namespace mtsamd

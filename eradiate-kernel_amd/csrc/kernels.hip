@@ -379,14 +379,14 @@ hipError_t launch_film_sum_slots(float *d_film, const float *d_slots, size_t fil
 }
 
 size_t render_workspace_floats(uint64_t threads, int variant) {
-    if (variant < 10000) return 0;
-    const uint64_t wg = (uint64_t) (variant - 10000), padded = (threads + wg - 1) / wg * wg;
+    if (!kv::is_ring(variant)) return 0;
+    const uint64_t wg = (uint64_t) kv::ring_paths(variant), padded = (threads + wg - 1) / wg * wg;
     return (size_t) padded * MTS_COLD_RECORD + 32;      // workgroup drivers: one 128-byte record per path
 }
 
 #endif // MTS_SPEC_N == 3
 
-// ---- the render launchers: one per translation unit (launch.h), each choosing among the kernels of its unit by a.variant
+// ---- the render launchers: one per translation unit (launch.h), each choosing among the kernels of its unit by a.variant (render_plan.cpp: KERNEL_ROWS)
 typedef void (*WgKernel)(DScene, const DBlock *, uint32_t, uint32_t, uint32_t, float *, float *, uint32_t, unsigned long long *,
                          const uint32_t *, const uint32_t *, uint32_t);
 typedef void (*LaneKernel)(DScene, const DBlock *, uint32_t, uint32_t, uint32_t, float *, unsigned long long *, const uint32_t *);
@@ -409,57 +409,57 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     if (a.n_blocks == 0) return hipSuccess;
     // cost-sorted tiles (regrouping kernels only): the launch covers n_tiles slots of 16 paths instead of the blocks' concatenated Morton orders
     const uint64_t threads = a.tiles != nullptr ? (uint64_t) a.n_tiles * MTS_TILE_PIXELS : (uint64_t) a.n_blocks * a.block_size * a.block_size;
-    if (a.tiles != nullptr && a.variant < 10000) return hipErrorInvalidConfiguration;
+    if (a.tiles != nullptr && !kv::is_ring(a.variant)) return hipErrorInvalidConfiguration;
     if (threads + 1024 >= ((uint64_t) 1 << 32)) return hipErrorInvalidValue;      // thread and path indices are 32 bit (mts_render launches in chunks)
     const int integ = a.sc->integrator.type;
     const bool volpath = integ == MTS_INTEGRATOR_VOLPATH, mis = integ == MTS_INTEGRATOR_VOLPATHMIS, spec_mis = a.sc->integrator.use_spectral_mis != 0;
 #if defined(MTS_LEAN_PATH)    // kernels_lean_p.hip / _ps.hip: `path` as the flat loop with regeneration, nothing else
     (void) volpath; (void) mis; (void) spec_mis;
-    if (a.variant == 1 && integ == MTS_INTEGRATOR_PATH) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_PATH));
+    if (a.variant == kv::FLAT && integ == MTS_INTEGRATOR_PATH) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_PATH));
     return hipErrorInvalidConfiguration;
 #elif defined(MTS_LEAN)       // the other lean units: the regrouping machines of `volpath` and of `volpathmis` with spectral MIS, nothing else
     if (a.sc->sensor.wavefront) return hipErrorInvalidConfiguration;
 #if MTS_SPEC_N != 3           // the spectral variant's machines: 256-path workgroups
     // register budget of three waves per SIMD (three 256-path workgroups per CU): with the spectral grid lookups inline the allocator needs the bound
-    if (a.variant == 10256 && volpath) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 3));
-    if (a.variant == 10256 && mis && spec_mis) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256));
+    if (a.variant == kv::ring(256) && volpath) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 3));
+    if (a.variant == kv::ring(256) && mis && spec_mis) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256));
 #else
-    if (a.variant == 11024 && volpath) return launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4));
+    if (a.variant == kv::ring(1024) && volpath) return launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4));
 #if defined(MTS_LEAN_MIS_768)   // the 512 paths served by 768 threads: three waves per SIMD want <= 168 VGPRs, which this unit's kernel meets (C3M 375 -> 393)
-    if (a.variant == 10512 && mis && spec_mis) return launch_wg(a, threads, 512, 768, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 768));
+    if (a.variant == kv::ring(512) && mis && spec_mis) return launch_wg(a, threads, 512, 768, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 768));
 #else
-    if (a.variant == 10512 && mis && spec_mis) return launch_wg(a, threads, 512, 512, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 512));
+    if (a.variant == kv::ring(512) && mis && spec_mis) return launch_wg(a, threads, 512, 512, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 512));
 #endif
 #endif
     return hipErrorInvalidConfiguration;
 #else                         // the general kernels
 #if MTS_SPEC_N == 3
-    if (a.variant >= 10000 && volpath) {                      // asynchronous regrouping, variant = 10000 + paths per workgroup
+    if (kv::is_ring(a.variant) && volpath) {                      // asynchronous regrouping
         if (a.sc->sensor.wavefront)                           // gpu_* streams: the instantiation that recomputes the generator's increment (wg_block, WF)
-            return a.variant == 11024 ? launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4, true)) : hipErrorInvalidConfiguration;
-        if (a.variant == 11024) return launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4));
-        if (a.variant == 10256) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 4));
+            return a.variant == kv::ring(1024) ? launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4, true)) : hipErrorInvalidConfiguration;
+        if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4));
+        if (a.variant == kv::ring(256)) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 4));
         return hipErrorInvalidConfiguration;
     }
-    if (a.variant >= 10000 && mis) {                          // the same machinery, 512 or 256 paths per workgroup
-        if (a.variant == 10512)
+    if (kv::is_ring(a.variant) && mis) {                          // the same machinery, 512 or 256 paths per workgroup
+        if (a.variant == kv::ring(512))
             return launch_wg(a, threads, 512, 512, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 512) : MTS_BY_COUNT(render_kernel_wga_mis, false, 512, 512));
-        if (a.variant == 10256)
+        if (a.variant == kv::ring(256))
             return launch_wg(a, threads, 256, 256, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256) : MTS_BY_COUNT(render_kernel_wga_mis, false, 256, 256));
         return hipErrorInvalidConfiguration;
     }
-    if (a.variant != 0 && volpath) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_VOLPATH));     // the flat state machine per lane
+    if (a.variant != kv::NESTED && volpath) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_VOLPATH));     // the flat state machine per lane
 #else
     // four-wide state: `volpath` 42 hot dwords per path; `volpathmis` 69 with spectral MIS (round 4: the path's matrices are parked during
     // walks), 53 without -- 256 paths per workgroup, two or three workgroups per CU
-    if (a.variant >= 10000 && volpath)
-        return a.variant == 10256 ? launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 2)) : hipErrorInvalidConfiguration;
-    if (a.variant >= 10000 && mis)
-        return a.variant == 10256 ? launch_wg(a, threads, 256, 256, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256) : MTS_BY_COUNT(render_kernel_wga_mis, false, 256, 256))
+    if (kv::is_ring(a.variant) && volpath)
+        return a.variant == kv::ring(256) ? launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 2)) : hipErrorInvalidConfiguration;
+    if (kv::is_ring(a.variant) && mis)
+        return a.variant == kv::ring(256) ? launch_wg(a, threads, 256, 256, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256) : MTS_BY_COUNT(render_kernel_wga_mis, false, 256, 256))
                                   : hipErrorInvalidConfiguration;
 #endif
     if (integ == MTS_INTEGRATOR_PATH)                         // flat: one loop over path segments with regeneration (path_pixel_flat)
-        return launch_lane(a, threads, a.variant != 0 ? MTS_BY_COUNT(render_kernel, true, NI_PATH) : MTS_BY_COUNT(render_kernel, false, NI_PATH));
+        return launch_lane(a, threads, a.variant != kv::NESTED ? MTS_BY_COUNT(render_kernel, true, NI_PATH) : MTS_BY_COUNT(render_kernel, false, NI_PATH));
     if (volpath) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, false, NI_VOLPATH));
     return launch_lane(a, threads, spec_mis ? MTS_BY_COUNT(render_kernel, false, NI_VOLPATHMIS) : MTS_BY_COUNT(render_kernel, false, NI_VOLPATHMIS_NOSPEC));
 #endif

@@ -2,12 +2,12 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include "dscene.h"
+#include "kernel_names.h"
 
 namespace mtsamd {
 
 // One launch of a render kernel over `n_blocks` spiral blocks, as mts_render (capi.cpp) hands it to every render launcher below.
-// variant: 0 = nested formulation, 1 = flat per-lane state machine, 10000 + P = workgroup-regrouping kernel with P paths per
-// workgroup (needs a workspace of render_workspace_floats() floats for the cold path state).
+// variant: kernel_names.h's kv names; a ring variant needs a workspace of render_workspace_floats() floats for the cold path state.
 struct RenderArgs {
     const DScene *sc;
     const DBlock *blocks; uint32_t n_blocks, block_size, sample_count;
@@ -22,9 +22,7 @@ size_t render_workspace_floats(uint64_t paths, int variant);
 hipError_t launch_render(const RenderArgs &a);
 hipError_t launch_render_spectral(const RenderArgs &a);
 // the lean translation units (kernels_lean_*.hip), for scenes that keep the promises of their traits (integrator_dev.h: MTS_TRAITS);
-// anything else: hipErrorInvalidConfiguration.  a / b / c / h: the regrouping kernels of rgb / mono `volpath` (variant 11024) and
-// `volpathmis` (10512) -- a: every promise, b: rpv and blend-weight grids allowed, c: as b with a BVH, h: homogeneous media; s: the
-// spectral variant's 256-path machines (10256); p / ps: `path` as the flat loop (variant 1) without a BVH, spheres and rpv (rgb / spectral)
+// anything else: hipErrorInvalidConfiguration.  Which kernels each carries and what it promises: render_plan.cpp, KERNEL_ROWS / KERNEL_UNITS
 hipError_t launch_render_lean_a(const RenderArgs &a);
 hipError_t launch_render_lean_b(const RenderArgs &a);
 hipError_t launch_render_lean_c(const RenderArgs &a);

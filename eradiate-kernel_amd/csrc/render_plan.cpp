@@ -22,7 +22,7 @@ static int one_of(const char *name, std::initializer_list<const char *> values, 
 
 RenderSwitches read_render_switches() {
     RenderSwitches sw;
-    static const int KERNELS[] = { 0, 1, 10256, 11024 };
+    static const int KERNELS[] = { kv::NESTED, kv::FLAT, kv::ring(256), kv::ring(1024) };
     const int kernel = one_of("MTSAMD_KERNEL", { "nested", "flat", "wga256", "wga1024" }, -1);
     sw.kernel = kernel < 0 ? -1 : KERNELS[kernel];
     sw.lean = one_of("MTSAMD_LEAN", { "0", "1", "2" }, 1);
@@ -42,6 +42,120 @@ RenderSwitches read_render_switches() {
     return sw;
 }
 
+// ---- The kernel table (render_plan.h).  The rows are read off the launchers of kernels.hip, unit by unit.
+const KernelRow KERNEL_ROWS[] = {
+    // unit, variant, integrator, spectral MIS, wavefront streams, spectral build
+    // the general kernels of the rgb / mono build (kernels.hip)
+    { UNIT_GENERAL, kv::ring(1024), MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_NO,     false },
+    { UNIT_GENERAL, kv::ring(1024), MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_YES,    false },     // the instantiation that recomputes the generator's increment (WF)
+    { UNIT_GENERAL, kv::ring(256),  MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_NO,     false },
+    { UNIT_GENERAL, kv::ring(512),  MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_NO,     false },
+    { UNIT_GENERAL, kv::ring(512),  MTS_INTEGRATOR_VOLPATHMIS, ROW_NO,     ROW_NO,     false },
+    { UNIT_GENERAL, kv::ring(256),  MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_NO,     false },
+    { UNIT_GENERAL, kv::ring(256),  MTS_INTEGRATOR_VOLPATHMIS, ROW_NO,     ROW_NO,     false },
+    { UNIT_GENERAL, kv::FLAT,       MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_EITHER, false },     // the flat state machine per lane
+    { UNIT_GENERAL, kv::FLAT,       MTS_INTEGRATOR_PATH,       ROW_EITHER, ROW_EITHER, false },     // one flat loop with regeneration (path_pixel_flat)
+    { UNIT_GENERAL, kv::FLAT,       MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_EITHER, false },     // `volpathmis` has no flat kernel per lane: the launcher runs
+    { UNIT_GENERAL, kv::FLAT,       MTS_INTEGRATOR_VOLPATHMIS, ROW_NO,     ROW_EITHER, false },     // the nested one (blocks below 256 pixels, MTSAMD_KERNEL=flat)
+    { UNIT_GENERAL, kv::NESTED,     MTS_INTEGRATOR_PATH,       ROW_EITHER, ROW_EITHER, false },
+    { UNIT_GENERAL, kv::NESTED,     MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_EITHER, false },
+    { UNIT_GENERAL, kv::NESTED,     MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_EITHER, false },
+    { UNIT_GENERAL, kv::NESTED,     MTS_INTEGRATOR_VOLPATHMIS, ROW_NO,     ROW_EITHER, false },
+    // the general kernels of the spectral build (kernels_spectral.hip): four-wide state, 256-path workgroups
+    { UNIT_GENERAL, kv::ring(256),  MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_NO,     true },
+    { UNIT_GENERAL, kv::ring(256),  MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_NO,     true },
+    { UNIT_GENERAL, kv::ring(256),  MTS_INTEGRATOR_VOLPATHMIS, ROW_NO,     ROW_NO,     true },
+    { UNIT_GENERAL, kv::FLAT,       MTS_INTEGRATOR_PATH,       ROW_EITHER, ROW_EITHER, true },
+    { UNIT_GENERAL, kv::NESTED,     MTS_INTEGRATOR_PATH,       ROW_EITHER, ROW_EITHER, true },
+    { UNIT_GENERAL, kv::NESTED,     MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_EITHER, true },
+    { UNIT_GENERAL, kv::NESTED,     MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_EITHER, true },
+    { UNIT_GENERAL, kv::NESTED,     MTS_INTEGRATOR_VOLPATHMIS, ROW_NO,     ROW_EITHER, true },
+#if !defined(MTSAMD_BLOCKSTATS)                                 // the diagnostic build compiles no lean unit
+    // a / b / c / h: the regrouping machines of rgb / mono `volpath` and of `volpathmis` with spectral MIS
+    { UNIT_A,       kv::ring(1024), MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_NO,     false },
+    { UNIT_A,       kv::ring(512),  MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_NO,     false },     // its 512 paths served by 768 threads
+    { UNIT_B,       kv::ring(1024), MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_NO,     false },
+    { UNIT_B,       kv::ring(512),  MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_NO,     false },
+    { UNIT_C,       kv::ring(1024), MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_NO,     false },
+    { UNIT_C,       kv::ring(512),  MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_NO,     false },
+    { UNIT_H,       kv::ring(1024), MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_NO,     false },
+    { UNIT_H,       kv::ring(512),  MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_NO,     false },
+    // s: the same machines of the spectral build
+    { UNIT_S,       kv::ring(256),  MTS_INTEGRATOR_VOLPATH,    ROW_EITHER, ROW_NO,     true },
+    { UNIT_S,       kv::ring(256),  MTS_INTEGRATOR_VOLPATHMIS, ROW_YES,    ROW_NO,     true },
+    // p / ps: `path` as the flat loop
+    { UNIT_P,       kv::FLAT,       MTS_INTEGRATOR_PATH,       ROW_EITHER, ROW_EITHER, false },
+    { UNIT_PS,      kv::FLAT,       MTS_INTEGRATOR_PATH,       ROW_EITHER, ROW_EITHER, true },
+#endif
+};
+// In order of preference: the first unit whose promises a scene keeps and which has a row for it renders it.
+const UnitRecord KERNEL_UNITS[] = {
+#if !defined(MTSAMD_BLOCKSTATS)
+    { UNIT_A,  MT_UNIT_A },                                     // every promise: no call left
+    { UNIT_B,  MT_UNIT_B },                                     // rpv and grids behind volume_eval() allowed
+    { UNIT_C,  MT_UNIT_C },                                     // ... and a BVH
+    { UNIT_H,  MT_UNIT_H },                                     // homogeneous media
+    { UNIT_S,  MT_UNIT_B },
+    { UNIT_P,  MT_UNIT_P_NEEDS },                               // compiled with MT_UNIT_P, of which `path` can reach these: a walked
+    { UNIT_PS, MT_UNIT_P_NEEDS },                               // primitive list, no spheres, no rpv
+#endif
+    { UNIT_GENERAL, 0 },
+};
+const size_t KERNEL_ROW_COUNT = sizeof(KERNEL_ROWS) / sizeof(KERNEL_ROWS[0]), KERNEL_UNIT_COUNT = sizeof(KERNEL_UNITS) / sizeof(KERNEL_UNITS[0]);
+
+// The render kernel of a scene, the one place that uses MTSAMD_KERNEL and MTSAMD_LEAN: the variant by the rules below, then the first
+// unit in order of preference whose promises the scene keeps and whose rows carry that variant for the scene.
+KernelChoice choose_kernel(const KernelFacts &f, uint32_t block_size, const RenderSwitches &sw) {
+    const bool path = f.integrator == MTS_INTEGRATOR_PATH, vol = f.integrator == MTS_INTEGRATOR_VOLPATH, mis = f.integrator == MTS_INTEGRATOR_VOLPATHMIS, spectral = f.spectral;
+    // MTSAMD_KERNEL = nested | flat | wga256 | wga1024 (default: asynchronous regrouping, 1024 paths served by 1024 threads)
+    int variant = sw.kernel >= 0 ? sw.kernel : kv::ring(1024);
+    // without media there are no tracking walks to regroup: the per-lane kernels win (cornell box 512 x 512 x 256, volpath: rings 992,
+    // per lane 1242 Msamples/s; `path` per lane: 2342, as one flat loop with regeneration 2910)
+    if (sw.kernel < 0 && !f.has_media && !path) variant = kv::NESTED;
+    if (path) variant = variant != kv::NESTED ? kv::FLAT : kv::NESTED;      // per lane: flat loop with regeneration (every variant), or nested (MTSAMD_KERNEL=nested)
+    if (kv::is_ring(variant)) {
+        uint32_t wg = (uint32_t) kv::ring_paths(variant);
+        if (mis) wg = std::min(wg, 512u);                       // four weight matrices per path: 512 paths fill the LDS
+        if (spectral) wg = std::min(wg, 256u);                  // four-wide spectra: 42 hot dwords per path; three 256-path workgroups per CU (12 waves) beat one of 512 (8 waves) by 10 %
+        // a workgroup of the regrouping kernels sits in ONE spiral block: blocks smaller than its path count get the largest
+        // workgroup that divides them (16 x 16 -> 256 paths); only blocks below 256 pixels fall back to the per-lane kernel
+        while (wg > 256 && (block_size * block_size) % wg != 0) wg /= 2;
+        variant = (block_size * block_size) % wg != 0 ? kv::FLAT : kv::ring((int) wg);
+    }
+    if (spectral && variant == kv::FLAT && !path) variant = kv::NESTED;     // the spectral build's per-lane flat kernel is `path`'s
+    // AOV channels (nbins / bins) and a sensor response function: `volpath` and (round 4) `volpathmis` carry them on the regrouping
+    // machines (their NEW blocks) and `path` in its flat loop (kernels.hip: path_pixel_flat); a discrete response function with repeated
+    // wavelengths keeps the volumetric integrators per lane
+    if ((f.has_bins || f.has_srf) && !(variant == kv::FLAT && path) && !(kv::is_ring(variant) && !path && f.srf_lookup_by_wavelength)) variant = kv::NESTED;
+    // Wavefront (gpu_*) streams carry their own PCG32 increment per (pixel, sample).  The regrouping machine of rgb / mono `volpath` keeps
+    // only the generator's 64-bit state in LDS and recomputes the increment on every load (round 4: wg_block's WF instantiation, 1024-path
+    // workgroups); everything else runs per lane, where the generator lives in registers: `volpath` as the flat state machine, the
+    // others nested
+    if (f.wavefront && kv::is_ring(variant) && !(variant == kv::ring(1024) && vol && !spectral)) variant = vol && !spectral ? kv::FLAT : kv::NESTED;
+    auto serves = [&](const KernelRow &r) {
+        auto admits = [](Tri t, bool v) { return t == ROW_EITHER || (t == ROW_YES) == v; };
+        return r.variant == variant && r.integrator == f.integrator && r.spectral == spectral && admits(r.spectral_mis, f.use_spectral_mis) && admits(r.wavefront, f.wavefront);
+    };
+    for (size_t u = 0; u < KERNEL_UNIT_COUNT; ++u) {
+        const UnitRecord &unit = KERNEL_UNITS[u];
+        // MTSAMD_LEAN = 0: never a lean unit; 2: unit a is skipped (a scene that qualifies for it runs on b)
+        if (unit.unit != UNIT_GENERAL && (sw.lean == 0 || (sw.lean == 2 && unit.unit == UNIT_A))) continue;
+        if ((f.traits & unit.promises) != unit.promises) continue;
+        for (size_t r = 0; r < KERNEL_ROW_COUNT; ++r)
+            if (KERNEL_ROWS[r].unit == unit.unit && serves(KERNEL_ROWS[r])) return { variant, unit.unit };
+    }
+    throw std::runtime_error("no render kernel for variant " + std::to_string(variant) + " of integrator " + std::to_string(f.integrator));
+}
+
+uint32_t plan_block_size(int32_t block_size_) {
+    // integrator.cpp:26-32,89-97: the reference's heuristic depends on the host thread count; this
+    // backend pins MTS_BLOCK_SIZE = 32 when the scene leaves block_size at 0
+    uint32_t block_size = block_size_ > 0 ? (uint32_t) block_size_ : 32u;
+    { uint32_t q = 1; while (q < block_size) q <<= 1; block_size = q; }
+    if (block_size > 1024) throw std::runtime_error("block_size too large");
+    return block_size;
+}
+
 RenderPlan plan_render(const DSensor &se, int32_t samples_per_pass_, int32_t block_size_, int32_t film_channels, int shard_index, int shard_count,
                        int cus, const RenderSwitches &sw) {
     RenderPlan p;
@@ -51,12 +165,7 @@ RenderPlan plan_render(const DSensor &se, int32_t samples_per_pass_, int32_t blo
     if (samples_per_pass == 0 || (total_spp % samples_per_pass) != 0)
         throw std::runtime_error("sample_count (" + std::to_string(total_spp) + ") must be a multiple of samples_per_pass (" + std::to_string(samples_per_pass) + ").");
     p.n_passes = (total_spp + samples_per_pass - 1) / samples_per_pass;
-    // integrator.cpp:26-32,89-97: the reference's heuristic depends on the host thread count; this
-    // backend pins MTS_BLOCK_SIZE = 32 when the scene leaves block_size at 0
-    uint32_t block_size = block_size_ > 0 ? (uint32_t) block_size_ : 32u;
-    { uint32_t q = 1; while (q < block_size) q <<= 1; block_size = q; }
-    if (block_size > 1024) throw std::runtime_error("block_size too large");
-    p.block_size = block_size;
+    const uint32_t block_size = p.block_size = plan_block_size(block_size_);
     // spiral.cpp: enumerate every (pass, block) pair in the reference's order; keep this shard's blocks
     Spiral spiral; spiral.init(se.crop_w, se.crop_h, se.crop_x, se.crop_y, (int) block_size, p.n_passes);
     // Passes are independent jobs (each block id seeds its own streams), so the (pass, block) pairs of this shard are launched together,
@@ -115,7 +224,7 @@ RenderPlan plan_render(const DSensor &se, int32_t samples_per_pass_, int32_t blo
 LptPolicy lpt_policy(int lpt, int variant, bool few_waves, const RenderPlan &plan, int cus, bool stop_requested) {
     const bool force = lpt == 2 || lpt == 3;
     uint32_t cal_spp = (uint32_t) std::max<size_t>(std::min<size_t>(4, plan.launch_spp / 128), force && plan.launch_spp >= 2 ? 1 : 0);
-    if (!(variant >= 10000 && plan.block_size <= 256 && lpt != 0 && (force || plan.chunks[0].size() > (size_t) std::max(cus, 1)) && !stop_requested)) cal_spp = 0;
+    if (!(kv::is_ring(variant) && plan.block_size <= 256 && lpt != 0 && (force || plan.chunks[0].size() > (size_t) std::max(cus, 1)) && !stop_requested)) cal_spp = 0;
     return { cal_spp, lpt == 3 || (lpt != 1 && few_waves) };
 }
 

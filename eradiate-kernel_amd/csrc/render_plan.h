@@ -1,13 +1,17 @@
 // render_plan.h -- the host arithmetic of mts_render (capi.cpp), apart from the device so that the CPU test-suite can pin it
-// (tests/test_render_plan.py): the render switches, the passes and blocks of a shard, and the cost-sorted schedule of each launch.
-// Plain C++17: dscene.h and the standard library only.
+// (tests/test_render_plan.py): the render switches, the kernel table and the choice of a scene's render kernel, the passes and blocks
+// of a shard, and the cost-sorted schedule of each launch.
+// Plain C++17: dscene.h, the C ABI's enums and the standard library only.
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <utility>
 #include <vector>
 #include "dscene.h"
+#include "kernel_names.h"                               // kv (nested, flat, ring(P), stat()) and enum KernelUnit
+#include "../../include/mtsamd.h"
 
 namespace mtsamd {
 
@@ -45,7 +49,7 @@ struct Spiral {
 
 // The switches of a render, read once, before anything else happens; a value outside the accepted ones is an error.
 struct RenderSwitches {
-    int kernel = -1;                  // MTSAMD_KERNEL: -1 unset, else the variant it names (nested 0, flat 1, wga256 10256, wga1024 11024)
+    int kernel = -1;                  // MTSAMD_KERNEL: -1 unset, else the variant it names (nested, flat, wga256 = ring(256), wga1024 = ring(1024))
     int lean = 1;                     // MTSAMD_LEAN: 0 never a lean unit, 1 the leanest unit a scene qualifies for, 2 unit b where a would do
     int lpt = -1;                     // MTSAMD_LPT: -1 unset, 0 spiral order, 1 whole blocks by cost, 2 the default forced, 3 tiles by cost (lpt_policy)
     bool lpt_debug = false;           // MTSAMD_LPT_DEBUG: set
@@ -55,6 +59,30 @@ struct RenderSwitches {
 };
 RenderSwitches read_render_switches();
 
+// ---- The kernel table: every render kernel choose_kernel can select, as the launchers of kernels.hip carry them (which keep the thread
+// counts and the instantiations).  A row serves a scene of its integrator and build whose spectral MIS and random streams it admits.
+enum Tri : int { ROW_NO = 0, ROW_YES = 1, ROW_EITHER = 2 };
+struct KernelRow {
+    KernelUnit unit; int variant; int integrator;       // MTS_INTEGRATOR_*
+    Tri spectral_mis;                                   // mts_integrator.use_spectral_mis (volpathmis)
+    Tri wavefront;                                      // the wavefront (gpu_*) streams: one generator per (pixel, sample)
+    bool spectral;                                      // the spectral build (MTS_SPEC_N = 4) or the rgb / mono one
+};
+// A unit and what a scene must keep of dscene.h's MT_* promises to run on it; KERNEL_UNITS lists them in order of preference.
+struct UnitRecord { KernelUnit unit; int promises; };
+extern const KernelRow KERNEL_ROWS[];
+extern const UnitRecord KERNEL_UNITS[];
+extern const size_t KERNEL_ROW_COUNT, KERNEL_UNIT_COUNT;
+
+// What the choice reads of a scene (capi.cpp: facts_of)
+struct KernelFacts {
+    int integrator;                                     // MTS_INTEGRATOR_*
+    bool spectral, use_spectral_mis, has_media, has_bins /* bin_count > 0 */, has_srf /* srf >= 0 */, srf_lookup_by_wavelength, wavefront;
+    int traits;                                         // MT_* (scene_host.cpp: scene_traits)
+};
+struct KernelChoice { int variant; KernelUnit unit; };
+KernelChoice choose_kernel(const KernelFacts &f, uint32_t block_size, const RenderSwitches &sw);
+
 // Passes, blocks and film slots of one shard of a render (integrator.cpp:58-97; the comments of render_plan.cpp say why).
 struct RenderPlan {
     uint32_t block_size;                        // a power of two
@@ -63,6 +91,7 @@ struct RenderPlan {
     std::vector<std::vector<DBlock>> chunks;    // this shard's (pass, block) entries in spiral order, cut into launches
     uint64_t samples;
 };
+uint32_t plan_block_size(int32_t block_size);          // the block size of a render: the scene's, or the default, as a power of two
 RenderPlan plan_render(const DSensor &se, int32_t samples_per_pass, int32_t block_size, int32_t film_channels, int shard_index, int shard_count,
                        int cus, const RenderSwitches &sw);
 

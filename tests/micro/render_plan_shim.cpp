@@ -28,6 +28,32 @@ int rp_switches(int64_t *out, char *err) {
     SHIM_CATCH
 }
 
+// choose_kernel under the environment's switches for `n` scenes, nine facts each: integrator, spectral, use_spectral_mis, media, bins, srf,
+// srf lookup by wavelength, wavefront, traits.  out: mts_stats.kernel_variant of each
+int rp_choose_kernel(const int32_t *facts, int64_t n, uint32_t block_size, int32_t *out, char *err) {
+    SHIM_TRY
+    const RenderSwitches sw = read_render_switches();
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t *f = facts + 9 * k;
+        const KernelChoice kc = choose_kernel({ f[0], f[1] != 0, f[2] != 0, f[3] != 0, f[4] != 0, f[5] != 0, f[6] != 0, f[7] != 0, f[8] }, block_size, sw);
+        out[k] = kv::stat(kc.variant, kc.unit);
+    }
+    SHIM_CATCH
+}
+
+// the kernel table: six words per row (unit, variant, integrator, spectral MIS and wavefront streams as 0 no / 1 yes / 2 either, spectral
+// build) and two per unit in order of preference (unit, promises); returns the number of rows, the number of units in *n_units
+int rp_kernel_rows(int32_t *rows, int32_t *units, int32_t *n_units) {
+    for (size_t r = 0; r < KERNEL_ROW_COUNT; ++r) {
+        const KernelRow &k = KERNEL_ROWS[r];
+        const int32_t v[6] = { k.unit, k.variant, k.integrator, k.spectral_mis, k.wavefront, k.spectral };
+        memcpy(rows + 6 * r, v, sizeof(v));
+    }
+    for (size_t u = 0; u < KERNEL_UNIT_COUNT; ++u) { units[2 * u] = KERNEL_UNITS[u].unit; units[2 * u + 1] = KERNEL_UNITS[u].promises; }
+    *n_units = (int32_t) KERNEL_UNIT_COUNT;
+    return (int) KERNEL_ROW_COUNT;
+}
+
 // plan_render under the environment's switches.  head: block_size, n_passes, split, launch_spp, film_floats, n_slots, pass_slots, samples,
 // number of chunks, number of entries; up to `cap` entries go to `blocks` and the size of each chunk (up to `cap`) to `chunk_sizes`.
 int rp_plan(const int32_t *crop /* x, y, w, h */, int32_t sample_count, int32_t wavefront, int32_t samples_per_pass, int32_t block_size,

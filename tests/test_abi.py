@@ -182,6 +182,57 @@ def test_scene_traits(L):
     assert traits(scenes.c5_atmosphere_spectral(16, 16, 4, layers=8), spectral=True) & B_UNIT == B_UNIT   # spectral variant: unit s
 
 
+def test_kernel_choice(L, monkeypatch):
+    """Which render kernel mts_render launches for a scene (render_plan.cpp: choose_kernel over the kernel table) from real scene
+    descriptions, without a GPU, through a host-only debug export: mts_stats.kernel_variant as the GPU suite asserts it of the same
+    scenes, and for every row of the kernel table the scene and switches that tests/test_gpu_parity.py renders it with."""
+    import tests.kernel_rows as kr
+    SD = importlib.import_module("eradiate-kernel_amd.scene_dict")
+    scenes = importlib.import_module("eradiate-kernel_amd.scenes")
+    L.mts_debug_kernel_choice.argtypes = [C.POINTER(A.SceneDesc), C.POINTER(C.c_int32)]
+    for name in kr.SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+
+    def choice(d, spectral=False, **integrator):
+        d = dict(d, integrator=dict(d["integrator"], **integrator))
+        desc, keep = SD.build_scene_desc(d, spectral=spectral)
+        v = C.c_int32(-1)
+        assert L.mts_debug_kernel_choice(C.byref(desc), C.byref(v)) == 0, L.mts_last_error()
+        return v.value
+
+    c3 = scenes.c3_heterogeneous(64, 64, 4, res=8)
+    assert choice(c3) == 111024 and choice(c3, type="volpathmis") == 110512                       # the metric scene: 1024 / 512 paths, unit a
+    assert choice(c3, block_size=16) == 10256 and choice(c3, block_size=8) == 1                   # 16 x 16 blocks: 256 paths, general
+    box = scenes.c1_cornell(32, 32, 4)
+    assert choice(box, type="volpath") == 0 and choice(box) == 400001                             # no media: per lane; `path`: the flat loop, unit p
+    assert choice(scenes.c4_atmosphere(32, 32, 4, layers=8)) == 211024 and choice(scenes.c2_homogeneous_slab(32, 32, 4)) == 611024
+    c5 = scenes.c5_atmosphere_spectral(16, 16, 4, layers=8)
+    assert choice(c5, spectral=True) == 310256 and choice(kr.spectral_cornell(16, 16, 4), spectral=True) == 500001
+    wave = scenes.c3_heterogeneous(64, 64, 4, res=8); wave["sensor"]["sampler"]["wavefront"] = True
+    assert choice(wave) == 11024 and choice(wave, type="volpathmis") == 0                         # wavefront streams: the general WF machine; nested
+    # bins around volpath under a discrete response function: on the machine, unless a wavelength repeats
+    slab = scenes.c2_homogeneous_slab(40, 24, 8)
+    slab["sun"]["irradiance"] = {"type": "uniform", "value": 1.5, "lambda_min": 380., "lambda_max": 780.}
+    slab["ground"]["bsdf"]["reflectance"] = {"type": "regular", "lambda_min": 400., "lambda_max": 800., "values": "0.2, 0.9, 0.4"}
+    slab["integrator"] = {"type": "bins", "bins": "a:400:500, b:500:600, c:600:800", "integrator": dict(slab["integrator"])}
+    for wavelengths, expect in (("450, 550, 650, 750", 10256), ("450, 550, 550, 750", 0)):
+        slab["sensor"]["srf"] = {"type": "discrete", "wavelengths": wavelengths, "values": "0.5, 1.0, 0.75, 0.25"}
+        assert choice(slab, spectral=True) == expect
+    monkeypatch.setenv("MTSAMD_LEAN", "0")
+    assert choice(box) == 1 and choice(c3) == 11024 and choice(c5, spectral=True) == 10256
+    monkeypatch.delenv("MTSAMD_LEAN")
+    for row, case in kr.ROWS.items():
+        for name in kr.SWITCHES:
+            monkeypatch.delenv(name, raising=False)
+        for name, value in case["env"].items():
+            monkeypatch.setenv(name, value)
+        assert choice(case["scene"](), spectral=row[5]) == kr.stat(row[1], row[0]), row
+    monkeypatch.setenv("MTSAMD_KERNEL", "wga512")                                                # the switches are read as mts_render reads them
+    desc, keep = SD.build_scene_desc(c3)
+    v = C.c_int32(-1)
+    assert L.mts_debug_kernel_choice(C.byref(desc), C.byref(v)) != 0 and b"MTSAMD_KERNEL must be one of" in L.mts_last_error()
+
+
 def test_binary_identifies_its_sources(L, tmp_path, monkeypatch):
     """mts_build_id(): the library carries a hash of the sources, headers and flags it was built from; the build script rebuilds when
     the tree's hash differs (no mtimes), and the binding refuses a library that is not the tree's -- a header touched without a

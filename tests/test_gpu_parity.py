@@ -10,6 +10,7 @@ import importlib
 import numpy as np
 import pytest
 
+import tests.kernel_rows as kr
 import tests.oracle_binding as ob
 import tests.transport_cases as tc
 from tests.golden_util import golden_cases, load_golden
@@ -1255,14 +1256,7 @@ def gpu_spectral(pkg):
     pkg.set_variant("gpu_rgb")
 
 
-def _spectral_cornell(width, height, spp):
-    d = scenes.c1_cornell(width, height, spp)
-    for k, v in d.items():
-        if isinstance(v, dict) and "bsdf" in v:
-            rgb = v["bsdf"]["reflectance"]["value"]
-            v["bsdf"]["reflectance"] = {"type": "regular", "lambda_min": 400., "lambda_max": 700., "values": [rgb[2], rgb[1], rgb[0]]}
-    d["light"]["emitter"]["radiance"] = {"type": "d65", "scale": 3.0}
-    return d
+_spectral_cornell = kr.spectral_cornell
 
 
 def _spectral_cases():
@@ -1504,7 +1498,7 @@ def _sample_head_scenes(spectral, integrator):
 
 
 def _sample_head_variant(spectral, integrator, kernel, name):
-    """mts_stats.kernel_variant modulo the lean unit (capi.cpp: choose_kernel): 0 nested per lane, 1 flat per lane, 10000 + paths per workgroup."""
+    """mts_stats.kernel_variant modulo the lean unit (render_plan.cpp: choose_kernel): 0 nested per lane, 1 flat per lane, 10000 + paths per workgroup."""
     if kernel == "nested":
         return 0
     if integrator == "path" or kernel == "flat":
@@ -1636,3 +1630,36 @@ def test_bin_integrators_srf_and_irregular_spectra(gpu_spectral):
     st = scene.integrator().last_stats
     assert st["kernel_variant"] % 100000 == 10256               # bins + srf on the regrouping machine (v_spectral::render_kernel_wga), not per lane
     assert (st["n_iter"], st["n_lookup"], st["n_nee_step"]) == (o.last_stats["n_iter"], o.last_stats["n_lookup"], o.last_stats["n_nee_step"])
+
+
+_KERNEL_ROW_REFS = {}
+
+
+@pytest.mark.parametrize("row", sorted(kr.ROWS), ids=lambda r: "unit%d-%d-integ%d-mis%d-wf%d-%s" % (r[:5] + ("spectral" if r[5] else "rgb",)))
+def test_every_row_of_the_kernel_table_launches(pkg, gpu_rgb, monkeypatch, row):
+    """Every render kernel mts_render can choose (render_plan.cpp: KERNEL_ROWS; tests/kernel_rows.py names a scene and the switches for
+    each row) launches: one spiral block, two samples per pixel, reported as the row's unit and variant, the film the oracle's."""
+    case = kr.ROWS[row]
+    unit, variant, spectral = row[0], row[1], row[5]
+    for name in kr.SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in case["env"].items():
+        monkeypatch.setenv(name, value)
+    d = case["scene"]()
+    if (case["name"], spectral) not in _KERNEL_ROW_REFS:
+        ref = ob.OracleScene(case["scene"](), spectral=spectral).render()
+        ref.setflags(write=False)
+        _KERNEL_ROW_REFS[(case["name"], spectral)] = ref
+    ref = _KERNEL_ROW_REFS[(case["name"], spectral)]
+    before = pkg.variant()
+    pkg.set_variant("gpu_spectral" if spectral else "gpu_rgb")
+    try:
+        gpu, st = gpu_render(pkg, d)
+    finally:
+        pkg.set_variant(before)
+    assert st["kernel_variant"] == kr.stat(variant, unit), st["kernel_variant"]
+    assert ref[..., :3].max() > 0
+    if case["exact"]:
+        assert np.array_equal(gpu, ref), (int((gpu != ref).sum()), float(np.abs(gpu - ref).max()))
+    else:
+        assert_parity(gpu, ref)

@@ -1,5 +1,6 @@
 """The host arithmetic of mts_render (csrc/render_plan.cpp) on the CPU: spiral, shards and launches, film slots and the wavefront split,
-the smoothing of measured tile costs, the cost-sorted schedule, and the render switches.  GPU films cannot see any of it by design (the
+the smoothing of measured tile costs, the cost-sorted schedule, the render switches, and the kernel table with the choice of a scene's
+render kernel.  GPU films cannot see any of it by design (the
 order of blocks and tiles changes no pixel), so it is pinned here against restatements in Python.
 
 render_plan.cpp is compiled with g++ next to an extern "C" shim (tests/micro/render_plan_shim.cpp) and loaded by ctypes."""
@@ -10,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import tests.kernel_rows as kr
 import tests.oracle_binding as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,6 +32,8 @@ def L(tmp_path_factory):
     lib.rp_lpt_policy.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_int, i64p, C.c_char_p]
     lib.rp_calibration_blocks.argtypes = [u32p, C.c_int64, u32p, i64p, C.c_char_p]
     lib.rp_smooth.argtypes = [u64p, u32p, C.c_int64, C.c_uint32, i32p, u64p, u32p, C.c_int, C.c_uint32, C.c_char_p]
+    lib.rp_choose_kernel.argtypes = [i32p, C.c_int64, C.c_uint32, i32p, C.c_char_p]
+    lib.rp_kernel_rows.argtypes = [i32p, i32p, i32p]
     lib.rp_schedule.argtypes = [u32p, C.c_int64, u64p, u32p, C.c_int64, u64p, C.c_int64, C.c_uint32, C.c_int, C.c_uint32, C.c_int64, u32p, i64p, C.c_char_p]
     return lib
 
@@ -284,3 +288,116 @@ def test_switches_reject_other_values(L, env, name, value, message):
         switches(L)
     with pytest.raises(RuntimeError, match=message):                       # before any planning, whatever the scene
         plan(L, (0, 0, 8, 8), 4)
+
+
+# ---------------------------------------------------------------- the kernel table and the choice of a scene's render kernel
+MEDIA, NO_BVH, NO_SPHERE, NO_GRID_EVAL, NO_SHAPE_EMITTER, NO_PHASE_TREE, NO_RPV, HOMOG = (1 << k for k in range(8))      # dscene.h: MT_*
+UNIT_A = MEDIA | NO_BVH | NO_SPHERE | NO_GRID_EVAL | NO_SHAPE_EMITTER | NO_PHASE_TREE | NO_RPV
+UNIT_B = MEDIA | NO_BVH | NO_SPHERE | NO_SHAPE_EMITTER | NO_PHASE_TREE
+FACTS = ("integrator", "spectral", "use_spectral_mis", "media", "bins", "srf", "srf_lookup_by_wavelength", "wavefront", "traits")
+
+
+def kernel_table(L):
+    rows, units, n_units = np.zeros((256, 6), np.int32), np.zeros((16, 2), np.int32), np.zeros(1, np.int32)
+    n = L.rp_kernel_rows(rows, units, n_units)
+    return [tuple(int(v) for v in r[:5]) + (bool(r[5]),) for r in rows[:n]], [(int(u), int(p)) for u, p in units[:n_units[0]]]
+
+
+def choose(L, facts, block_size=32):
+    facts = np.ascontiguousarray(facts, np.int32).reshape(-1, 9)
+    out = np.zeros(len(facts), np.int32)
+    call(L.rp_choose_kernel, facts, len(facts), block_size, out)
+    return out
+
+
+def choose_one(L, block_size=32, **f):
+    facts = dict(integrator=kr.VOLPATH, spectral=0, use_spectral_mis=1, media=1, bins=0, srf=0, srf_lookup_by_wavelength=1, wavefront=0, traits=0)
+    assert set(f) <= set(facts)
+    facts.update(f)
+    return int(choose(L, [facts[k] for k in FACTS], block_size)[0])
+
+
+def test_kernel_table_lists_every_unit_once(L):
+    rows, units = kernel_table(L)
+    assert len(set(rows)) == len(rows) and sorted(u for u, _ in units) == list(range(8)) == sorted({r[0] for r in rows})
+    assert [u for u, _ in units] == [kr.A, kr.B, kr.C, kr.H, kr.S, kr.P, kr.PS, kr.GENERAL]        # the order of preference
+    promises = dict(units)
+    assert promises[kr.GENERAL] == 0 and promises[kr.A] == UNIT_A and promises[kr.B] == promises[kr.S] == UNIT_B
+    assert promises[kr.C] == UNIT_B & ~NO_BVH and promises[kr.H] == (UNIT_A & ~MEDIA & ~NO_RPV) | HOMOG
+    assert promises[kr.P] == promises[kr.PS] == NO_BVH | NO_SPHERE | NO_RPV
+    # a unit of the spectral build holds spectral rows only, and the other way round
+    assert {r[0] for r in rows if r[5]} == {kr.GENERAL, kr.S, kr.PS} and {r[0] for r in rows if not r[5]} == {kr.GENERAL, kr.A, kr.B, kr.C, kr.H, kr.P}
+
+
+def test_every_row_of_the_kernel_table_has_a_scene(L):
+    assert set(kr.ROWS) == set(kernel_table(L)[0])
+
+
+def test_choice_over_the_whole_input_space(L, env):
+    """Every scene the choice can tell apart -- 3 integrators x 7 yes / no facts x 256 trait masks -- under every value of MTSAMD_KERNEL
+    and MTSAMD_LEAN and block sizes 8 .. 64: the result is always a row of the table that serves the scene, every row is reached, a
+    lean unit only ever renders a scene that keeps its promises, and a ring's paths divide the block."""
+    rows, units = kernel_table(L)
+    promises = dict(units)
+    grid = np.stack(np.meshgrid(np.arange(3), *[np.arange(2)] * 7, np.arange(256), indexing="ij"), -1).reshape(-1, 9).astype(np.int32)
+    assert len(grid) == 3 * 128 * 256
+    integ, spectral, smis, wavefront, traits = grid[:, 0], grid[:, 1], grid[:, 2], grid[:, 7], grid[:, 8]
+    reached, cases = set(), 0
+    for kernel in (None, "nested", "flat", "wga256", "wga1024"):
+        for lean in ("0", "1", "2"):
+            env.setenv("MTSAMD_LEAN", lean)
+            if kernel is None: env.delenv("MTSAMD_KERNEL", raising=False)
+            else: env.setenv("MTSAMD_KERNEL", kernel)
+            for bs in (8, 16, 32, 64):
+                out = choose(L, grid, bs)
+                unit, variant = kr.stat_unit(out), kr.stat_variant(out)
+                cases += len(out)
+                served = np.zeros(len(out), bool)
+                for r in rows:
+                    m = (unit == r[0]) & (variant == r[1]) & (integ == r[2]) & (spectral == r[5])
+                    m &= (r[3] == kr.EITHER) | (smis == r[3])
+                    m &= (r[4] == kr.EITHER) | (wavefront == r[4])
+                    if m.any():
+                        reached.add(r)
+                    served |= m
+                assert served.all(), (kernel, lean, bs, grid[~served][0], out[~served][0])
+                if lean == "0":
+                    assert (unit == kr.GENERAL).all()
+                if lean == "2":
+                    assert (unit != kr.A).all()
+                for u, p in promises.items():
+                    assert (traits[unit == u] & p == p).all(), (u, kernel, lean, bs)
+                ringed = kr.is_ring(variant)
+                assert ((bs * bs) % (variant[ringed] - kr.ring(0)) == 0).all()
+    assert cases == 5 * 3 * 4 * 3 * 128 * 256 and reached == set(rows)
+
+
+def test_choice_of_the_scenes_the_gpu_suite_names(L, env):
+    """The kernels tests/test_gpu_parity.py expects of its scenes, from their facts alone."""
+    one = lambda **f: choose_one(L, **f)
+    c3 = dict(traits=UNIT_A)                                                                     # heterogeneous grey medium, every promise kept
+    assert one(**c3) == 111024 == kr.stat(kr.ring(1024), kr.A)                                   # C3-like scene
+    assert one(integrator=kr.VOLPATHMIS, **c3) == kr.stat(kr.ring(512), kr.A) == 110512          # volpathmis with spectral MIS on the same scene
+    assert one(integrator=kr.VOLPATHMIS, use_spectral_mis=0, **c3) == 10512                      # ... without: no lean kernel
+    assert one(media=0, traits=UNIT_A & ~MEDIA) == 0                                             # media-free volpath: nested per lane
+    box = dict(integrator=kr.PATH, media=0, traits=NO_BVH | NO_SPHERE | NO_GRID_EVAL | NO_PHASE_TREE | NO_RPV)
+    assert one(**box) == 400001                                                                  # Cornell `path`: the flat loop, unit p
+    env.setenv("MTSAMD_LEAN", "0")
+    assert one(**box) == 1 and one(**c3) == 11024
+    env.setenv("MTSAMD_LEAN", "2")
+    assert one(**c3) == 211024 and one(**box) == 400001
+    env.delenv("MTSAMD_LEAN")
+    assert one(spectral=1, traits=UNIT_B) == 310256                                              # spectral layered atmosphere: unit s
+    assert one(spectral=1, integrator=kr.VOLPATHMIS, traits=UNIT_B) == 310256 and one(spectral=1, traits=UNIT_B & ~MEDIA) == 10256
+    assert one(spectral=1, **box) == 500001                                                      # spectral `path` without BVH, spheres or rpv: unit ps
+    assert one(spectral=1, **dict(box, traits=box["traits"] & ~NO_SPHERE)) == 1
+    assert one(wavefront=1, **c3) == 11024                                                       # wavefront rgb volpath: the general 1024-path machine
+    assert one(wavefront=1, integrator=kr.VOLPATHMIS, **c3) == 0                                 # wavefront volpathmis: nested
+    assert one(wavefront=1, spectral=1, traits=UNIT_B) == 0 and one(wavefront=1, **box) == 400001
+    # bins with a discrete response function that repeats a wavelength: nested; with distinct wavelengths on the machine
+    assert one(spectral=1, bins=1, srf=1, srf_lookup_by_wavelength=0, traits=UNIT_B) == 0
+    assert one(spectral=1, bins=1, srf=1, traits=UNIT_B) == 310256 and one(spectral=1, bins=1, srf=1, srf_lookup_by_wavelength=0, **box) == 500001
+    assert one(block_size=16, traits=0) == 10256 and one(block_size=16, **c3) == 10256           # 16 x 16 blocks: 256 paths, general
+    assert one(block_size=16, integrator=kr.VOLPATHMIS, **c3) == 10256 and one(block_size=8, **c3) == 1
+    assert one(traits=UNIT_B) == 211024 and one(traits=UNIT_B & ~NO_BVH) == 711024               # rpv ground: b; a BVH: c
+    assert one(media=1, traits=(UNIT_A & ~MEDIA & ~NO_RPV) | HOMOG) == 611024                    # homogeneous media: h
