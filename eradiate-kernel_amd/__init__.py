@@ -307,11 +307,15 @@ class Scene:
                                           p.ctypes.data_as(A.fp), nn.ctypes.data_as(A.fp)))
         return {"t": t, "shape": shape, "prim_index": prim, "p": p, "n": nn}
 
+    def destroy(self):
+        """Frees the device scene now instead of with the last reference; the object is unusable afterwards."""
+        if getattr(self, "_handle", None):
+            A.lib().mts_scene_destroy(self._handle)
+            self._handle = None
+
     def __del__(self):
         try:
-            if getattr(self, "_handle", None):
-                A.lib().mts_scene_destroy(self._handle)
-                self._handle = None
+            self.destroy()
         except Exception:
             pass
 
@@ -415,3 +419,8 @@ for _p in ("mitsuba_amd",):
     import sys as _sys
     _sys.modules[_p + ".core"].xml = _sys.modules[_p + ".core.xml"]
 render = _virtual_module("render", Scene=Scene, Integrator=Integrator, Sensor=Sensor, Film=Film)
+# mitsuba.python.util (src/python/python/util.py): `from mitsuba_amd.python.util import traverse`
+from .params import ParameterMap, traverse                                   # noqa: E402
+_util = _virtual_module("python.util", traverse=traverse, ParameterMap=ParameterMap)
+python = _virtual_module("python", util=_util)
+_sys.modules["mitsuba_amd.python"].util = _sys.modules["mitsuba_amd.python.util"]

@@ -12,7 +12,7 @@ from . import _buildid
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTSAMD_LIB") or os.path.join(HERE, "libmtsamd.so")
 
-MTS_ABI_VERSION = 9
+MTS_ABI_VERSION = 10
 
 # enums (include/mtsamd.h)
 VOLUME_CONST, VOLUME_GRID, VOLUME_GRID_SPECTRAL = 0, 1, 2
@@ -28,6 +28,7 @@ SENSOR_PERSPECTIVE, SENSOR_DISTANT, SENSOR_MRADIANCEMETER, SENSOR_MDISTANT, SENS
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
 DISTANT_TARGET_NONE, DISTANT_TARGET_POINT, DISTANT_TARGET_SHAPE = 0, 1, 2
 INTEGRATOR_PATH, INTEGRATOR_VOLPATH, INTEGRATOR_VOLPATHMIS = 0, 1, 2
+OBJ_SPECTRUM, OBJ_VOLUME, OBJ_PHASE, OBJ_MEDIUM, OBJ_BSDF, OBJ_EMITTER = 0, 1, 2, 3, 4, 5
 
 f32 = C.c_float
 i32 = C.c_int32
@@ -121,14 +122,18 @@ class RenderOpts(C.Structure):
                 ("film_on_device", i32), ("collect_counters", i32), ("film_capacity", C.c_int64)]
 
 
+class Dirty(C.Structure):
+    _fields_ = [("object", i32), ("index", i32), ("device_data", C.c_void_p)]
+
+
 ABI_STRUCTS = {"mts_spectrum": Spectrum, "mts_transform": Transform, "mts_volume": Volume, "mts_phase": Phase, "mts_medium": Medium,
                "mts_bsdf": Bsdf, "mts_shape": Shape, "mts_emitter": Emitter, "mts_sensor": Sensor,
                "mts_integrator": Integrator, "mts_scene_desc": SceneDesc, "mts_stats": Stats,
-               "mts_render_opts": RenderOpts}
+               "mts_render_opts": RenderOpts, "mts_dirty": Dirty}
 
 # every symbol include/mtsamd.h declares
 ABI_SYMBOLS = ["mts_abi_version", "mts_build_id", "mts_last_error", "mts_device_count", "mts_scene_create", "mts_scene_destroy",
-               "mts_render", "mts_cancel", "mts_sigint_scope_enter", "mts_sigint_scope_exit", "mts_sample", "mts_sample_spectral", "mts_ray_intersect", "mts_abi_sizeof", "mts_sample_tea", "mts_wavefront_sampler"]
+               "mts_render", "mts_cancel", "mts_sigint_scope_enter", "mts_sigint_scope_exit", "mts_sample", "mts_sample_spectral", "mts_ray_intersect", "mts_abi_sizeof", "mts_sample_tea", "mts_wavefront_sampler", "mts_scene_update"]
 
 _lib = None
 
@@ -161,6 +166,10 @@ def lib():
     L.mts_ray_intersect.argtypes = [C.c_void_p, i32, fp, fp, fp, fp, fp, C.POINTER(i32), C.POINTER(i32), fp, fp]
     L.mts_sample_tea.argtypes = [C.c_int, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), fp]
     L.mts_wavefront_sampler.argtypes = [C.c_int, i32, C.c_uint64, i32, fp]
+    L.mts_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Dirty), i32, C.c_void_p]
+    # debug entries (not in the header): the host half of an update, and a hash of the device scene
+    L.mts_debug_update_plan.argtypes = [C.POINTER(SceneDesc), C.POINTER(SceneDesc), C.POINTER(Dirty), i32, C.POINTER(i32), C.POINTER(i32)]
+    L.mts_debug_scene_digest.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mts_abi_sizeof.argtypes = [C.c_char_p]
     L.mts_abi_sizeof.restype = C.c_int
     if L.mts_abi_version() != MTS_ABI_VERSION:

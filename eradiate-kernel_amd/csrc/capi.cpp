@@ -86,7 +86,7 @@ const char *mts_last_error(void) { return g_error.c_str(); }
 int mts_abi_sizeof(const char *name) {
 #define SZ(T) if (!strcmp(name, #T)) return (int) sizeof(T);
     SZ(mts_spectrum) SZ(mts_transform) SZ(mts_volume) SZ(mts_phase) SZ(mts_medium) SZ(mts_bsdf) SZ(mts_shape) SZ(mts_emitter)
-    SZ(mts_sensor) SZ(mts_integrator) SZ(mts_scene_desc) SZ(mts_stats) SZ(mts_render_opts)
+    SZ(mts_sensor) SZ(mts_integrator) SZ(mts_scene_desc) SZ(mts_stats) SZ(mts_render_opts) SZ(mts_dirty)
 #undef SZ
     return -1;
 }
@@ -200,6 +200,44 @@ int mts_debug_kernel_choice(const mts_scene_desc *desc, int32_t *kernel_variant)
         *kernel_variant = kv::stat(kc.variant, kc.unit);
     } catch (...) { free_host_scene(hs); throw; }
     free_host_scene(hs);
+    API_CATCH
+}
+
+// traverse() + params.update() of the reference (src/python/python/util.py:14-190): the dirty records of `desc` and everything derived
+// from them are rebuilt by the constructors' own functions and rewritten in place (scene_host.cpp: update_host_scene)
+int mts_scene_update(mts_scene *scene, const mts_scene_desc *desc, const mts_dirty *dirty, int32_t n, void *stream) {
+    API_TRY
+    if (!scene) throw std::runtime_error("mts_scene_update: scene is NULL");
+    // every entry that reads the device scene (mts_render for the whole render, mts_sample / _spectral, mts_ray_intersect, the digest) or
+    // rewrites it (another update) holds the handle's mutex: an update never waits for them, it is refused
+    std::unique_lock<std::mutex> guard(scene->render_mutex, std::try_to_lock);
+    if (!guard.owns_lock()) throw std::runtime_error("mts_scene_update: a render of this scene is in flight (or another call on this handle: a sample / intersection query, another update)");
+    update_host_scene(*scene->hs, desc, dirty, n, (hipStream_t) stream);
+    API_CATCH
+}
+
+// Not part of the ABI: the host half of an update -- build_host_scene(before), then mts_scene_update's work with `after` through the
+// host functions -- and what the next render would run on: the traits and mts_stats.kernel_variant.  No device is touched
+// (tests/test_traverse.py compares with mts_debug_scene_traits / mts_debug_kernel_choice of `after`).
+int mts_debug_update_plan(const mts_scene_desc *before, const mts_scene_desc *after, const mts_dirty *dirty, int32_t n, int32_t *traits, int32_t *kernel_variant) {
+    API_TRY
+    if (!traits || !kernel_variant) throw std::runtime_error("mts_debug_update_plan: NULL output");
+    HostScene *hs = build_host_scene(before);
+    try {
+        update_host_scene(*hs, after, dirty, n, nullptr);
+        const KernelChoice kc = choose_kernel(facts_of(*hs), plan_block_size(hs->integrator.block_size), read_render_switches());
+        *traits = hs->traits; *kernel_variant = kv::stat(kc.variant, kc.unit);
+    } catch (...) { free_host_scene(hs); throw; }
+    free_host_scene(hs);
+    API_CATCH
+}
+
+// Not part of the ABI: a hash of the device scene's contents (scene_host.cpp: digest_host_scene).  Two scenes with equal digests render equal films.
+int mts_debug_scene_digest(mts_scene *scene, uint64_t *out8) {
+    API_TRY
+    if (!scene || !out8) throw std::runtime_error("mts_debug_scene_digest: NULL argument");
+    std::lock_guard<std::mutex> guard(scene->render_mutex);
+    digest_host_scene(*scene->hs, out8);
     API_CATCH
 }
 
@@ -368,6 +406,7 @@ int mts_sample(mts_scene *scene, int32_t n, uint64_t seed_offset, const float *o
     if (!scene || n < 0) throw std::runtime_error("mts_sample: invalid argument");
     if (n == 0) return 0;
     HostScene &hs = *scene->hs;
+    std::lock_guard<std::mutex> guard(scene->render_mutex);         // not while an update rewrites the scene
     if (hs.integrator.spectral) throw std::runtime_error("mts_sample: the scene was built for the spectral variant (use mts_sample_spectral: the rays carry wavelengths)");
 #if defined(MTSAMD_HOST_ONLY)
     HOST_ONLY_STOP("mts_sample");
@@ -391,6 +430,7 @@ int mts_sample_spectral(mts_scene *scene, int32_t n, uint64_t seed_offset, const
     if (n == 0) return 0;
     if (!ox || !oy || !oz || !dx || !dy || !dz || !wavelengths || !out_spec || !out_valid) throw std::runtime_error("mts_sample_spectral: null array");
     HostScene &hs = *scene->hs;
+    std::lock_guard<std::mutex> guard(scene->render_mutex);         // not while an update rewrites the scene
     if (!hs.integrator.spectral) throw std::runtime_error("mts_sample_spectral: the scene was built for an rgb / mono variant (use mts_sample)");
 #if defined(MTSAMD_HOST_ONLY)
     HOST_ONLY_STOP("mts_sample_spectral");
@@ -446,6 +486,7 @@ int mts_ray_intersect(mts_scene *scene, int32_t n, const float *o, const float *
     if (!scene || n < 0) throw std::runtime_error("mts_ray_intersect: invalid argument");
     if (n == 0) return 0;
     HostScene &hs = *scene->hs; (void) hs;
+    std::lock_guard<std::mutex> guard(scene->render_mutex);         // not while an update rewrites the scene
 #if defined(MTSAMD_HOST_ONLY)
     HOST_ONLY_STOP("mts_ray_intersect");
 #else

@@ -378,6 +378,66 @@ hipError_t launch_film_sum_slots(float *d_film, const float *d_slots, size_t fil
     return hipGetLastError();
 }
 
+// ---- scene updates (mts_scene_update, capi.cpp): what Volume's constructor derives from a grid's data (scene_host.cpp: grid_stats) and
+// build_pair_grid's interleaving, in one pass over a grid that already lies in the scene's device memory.  Memory bound: 16-byte loads and
+// stores over a grid-stride loop, a scalar tail for the last count % 4 values; a bounded launch (launch_grid_update), one atomic per workgroup.
+__device__ __forceinline__ uint32_t grid_float_key(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : u | 0x80000000u; }
+// value k differs bitwise from the same channel of column (0, 0) of its z slice
+__device__ __forceinline__ bool grid_differs(const float *__restrict__ grid, uint32_t k, float v, uint32_t plane, uint32_t channels) {
+    const uint32_t r = k % plane, c = channels == 1 ? 0u : r % channels;
+    return __float_as_uint(grid[k - r + c]) != __float_as_uint(v);
+}
+__device__ __forceinline__ void grid_pair_store(const GridUpdateJob &j, uint32_t k, float v) {      // voxel k of a single-channel grid -> its slot(s) of the pair grid
+    const float o = j.partner[k];
+    const float s = j.slot == 0 ? v : o, a = j.slot == 0 ? o : v;
+    if (j.nx == 1) *reinterpret_cast<float4 *>(j.pair + 4 * (size_t) k) = make_float4(s, a, s, a);
+    else *reinterpret_cast<float2 *>(j.pair + 2 * (size_t) k) = make_float2(s, a);
+}
+__global__ void __launch_bounds__(256) grid_update_kernel(GridUpdateJob j) {
+    __shared__ uint32_t wave_key[4], wave_differs[4];
+    const uint32_t tid = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u, quads = j.count / 4u;
+    uint32_t key = 0u; bool differs = false;
+    for (uint32_t q = tid; q < quads; q += stride) {
+        const float4 v = reinterpret_cast<const float4 *>(j.grid)[q];
+        const float e[4] = { v.x, v.y, v.z, v.w };
+        if (j.stats) for (int i = 0; i < 4; ++i) { key = max(key, grid_float_key(e[i])); differs = differs || grid_differs(j.grid, 4u * q + i, e[i], j.plane, j.channels); }
+        if (j.pair) {
+            if (j.nx == 1) for (int i = 0; i < 4; ++i) grid_pair_store(j, 4u * q + i, e[i]);
+            else {                                                  // rows of nx >= 2 voxels: the pair grid is the two grids interleaved value by value
+                const float4 o = reinterpret_cast<const float4 *>(j.partner)[q];
+                const float4 s = j.slot == 0 ? v : o, a = j.slot == 0 ? o : v;
+                float4 *out = reinterpret_cast<float4 *>(j.pair + 8 * (size_t) q);
+                out[0] = make_float4(s.x, a.x, s.y, a.y); out[1] = make_float4(s.z, a.z, s.w, a.w);
+            }
+        }
+    }
+    if (tid < j.count - 4u * quads) {                              // the tail
+        const uint32_t k = 4u * quads + tid; const float v = j.grid[k];
+        if (j.stats) { key = max(key, grid_float_key(v)); differs = differs || grid_differs(j.grid, k, v, j.plane, j.channels); }
+        if (j.pair) grid_pair_store(j, k, v);
+    }
+    if (j.pair && tid == 0) {                                       // the padding voxel behind the last row
+        const size_t end = 2 * (size_t) (j.nx == 1 ? 2u * j.count : j.count);
+        j.pair[end] = 0.f; j.pair[end + 1] = 0.f;
+    }
+    if (!j.stats) return;                                           // uniform over the launch
+    for (int o = 32; o > 0; o >>= 1) key = max(key, (uint32_t) __shfl_xor((int) key, o, 64));
+    const bool wave_diff = __any(differs);
+    if ((threadIdx.x & 63u) == 0) { wave_key[threadIdx.x >> 6] = key; wave_differs[threadIdx.x >> 6] = wave_diff ? 1u : 0u; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicMax(j.stats, max(max(wave_key[0], wave_key[1]), max(wave_key[2], wave_key[3])));
+        if (wave_differs[0] | wave_differs[1] | wave_differs[2] | wave_differs[3]) atomicAnd(j.stats + 1, 0u);
+    }
+}
+hipError_t launch_grid_update(const GridUpdateJob &job, int compute_units, hipStream_t stream) {
+    if (job.count == 0 || !job.grid || (job.pair && (!job.partner || job.channels != 1 || job.nx == 0)) || job.plane == 0 || job.channels == 0) return hipErrorInvalidValue;
+    // enough workgroups to fill the device (eight of 256 threads per CU), never more than the data gives work to
+    const uint32_t quads = job.count / 4u, wanted = (quads + 255u) / 256u, bound = (uint32_t) (compute_units > 0 ? compute_units : 256) * 8u;
+    hipLaunchKernelGGL(grid_update_kernel, dim3(wanted < 1u ? 1u : (wanted < bound ? wanted : bound)), dim3(256), 0, stream, job);
+    return hipGetLastError();
+}
+
 size_t render_workspace_floats(uint64_t threads, int variant) {
     if (!kv::is_ring(variant)) return 0;
     const uint64_t wg = (uint64_t) kv::ring_paths(variant), padded = (threads + wg - 1) / wg * wg;

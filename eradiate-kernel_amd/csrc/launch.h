@@ -32,6 +32,20 @@ hipError_t launch_render_lean_p(const RenderArgs &a);
 hipError_t launch_render_lean_ps(const RenderArgs &a);
 // film = sum over k < count of the film-sized slot k of d_slots, added in slot order (the passes of a render: capi.cpp)
 hipError_t launch_film_sum_slots(float *d_film, const float *d_slots, size_t film_floats, uint32_t count, hipStream_t stream);
+// One pass over a grid a scene update has just written (mts_scene_update, capi.cpp): the statistics the volume's constructor
+// derives from the data and, where a medium keeps the grid interleaved with its partner, that pair grid (DMedium::pair_grid).
+struct GridUpdateJob {
+    const float *grid;          // the dirty grid in the scene's device memory: `count` floats, z slices of `plane` floats, voxels of `channels`
+    uint32_t count, plane, channels;
+    uint32_t *stats;            // NULL, or two words: [0] atomicMax of the order-preserving key of every value (grid_key_to_float), [1] set to 0
+                                // when some column differs bitwise from column (0, 0) of its slice; the caller presets { 0, 1 }
+    float *pair;                // NULL, or the pair grid `grid` belongs to (single-channel grids only) ...
+    const float *partner;       // ... the other grid of the pair, and which of the two slots of a voxel `grid` fills (0 sigma_t, 1 albedo)
+    uint32_t slot, nx;          // nx == 1: the column is stored twice (scene_host.cpp: build_pair_grid)
+};
+hipError_t launch_grid_update(const GridUpdateJob &job, int compute_units, hipStream_t stream);
+// the value behind a key of GridUpdateJob::stats[0]: keys order like the floats they stand for (-0 below +0; NaNs are outside the contract)
+inline float grid_key_to_float(uint32_t key) { const uint32_t u = (key & 0x80000000u) ? key ^ 0x80000000u : ~key; float f; __builtin_memcpy(&f, &u, 4); return f; }
 hipError_t launch_sample(const DScene &sc, int32_t n, uint64_t seed_offset, const float *d_rays, float *d_rgb, uint8_t *d_valid, hipStream_t stream);
 // spectral variant (kernels_spectral.hip): per-ray wavelengths (4 n floats), four-wide result
 hipError_t launch_sample_spectral(const DScene &sc, int32_t n, uint64_t seed_offset, const float *d_rays, const float *d_wavelengths, float *d_spec, uint8_t *d_valid,

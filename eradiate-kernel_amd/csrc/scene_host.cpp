@@ -7,7 +7,10 @@
 #include <cmath>
 #include <cstring>
 #include <algorithm>
+#include <map>
+#include <set>
 #include "scene_host.h"
+#include "launch.h"
 #include "cie_tables.h"
 
 namespace mtsamd {
@@ -222,6 +225,236 @@ static int scene_traits(const HostScene &hs, bool spectral) {
     return tr;
 }
 
+// ---------------------------------------------------------------- per-record constructors
+// build_host_scene runs them for every record of a description; update_host_scene (mts_scene_update) for the dirty records and the
+// records derived from them: creation and update share this code, so an updated scene holds what a fresh one would.
+
+// spectra (spectral variant; uniform.cpp:34-52, regular.cpp:27-58 + distr_1d.h:318-345)
+struct SpectrumArrays { std::vector<float> values, wavelengths, cdf; };
+static DSpectrum build_spectrum(const mts_spectrum &sp, SpectrumArrays &arrays) {
+    DSpectrum ds; memset(&ds, 0, sizeof(ds));
+    ds.type = sp.type; ds.value = sp.value; ds.lambda_min = sp.lambda_min; ds.lambda_max = sp.lambda_max;
+    if (sp.type == MTS_SPECTRUM_UNIFORM) {
+        ds.lambda_min = std::max(sp.lambda_min, 280.f); ds.lambda_max = std::min(sp.lambda_max, 2400.f);       // MTS_WAVELENGTH_MIN / MAX
+        if (!(ds.lambda_min < ds.lambda_max)) throw std::runtime_error("UniformSpectrum: 'lambda_min' must be less than 'lambda_max'");
+    } else if (sp.type == MTS_SPECTRUM_REGULAR) {
+        if (!(sp.lambda_min < sp.lambda_max)) throw std::runtime_error("ContinuousDistribution: invalid range!");
+        if (sp.count < 2 || !sp.values) throw std::runtime_error("ContinuousDistribution: needs at least two entries!");
+        bool mass = false;
+        for (int k = 0; k < sp.count; ++k) { if (sp.values[k] < 0.f) throw std::runtime_error("ContinuousDistribution: entries must be non-negative!"); mass = mass || sp.values[k] > 0.f; }
+        if (!mass) throw std::runtime_error("ContinuousDistribution: no probability mass found!");
+        arrays.values.assign(sp.values, sp.values + sp.count);
+        ds.count = sp.count;
+        const double interval_size = (double(sp.lambda_max) - double(sp.lambda_min)) / (sp.count - 1);
+        ds.inv_interval_size = (float) (1. / interval_size);
+    } else if (sp.type == MTS_SPECTRUM_IRREGULAR) {                  // irregular.cpp:33-63 + IrregularContinuousDistribution (distr_1d.h:560-600)
+        if (sp.count < 2 || !sp.values || !sp.wavelengths) throw std::runtime_error("IrregularContinuousDistribution: needs at least two entries!");
+        bool mass = false;
+        for (int k = 0; k < sp.count; ++k) {
+            if (sp.values[k] < 0.f) throw std::runtime_error("IrregularContinuousDistribution: entries must be non-negative!");
+            if (k > 0 && !(sp.wavelengths[k] > sp.wavelengths[k - 1])) throw std::runtime_error("IrregularContinuousDistribution: node positions must be strictly increasing!");
+            mass = mass || sp.values[k] > 0.f;
+        }
+        if (!mass) throw std::runtime_error("IrregularContinuousDistribution: no probability mass found!");
+        arrays.values.assign(sp.values, sp.values + sp.count);
+        arrays.wavelengths.assign(sp.wavelengths, sp.wavelengths + sp.count);
+        ds.count = sp.count; ds.lambda_min = sp.wavelengths[0]; ds.lambda_max = sp.wavelengths[sp.count - 1];
+    } else if (sp.type == MTS_SPECTRUM_DISCRETE) {                   // discrete.cpp:45-100 + DiscreteDistribution::update (distr_1d.h:49-83)
+        if (sp.count < 1 || !sp.values || !sp.wavelengths || !sp.pmf) throw std::runtime_error("DiscreteDistribution: empty distribution!");
+        arrays.values.assign(sp.values, sp.values + sp.count);
+        arrays.wavelengths.assign(sp.wavelengths, sp.wavelengths + sp.count);
+        std::vector<float> &cdf = arrays.cdf; cdf.resize((size_t) sp.count);
+        ds.count = sp.count; ds.valid_x = ds.valid_y = (uint32_t) -1;
+        double sum = 0.0;
+        for (int k = 0; k < sp.count; ++k) {
+            const double value = (double) sp.pmf[k];
+            sum += value; cdf[(size_t) k] = (float) sum;
+            if (value < 0.0) throw std::runtime_error("DiscreteDistribution: entries must be non-negative!");
+            else if (value > 0.0) { if (ds.valid_x == (uint32_t) -1) ds.valid_x = (uint32_t) k; ds.valid_y = (uint32_t) k; }
+        }
+        if (ds.valid_x == (uint32_t) -1) throw std::runtime_error("DiscreteDistribution: no probability mass found!");
+        ds.cdf_sum = (float) sum;
+    } else throw std::runtime_error("unknown spectrum type");
+    return ds;
+}
+
+// volumes (texture.cpp:89-92, texture.h:262-269, grid3d.cpp:137-161, volume_data.h:24-33,86-98)
+static bool volume_is_grid(const mts_volume &v) { return v.type == MTS_VOLUME_GRID || v.type == MTS_VOLUME_GRID_SPECTRAL; }
+// What the constructor derives from a grid's data.  The host loops; grid_update_kernel (kernels.hip) yields the same for a grid in device memory.
+// Outside the contract of both: NaNs, and the sign of a maximum that is a tie between -0 and +0 (this loop keeps the zero it met first, the
+// kernel's keys put -0 below +0: the two maxima then compare equal and may differ in the sign bit).
+struct GridStats { float max; int32_t columns_equal; };
+static GridStats grid_stats(const float *data, int nx, int ny, int nz, int channels) {
+    GridStats st;
+    const size_t n = (size_t) nx * ny * nz * channels;
+    float mx = -INFINITY;
+    for (size_t k = 0; k < n; ++k) mx = std::max(mx, data[k]);
+    st.max = mx;
+    {   // a profile that only varies with z (bitwise comparison: the lookups then read column (0, 0) for every corner)
+        const size_t row = (size_t) nx * channels, col = (size_t) channels;
+        bool equal = true;
+        for (size_t z = 0; z < (size_t) nz && equal; ++z) {
+            const float *base = data + z * (size_t) ny * row;
+            for (size_t c = 1; c < (size_t) ny * nx && equal; ++c) equal = memcmp(base, base + c * col, col * sizeof(float)) == 0;
+        }
+        st.columns_equal = equal ? 1 : 0;
+    }
+    return st;
+}
+// `known`: the statistics of the grid's data when the caller has them already (an update: validation, device grids); NULL: the host
+// loops over v.data, once the record has been validated.  `host_data`: v.data is what the grid holds (not so for mts_dirty::device_data).
+static void build_volume(const mts_volume &v, bool spectral, int32_t spectrum_count, bool host_data, const GridStats *known, DVolume &dv, DVolumeSp &vsp) {
+    memset(&dv, 0, sizeof(dv));
+    dv.type = v.type == MTS_VOLUME_GRID_SPECTRAL ? MTS_VOLUME_GRID : v.type; memcpy(dv.value, v.value, 12);
+    memset(&vsp, 0, sizeof(vsp)); vsp.value_sp = -1;
+    if (spectral && v.type == MTS_VOLUME_CONST) {
+        if (v.value_spectrum < 0 || v.value_spectrum >= spectrum_count) throw std::runtime_error("spectral variant: missing spectrum for a constvolume");
+        vsp.value_sp = v.value_spectrum;
+    }
+    if (v.type == MTS_VOLUME_GRID_SPECTRAL) {
+        if (!spectral) throw std::runtime_error("This volume data source can only be used with a spectral variant!");     // gridvolume_spectral.cpp:86-88
+        if (v.filter_type != MTS_FILTER_TRILINEAR) throw std::runtime_error("Invalid filter type, must be \"trilinear\"!");
+        if (v.channels < 2 || v.channels > 255) throw std::runtime_error("gridvolume_spectral: between 2 and 255 spectral nodes are supported");
+        vsp.spectral_grid = 1; vsp.lambda_min = v.lambda_min; vsp.lambda_max = v.lambda_max;
+    }
+    DXf w2l = xf_inverse(xf_from_abi(v.to_world));
+    if (volume_is_grid(v)) {
+        if (host_data && !v.data) throw std::runtime_error("gridvolume: missing data");
+        if ((long) v.nx * v.ny * v.nz < 8) throw std::runtime_error("Invalid grid dimensions (must have at least one value at each corner)");
+        if (v.type == MTS_VOLUME_GRID && v.channels != 1 && v.channels != 3) throw std::runtime_error("Unsupported channel count (expected 1 or 3)");
+        if (spectral && v.type == MTS_VOLUME_GRID && v.channels != 1)
+            throw std::runtime_error("spectral variant: 3-channel grids need the sRGB upsampling model (ext/rgb2spec data, absent); use gridvolume_spectral");
+        if ((int64_t) v.nx * v.ny * v.nz * v.channels >= (int64_t) 1 << 31) throw std::runtime_error("gridvolume: more than 2^31 values");
+        dv.nx = v.nx; dv.ny = v.ny; dv.nz = v.nz; dv.channels = v.channels; dv.filter = v.filter_type; dv.wrap = v.wrap_mode;
+        const GridStats st = known ? *known : grid_stats(v.data, v.nx, v.ny, v.nz, v.channels);
+        dv.max = st.max; dv.has_max = 1;
+        dv.columns_equal = st.columns_equal;
+        if (v.use_grid_bbox) {
+            F3 bmin = f3(v.file_bbox_min), bmax = f3(v.file_bbox_max);
+            w2l = xf_mul(xf_mul(xf_scale(vrcp(bmax - bmin)), xf_translate(-1.f * bmin)), w2l);
+        }
+        if (v.has_max_value) dv.max = v.max_value;
+    } else if (v.type != MTS_VOLUME_CONST) throw std::runtime_error("unknown volume type");
+    memcpy(dv.w2l, w2l.m, 64);
+    dv.affine = (w2l.m[12] == 0.f && w2l.m[13] == 0.f && w2l.m[14] == 0.f && w2l.m[15] == 1.f) ? 1 : 0;
+    DXf inv = xf_inverse(w2l);
+    F3 a = mat_point(inv.m, f3s(0.f)), b = mat_point(inv.m, f3s(1.f));
+    store3(dv.bbox.min, a); store3(dv.bbox.max, a); bbox_expand(dv.bbox, b);
+}
+
+// phase functions (hg.cpp:43-49, tabphase.cpp:33-51, distr_1d.h:293-345, blendphase.cpp:33-56).  `phases`: the records built so far
+// (a blendphase's children come before it); i: this record's index
+static DPhase build_phase(const mts_phase &p, int i, const std::vector<DPhase> &phases, int32_t phase_count, int32_t volume_count, std::vector<float> &pdf, std::vector<float> &cdf) {
+    DPhase dp; memset(&dp, 0, sizeof(dp));
+    dp.type = p.type; dp.g = p.g; dp.child[0] = p.child[0]; dp.child[1] = p.child[1]; dp.weight_volume = p.weight_volume;
+    if (p.type == MTS_PHASE_HG && (p.g >= 1 || p.g <= -1)) throw std::runtime_error("The asymmetry parameter must lie in the interval (-1, 1)!");
+    if (p.type == MTS_PHASE_BLEND) {
+        check_index(p.child[0], phase_count, "blendphase child", false);
+        check_index(p.child[1], phase_count, "blendphase child", false);
+        check_index(p.weight_volume, volume_count, "blendphase weight", false);
+        // nested blendphase plugins (blendphase.cpp:42-66: two arbitrary PhaseFunction children): children come before their parent
+        // in the description (the order a loader constructs them in; rules out cycles), DPhase::size = depth of the tree below
+        if (p.child[0] >= i || p.child[1] >= i) throw std::runtime_error("blendphase: a nested phase function must precede the blendphase that holds it");
+        int depth = 1;
+        for (int c = 0; c < 2; ++c)
+            if (phases[(size_t) p.child[c]].type == MTS_PHASE_BLEND) depth = std::max(depth, 1 + phases[(size_t) p.child[c]].size);
+        if (depth > 8) throw std::runtime_error("blendphase: more than 8 nested levels are not supported by this backend");
+        dp.size = depth;
+    } else if (p.type == MTS_PHASE_TABULATED) {
+        size_t size = (size_t) p.tab_count;
+        if (p.tab_count < 2 || !p.tab_values) throw std::runtime_error("ContinuousDistribution: needs at least two entries!");
+        pdf.assign(p.tab_values, p.tab_values + size); cdf.resize(size - 1);
+        dp.size = (int32_t) size; dp.range_x = -1.f; dp.range_y = 1.f;
+        dp.valid_x = dp.valid_y = (uint32_t) -1;
+        double range = double(dp.range_y) - double(dp.range_x), interval_size = range / (size - 1), integral = 0.;
+        for (size_t k = 0; k < size - 1; ++k) {
+            double y0 = (double) pdf[k], y1 = (double) pdf[k + 1];
+            double value = 0.5 * interval_size * (y0 + y1);
+            integral += value;
+            cdf[k] = (float) integral;
+            if (y0 < 0. || y1 < 0.) throw std::runtime_error("ContinuousDistribution: entries must be non-negative!");
+            else if (value > 0.) { if (dp.valid_x == (uint32_t) -1) dp.valid_x = (uint32_t) k; dp.valid_y = (uint32_t) k; }
+        }
+        if (dp.valid_x == (uint32_t) -1) throw std::runtime_error("ContinuousDistribution: no probability mass found!");
+        dp.integral = (float) integral; dp.normalization = (float) (1. / integral);
+        dp.interval_size = (float) interval_size; dp.inv_interval_size = (float) (1. / interval_size);
+    } else if (p.type < MTS_PHASE_ISOTROPIC || p.type > MTS_PHASE_TABULATED) throw std::runtime_error("unknown phase function type");
+    return dp;
+}
+
+// media (medium.cpp:12-29, homogeneous.cpp:21-28, heterogeneous.cpp:21-31), from the volume records they read.  Returns whether the medium
+// keeps its two grids interleaved as well (DMedium::pair_grid; build_pair_grid fills it)
+static bool build_medium(const mts_medium &m, const HostScene &hs, int32_t volume_count, int32_t phase_count, bool spectral, DMedium &dm) {
+    check_index(m.sigma_t_volume, volume_count, "medium sigma_t", false);
+    check_index(m.albedo_volume, volume_count, "medium albedo", false);
+    check_index(m.phase, phase_count, "medium phase", false);
+    memset(&dm, 0, sizeof(dm));
+    dm.type = m.type; dm.sigma_t = m.sigma_t_volume; dm.albedo = m.albedo_volume; dm.phase = m.phase; dm.scale = m.scale;
+    dm.sample_emitters = m.sample_emitters != 0; dm.has_spectral_extinction = m.has_spectral_extinction != 0;
+    dm.is_homogeneous = m.type == MTS_MEDIUM_HOMOGENEOUS;
+    if (m.type == MTS_MEDIUM_HETEROGENEOUS) {
+        const DVolume &st = hs.volumes[m.sigma_t_volume];
+        if (!st.has_max) throw std::runtime_error("max() not implemented (constvolume sigma_t in heterogeneous medium)");
+        dm.max_density = dm.scale * st.max;
+        // the kernels divide by the majorant two or three times per tracking step: with its correctly rounded reciprocal at hand an
+        // IEEE-exact quotient is five multiply-adds instead of the ~11-instruction division sequence (pm_div_by_invariant, pmath.h;
+        // the predicate that admits the majorant is pm_invariant_rcp, shared with the tests).
+        dm.inv_max_density = pm_invariant_rcp(dm.max_density);
+        dm.aabb = st.bbox;
+    } else if (m.type != MTS_MEDIUM_HOMOGENEOUS) throw std::runtime_error("unknown medium type");
+    // kernel fast paths that do not change a single bit of the result
+    const DVolume &a = hs.volumes[m.sigma_t_volume], &b = hs.volumes[m.albedo_volume];
+    dm.shared_grid = (a.type == MTS_VOLUME_GRID && b.type == MTS_VOLUME_GRID && a.nx == b.nx && a.ny == b.ny && a.nz == b.nz &&
+                      a.filter == b.filter && a.wrap == b.wrap && memcmp(a.w2l, b.w2l, 64) == 0) ? 1 : 0;
+    auto grey = [](const DVolume &v) { return v.type == MTS_VOLUME_GRID ? v.channels == 1 : (v.value[0] == v.value[1] && v.value[1] == v.value[2]); };
+    dm.grey = (grey(a) && grey(b) && !spectral) ? 1 : 0;       // spectral variant: values depend on the wavelength
+    if (spectral && dm.shared_grid) {                          // two gridvolume_spectral grids over one spectral interval: 2
+        const DVolumeSp &sa = hs.volume_sp[m.sigma_t_volume], &sb = hs.volume_sp[m.albedo_volume];
+        if (sa.spectral_grid && sb.spectral_grid && a.channels == b.channels && sa.lambda_min == sb.lambda_min && sa.lambda_max == sb.lambda_max)
+            dm.shared_grid = 2;
+    }
+    if (!(dm.shared_grid && a.channels == 1 && b.channels == 1 && a.filter == MTS_FILTER_TRILINEAR && a.wrap == MTS_WRAP_CLAMP)) return false;
+    memcpy(dm.pair_w2l, a.w2l, 64); dm.pair_nx = a.nx; dm.pair_ny = a.ny; dm.pair_nz = a.nz; dm.pair_affine = (a.affine ? 1 : 0) | ((a.columns_equal && b.columns_equal) ? 2 : 0);
+    return true;
+}
+// the two grids of such a medium interleaved, voxel by voxel {sigma_t, albedo}
+static void build_pair_grid(const DVolume &a, const std::vector<float> &ga, const std::vector<float> &gb, std::vector<float> &pair) {
+    // rows of at least two voxels (one 16-byte gather = both x-neighbours of both grids): a one-column grid -- the
+    // nz x 1 x 1 grids of 1-D atmospheres -- is stored with its column twice; both x-neighbours clamp to voxel 0 anyway
+    const size_t sx = a.nx < 2 ? 2 : (size_t) a.nx, rows = (size_t) a.ny * a.nz;
+    pair.assign(2 * (sx * rows + 1), 0.f);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t x = 0; x < sx; ++x) {
+            const size_t src = r * (size_t) a.nx + (x < (size_t) a.nx ? x : (size_t) a.nx - 1);
+            pair[2 * (r * sx + x)] = ga[src]; pair[2 * (r * sx + x) + 1] = gb[src];
+        }
+}
+
+static DBsdf build_bsdf(const mts_bsdf &b) {
+    if (b.type < MTS_BSDF_DIFFUSE || b.type > MTS_BSDF_BILAMBERTIAN) throw std::runtime_error("unknown BSDF type");
+    DBsdf db; memset(&db, 0, sizeof(db));
+    db.type = b.type; memcpy(db.reflectance, b.reflectance, 12); memcpy(db.rho_0, b.rho_0, 12); memcpy(db.k, b.k, 12);
+    memcpy(db.g, b.g, 12); memcpy(db.rho_c, b.rho_c, 12); memcpy(db.transmittance, b.transmittance, 12); db.flags = bsdf_flags(b.type);
+    return db;
+}
+// which of the six colour parameters each BSDF plugin reads (spectral variant: the spectra it needs)
+static const bool BSDF_SP_USED[4][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */ };
+
+// an emitter's record; the scene's bounding sphere comes from set_scene (scene.cpp:95-97)
+static DEmitter build_emitter(const mts_emitter &e, const float center[3], float bsphere_radius) {
+    DEmitter de; memset(&de, 0, sizeof(de));
+    de.type = e.type; de.to_world = xf_from_abi(e.to_world); memcpy(de.radiance, e.radiance, 12); de.shape = e.shape;
+    memcpy(de.bsphere_center, center, 12); de.bsphere_radius = bsphere_radius;
+    return de;
+}
+// the response function's weights can be recovered from the sampled wavelengths (srf_weights_of, integrator_dev.h, looks a weight up by its wavelength)
+static bool srf_lookup_by_wavelength(const HostScene &hs) {
+    if (hs.scene.srf < 0 || hs.spectra[(size_t) hs.scene.srf].type != MTS_SPECTRUM_DISCRETE) return true;
+    const std::vector<float> &w = hs.spectrum_wavelengths[(size_t) hs.scene.srf];
+    for (size_t k = 1; k < w.size(); ++k) if (!(w[k] > w[k - 1])) return false;
+    return true;
+}
+
 HostScene *build_host_scene(const mts_scene_desc *d) {
     if (!d) throw std::runtime_error("scene description is NULL");
     if (d->abi_version != MTS_ABI_VERSION) throw std::runtime_error("scene description: ABI version mismatch");
@@ -233,51 +466,9 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     if (spectral) {
         if (d->integrator.monochrome) throw std::runtime_error("a scene is either monochromatic or spectral");
         for (int i = 0; i < d->spectrum_count; ++i) {
-            const mts_spectrum &sp = d->spectra[i];
-            DSpectrum ds; memset(&ds, 0, sizeof(ds));
-            ds.type = sp.type; ds.value = sp.value; ds.lambda_min = sp.lambda_min; ds.lambda_max = sp.lambda_max;
-            hs.spectrum_values.emplace_back(); hs.spectrum_wavelengths.emplace_back(); hs.spectrum_cdf.emplace_back();
-            if (sp.type == MTS_SPECTRUM_UNIFORM) {
-                ds.lambda_min = std::max(sp.lambda_min, 280.f); ds.lambda_max = std::min(sp.lambda_max, 2400.f);       // MTS_WAVELENGTH_MIN / MAX
-                if (!(ds.lambda_min < ds.lambda_max)) throw std::runtime_error("UniformSpectrum: 'lambda_min' must be less than 'lambda_max'");
-            } else if (sp.type == MTS_SPECTRUM_REGULAR) {
-                if (!(sp.lambda_min < sp.lambda_max)) throw std::runtime_error("ContinuousDistribution: invalid range!");
-                if (sp.count < 2 || !sp.values) throw std::runtime_error("ContinuousDistribution: needs at least two entries!");
-                bool mass = false;
-                for (int k = 0; k < sp.count; ++k) { if (sp.values[k] < 0.f) throw std::runtime_error("ContinuousDistribution: entries must be non-negative!"); mass = mass || sp.values[k] > 0.f; }
-                if (!mass) throw std::runtime_error("ContinuousDistribution: no probability mass found!");
-                hs.spectrum_values.back().assign(sp.values, sp.values + sp.count);
-                ds.count = sp.count;
-                const double interval_size = (double(sp.lambda_max) - double(sp.lambda_min)) / (sp.count - 1);
-                ds.inv_interval_size = (float) (1. / interval_size);
-            } else if (sp.type == MTS_SPECTRUM_IRREGULAR) {                  // irregular.cpp:33-63 + IrregularContinuousDistribution (distr_1d.h:560-600)
-                if (sp.count < 2 || !sp.values || !sp.wavelengths) throw std::runtime_error("IrregularContinuousDistribution: needs at least two entries!");
-                bool mass = false;
-                for (int k = 0; k < sp.count; ++k) {
-                    if (sp.values[k] < 0.f) throw std::runtime_error("IrregularContinuousDistribution: entries must be non-negative!");
-                    if (k > 0 && !(sp.wavelengths[k] > sp.wavelengths[k - 1])) throw std::runtime_error("IrregularContinuousDistribution: node positions must be strictly increasing!");
-                    mass = mass || sp.values[k] > 0.f;
-                }
-                if (!mass) throw std::runtime_error("IrregularContinuousDistribution: no probability mass found!");
-                hs.spectrum_values.back().assign(sp.values, sp.values + sp.count);
-                hs.spectrum_wavelengths.back().assign(sp.wavelengths, sp.wavelengths + sp.count);
-                ds.count = sp.count; ds.lambda_min = sp.wavelengths[0]; ds.lambda_max = sp.wavelengths[sp.count - 1];
-            } else if (sp.type == MTS_SPECTRUM_DISCRETE) {                   // discrete.cpp:45-100 + DiscreteDistribution::update (distr_1d.h:49-83)
-                if (sp.count < 1 || !sp.values || !sp.wavelengths || !sp.pmf) throw std::runtime_error("DiscreteDistribution: empty distribution!");
-                hs.spectrum_values.back().assign(sp.values, sp.values + sp.count);
-                hs.spectrum_wavelengths.back().assign(sp.wavelengths, sp.wavelengths + sp.count);
-                std::vector<float> &cdf = hs.spectrum_cdf.back(); cdf.resize((size_t) sp.count);
-                ds.count = sp.count; ds.valid_x = ds.valid_y = (uint32_t) -1;
-                double sum = 0.0;
-                for (int k = 0; k < sp.count; ++k) {
-                    const double value = (double) sp.pmf[k];
-                    sum += value; cdf[(size_t) k] = (float) sum;
-                    if (value < 0.0) throw std::runtime_error("DiscreteDistribution: entries must be non-negative!");
-                    else if (value > 0.0) { if (ds.valid_x == (uint32_t) -1) ds.valid_x = (uint32_t) k; ds.valid_y = (uint32_t) k; }
-                }
-                if (ds.valid_x == (uint32_t) -1) throw std::runtime_error("DiscreteDistribution: no probability mass found!");
-                ds.cdf_sum = (float) sum;
-            } else throw std::runtime_error("unknown spectrum type");
+            SpectrumArrays arrays;
+            const DSpectrum ds = build_spectrum(d->spectra[i], arrays);
+            hs.spectrum_values.push_back(std::move(arrays.values)); hs.spectrum_wavelengths.push_back(std::move(arrays.wavelengths)); hs.spectrum_cdf.push_back(std::move(arrays.cdf));
             hs.spectra.push_back(ds);
         }
     }
@@ -294,155 +485,36 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     // ---- volumes (texture.cpp:89-92, texture.h:262-269, grid3d.cpp:137-161, volume_data.h:24-33,86-98)
     for (int i = 0; i < d->volume_count; ++i) {
         const mts_volume &v = d->volumes[i];
-        DVolume dv; memset(&dv, 0, sizeof(dv));
-        dv.type = v.type == MTS_VOLUME_GRID_SPECTRAL ? MTS_VOLUME_GRID : v.type; memcpy(dv.value, v.value, 12);
-        DVolumeSp vsp; memset(&vsp, 0, sizeof(vsp)); vsp.value_sp = -1;
-        if (spectral && v.type == MTS_VOLUME_CONST) vsp.value_sp = spectrum_index(v.value_spectrum, "a constvolume");
-        if (v.type == MTS_VOLUME_GRID_SPECTRAL) {
-            if (!spectral) throw std::runtime_error("This volume data source can only be used with a spectral variant!");     // gridvolume_spectral.cpp:86-88
-            if (v.filter_type != MTS_FILTER_TRILINEAR) throw std::runtime_error("Invalid filter type, must be \"trilinear\"!");
-            if (v.channels < 2 || v.channels > 255) throw std::runtime_error("gridvolume_spectral: between 2 and 255 spectral nodes are supported");
-            vsp.spectral_grid = 1; vsp.lambda_min = v.lambda_min; vsp.lambda_max = v.lambda_max;
-        }
+        DVolume dv; DVolumeSp vsp;
+        build_volume(v, spectral, d->spectrum_count, true, nullptr, dv, vsp);
         hs.volume_sp.push_back(vsp);
-        DXf w2l = xf_inverse(xf_from_abi(v.to_world));
-        if (v.type == MTS_VOLUME_GRID || v.type == MTS_VOLUME_GRID_SPECTRAL) {
-            if (!v.data) throw std::runtime_error("gridvolume: missing data");
-            if ((long) v.nx * v.ny * v.nz < 8) throw std::runtime_error("Invalid grid dimensions (must have at least one value at each corner)");
-            if (v.type == MTS_VOLUME_GRID && v.channels != 1 && v.channels != 3) throw std::runtime_error("Unsupported channel count (expected 1 or 3)");
-            if (spectral && v.type == MTS_VOLUME_GRID && v.channels != 1)
-                throw std::runtime_error("spectral variant: 3-channel grids need the sRGB upsampling model (ext/rgb2spec data, absent); use gridvolume_spectral");
-            if ((int64_t) v.nx * v.ny * v.nz * v.channels >= (int64_t) 1 << 31) throw std::runtime_error("gridvolume: more than 2^31 values");
-            dv.nx = v.nx; dv.ny = v.ny; dv.nz = v.nz; dv.channels = v.channels; dv.filter = v.filter_type; dv.wrap = v.wrap_mode;
-            size_t n = (size_t) v.nx * v.ny * v.nz * v.channels;
-            float mx = -INFINITY;
-            for (size_t k = 0; k < n; ++k) mx = std::max(mx, v.data[k]);
-            dv.max = mx; dv.has_max = 1;
-            {   // a profile that only varies with z (bitwise comparison: the lookups then read column (0, 0) for every corner)
-                const size_t row = (size_t) v.nx * v.channels, col = (size_t) v.channels;
-                bool equal = true;
-                for (size_t z = 0; z < (size_t) v.nz && equal; ++z) {
-                    const float *base = v.data + z * (size_t) v.ny * row;
-                    for (size_t c = 1; c < (size_t) v.ny * v.nx && equal; ++c) equal = memcmp(base, base + c * col, col * sizeof(float)) == 0;
-                }
-                dv.columns_equal = equal ? 1 : 0;
-            }
-            hs.grid_data.emplace_back(v.data, v.data + n);
-            if (v.use_grid_bbox) {
-                F3 bmin = f3(v.file_bbox_min), bmax = f3(v.file_bbox_max);
-                w2l = xf_mul(xf_mul(xf_scale(vrcp(bmax - bmin)), xf_translate(-1.f * bmin)), w2l);
-            }
-            if (v.has_max_value) dv.max = v.max_value;
-        } else if (v.type != MTS_VOLUME_CONST) throw std::runtime_error("unknown volume type");
+        if (volume_is_grid(v)) hs.grid_data.emplace_back(v.data, v.data + (size_t) v.nx * v.ny * v.nz * v.channels);
         else hs.grid_data.emplace_back();
-        memcpy(dv.w2l, w2l.m, 64);
-        dv.affine = (w2l.m[12] == 0.f && w2l.m[13] == 0.f && w2l.m[14] == 0.f && w2l.m[15] == 1.f) ? 1 : 0;
-        DXf inv = xf_inverse(w2l);
-        F3 a = mat_point(inv.m, f3s(0.f)), b = mat_point(inv.m, f3s(1.f));
-        store3(dv.bbox.min, a); store3(dv.bbox.max, a); bbox_expand(dv.bbox, b);
         hs.volumes.push_back(dv);
     }
     // ---- phase functions (hg.cpp:43-49, tabphase.cpp:33-51, distr_1d.h:293-345, blendphase.cpp:33-56)
     for (int i = 0; i < d->phase_count; ++i) {
-        const mts_phase &p = d->phases[i];
-        DPhase dp; memset(&dp, 0, sizeof(dp));
-        dp.type = p.type; dp.g = p.g; dp.child[0] = p.child[0]; dp.child[1] = p.child[1]; dp.weight_volume = p.weight_volume;
         hs.tab_pdf.emplace_back(); hs.tab_cdf.emplace_back();
-        if (p.type == MTS_PHASE_HG && (p.g >= 1 || p.g <= -1)) throw std::runtime_error("The asymmetry parameter must lie in the interval (-1, 1)!");
-        if (p.type == MTS_PHASE_BLEND) {
-            check_index(p.child[0], d->phase_count, "blendphase child", false);
-            check_index(p.child[1], d->phase_count, "blendphase child", false);
-            check_index(p.weight_volume, d->volume_count, "blendphase weight", false);
-            // nested blendphase plugins (blendphase.cpp:42-66: two arbitrary PhaseFunction children): children come before their parent
-            // in the description (the order a loader constructs them in; rules out cycles), DPhase::size = depth of the tree below
-            if (p.child[0] >= i || p.child[1] >= i) throw std::runtime_error("blendphase: a nested phase function must precede the blendphase that holds it");
-            int depth = 1;
-            for (int c = 0; c < 2; ++c)
-                if (d->phases[p.child[c]].type == MTS_PHASE_BLEND) depth = std::max(depth, 1 + hs.phases[(size_t) p.child[c]].size);
-            if (depth > 8) throw std::runtime_error("blendphase: more than 8 nested levels are not supported by this backend");
-            dp.size = depth;
-        } else if (p.type == MTS_PHASE_TABULATED) {
-            size_t size = (size_t) p.tab_count;
-            if (size < 2 || !p.tab_values) throw std::runtime_error("ContinuousDistribution: needs at least two entries!");
-            std::vector<float> &pdf = hs.tab_pdf.back(), &cdf = hs.tab_cdf.back();
-            pdf.assign(p.tab_values, p.tab_values + size); cdf.resize(size - 1);
-            dp.size = (int32_t) size; dp.range_x = -1.f; dp.range_y = 1.f;
-            dp.valid_x = dp.valid_y = (uint32_t) -1;
-            double range = double(dp.range_y) - double(dp.range_x), interval_size = range / (size - 1), integral = 0.;
-            for (size_t k = 0; k < size - 1; ++k) {
-                double y0 = (double) pdf[k], y1 = (double) pdf[k + 1];
-                double value = 0.5 * interval_size * (y0 + y1);
-                integral += value;
-                cdf[k] = (float) integral;
-                if (y0 < 0. || y1 < 0.) throw std::runtime_error("ContinuousDistribution: entries must be non-negative!");
-                else if (value > 0.) { if (dp.valid_x == (uint32_t) -1) dp.valid_x = (uint32_t) k; dp.valid_y = (uint32_t) k; }
-            }
-            if (dp.valid_x == (uint32_t) -1) throw std::runtime_error("ContinuousDistribution: no probability mass found!");
-            dp.integral = (float) integral; dp.normalization = (float) (1. / integral);
-            dp.interval_size = (float) interval_size; dp.inv_interval_size = (float) (1. / interval_size);
-        } else if (p.type < MTS_PHASE_ISOTROPIC || p.type > MTS_PHASE_TABULATED) throw std::runtime_error("unknown phase function type");
+        const DPhase dp = build_phase(d->phases[i], i, hs.phases, d->phase_count, d->volume_count, hs.tab_pdf.back(), hs.tab_cdf.back());
         hs.phases.push_back(dp);
     }
     // ---- media (medium.cpp:12-29, homogeneous.cpp:21-28, heterogeneous.cpp:21-31)
     for (int i = 0; i < d->medium_count; ++i) {
         const mts_medium &m = d->media[i];
-        check_index(m.sigma_t_volume, d->volume_count, "medium sigma_t", false);
-        check_index(m.albedo_volume, d->volume_count, "medium albedo", false);
-        check_index(m.phase, d->phase_count, "medium phase", false);
-        DMedium dm; memset(&dm, 0, sizeof(dm));
-        dm.type = m.type; dm.sigma_t = m.sigma_t_volume; dm.albedo = m.albedo_volume; dm.phase = m.phase; dm.scale = m.scale;
-        dm.sample_emitters = m.sample_emitters != 0; dm.has_spectral_extinction = m.has_spectral_extinction != 0;
-        dm.is_homogeneous = m.type == MTS_MEDIUM_HOMOGENEOUS;
-        if (m.type == MTS_MEDIUM_HETEROGENEOUS) {
-            const DVolume &st = hs.volumes[m.sigma_t_volume];
-            if (!st.has_max) throw std::runtime_error("max() not implemented (constvolume sigma_t in heterogeneous medium)");
-            dm.max_density = dm.scale * st.max;
-            // the kernels divide by the majorant two or three times per tracking step: with its correctly rounded reciprocal at hand an
-            // IEEE-exact quotient is five multiply-adds instead of the ~11-instruction division sequence (pm_div_by_invariant, pmath.h;
-            // the predicate that admits the majorant is pm_invariant_rcp, shared with the tests).
-            dm.inv_max_density = pm_invariant_rcp(dm.max_density);
-            dm.aabb = st.bbox;
-        } else if (m.type != MTS_MEDIUM_HOMOGENEOUS) throw std::runtime_error("unknown medium type");
-        {   // kernel fast paths that do not change a single bit of the result
-            const DVolume &a = hs.volumes[m.sigma_t_volume], &b = hs.volumes[m.albedo_volume];
-            dm.shared_grid = (a.type == MTS_VOLUME_GRID && b.type == MTS_VOLUME_GRID && a.nx == b.nx && a.ny == b.ny && a.nz == b.nz &&
-                              a.filter == b.filter && a.wrap == b.wrap && memcmp(a.w2l, b.w2l, 64) == 0) ? 1 : 0;
-            auto grey = [](const DVolume &v) { return v.type == MTS_VOLUME_GRID ? v.channels == 1 : (v.value[0] == v.value[1] && v.value[1] == v.value[2]); };
-            dm.grey = (grey(a) && grey(b) && !spectral) ? 1 : 0;       // spectral variant: values depend on the wavelength
-            if (spectral && dm.shared_grid) {                          // two gridvolume_spectral grids over one spectral interval: 2
-                const DVolumeSp &sa = hs.volume_sp[m.sigma_t_volume], &sb = hs.volume_sp[m.albedo_volume];
-                if (sa.spectral_grid && sb.spectral_grid && a.channels == b.channels && sa.lambda_min == sb.lambda_min && sa.lambda_max == sb.lambda_max)
-                    dm.shared_grid = 2;
-            }
-            std::vector<float> pair;
-            if (dm.shared_grid && a.channels == 1 && b.channels == 1 && a.filter == MTS_FILTER_TRILINEAR && a.wrap == MTS_WRAP_CLAMP) {
-                const std::vector<float> &ga = hs.grid_data[m.sigma_t_volume], &gb = hs.grid_data[m.albedo_volume];
-                // rows of at least two voxels (one 16-byte gather = both x-neighbours of both grids): a one-column grid -- the
-                // nz x 1 x 1 grids of 1-D atmospheres -- is stored with its column twice; both x-neighbours clamp to voxel 0 anyway
-                const size_t sx = a.nx < 2 ? 2 : (size_t) a.nx, rows = (size_t) a.ny * a.nz;
-                pair.assign(2 * (sx * rows + 1), 0.f);
-                for (size_t r = 0; r < rows; ++r)
-                    for (size_t x = 0; x < sx; ++x) {
-                        const size_t src = r * (size_t) a.nx + (x < (size_t) a.nx ? x : (size_t) a.nx - 1);
-                        pair[2 * (r * sx + x)] = ga[src]; pair[2 * (r * sx + x) + 1] = gb[src];
-                    }
-                memcpy(dm.pair_w2l, a.w2l, 64); dm.pair_nx = a.nx; dm.pair_ny = a.ny; dm.pair_nz = a.nz; dm.pair_affine = (a.affine ? 1 : 0) | ((a.columns_equal && b.columns_equal) ? 2 : 0);
-            }
-            hs.pair_data.push_back(std::move(pair));
-        }
+        DMedium dm;
+        std::vector<float> pair;
+        if (build_medium(m, hs, d->volume_count, d->phase_count, spectral, dm))
+            build_pair_grid(hs.volumes[(size_t) m.sigma_t_volume], hs.grid_data[(size_t) m.sigma_t_volume], hs.grid_data[(size_t) m.albedo_volume], pair);
+        hs.pair_data.push_back(std::move(pair));
         hs.media.push_back(dm);
     }
     // ---- BSDFs
     for (int i = 0; i < d->bsdf_count; ++i) {
         const mts_bsdf &b = d->bsdfs[i];
-        if (b.type < MTS_BSDF_DIFFUSE || b.type > MTS_BSDF_BILAMBERTIAN) throw std::runtime_error("unknown BSDF type");
-        DBsdf db; memset(&db, 0, sizeof(db));
-        db.type = b.type; memcpy(db.reflectance, b.reflectance, 12); memcpy(db.rho_0, b.rho_0, 12); memcpy(db.k, b.k, 12);
-        memcpy(db.g, b.g, 12); memcpy(db.rho_c, b.rho_c, 12); memcpy(db.transmittance, b.transmittance, 12); db.flags = bsdf_flags(b.type);
+        const DBsdf db = build_bsdf(b);
         hs.bsdfs.push_back(db);
         if (spectral) {                                                  // which of the six colour parameters each plugin reads
-            static const bool used[4][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */ };
-            for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(used[b.type][k] ? spectrum_index(b.spectrum[k], "a BSDF parameter") : 0);
+            for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(BSDF_SP_USED[b.type][k] ? spectrum_index(b.spectrum[k], "a BSDF parameter") : 0);
         }
     }
     // default BSDFs appended after the user's (shape.cpp:74-80): diffuse 0.5, and diffuse 0 for emitters
@@ -519,8 +591,8 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     float bsphere_radius = pm_max(MTS_RAY_EPSILON, norm(center - f3(sc.bbox.max)) * (1.f + MTS_RAY_EPSILON));
     for (int i = 0; i < d->emitter_count; ++i) {
         const mts_emitter &e = d->emitters[i];
-        DEmitter de; memset(&de, 0, sizeof(de));
-        de.type = e.type; de.to_world = xf_from_abi(e.to_world); memcpy(de.radiance, e.radiance, 12); de.shape = e.shape;
+        const float c3[3] = { center.x, center.y, center.z };
+        const DEmitter de = build_emitter(e, c3, bsphere_radius);
         if (e.type == MTS_EMITTER_AREA) {
             check_index(e.shape, d->shape_count, "area emitter shape", false);
             if ((hs.shapes[e.shape].type == MTS_SHAPE_CUBE || hs.shapes[e.shape].type == MTS_SHAPE_MESH) && hs.shapes[e.shape].area_lo < 0)
@@ -529,7 +601,6 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
             if (sc.environment >= 0) throw std::runtime_error("Only one environment emitter can be specified per scene.");
             sc.environment = i;
         } else if (e.type != MTS_EMITTER_DIRECTIONAL && e.type != MTS_EMITTER_POINT) throw std::runtime_error("unknown emitter type");
-        store3(de.bsphere_center, center); de.bsphere_radius = bsphere_radius;
         hs.emitters.push_back(de);
         if (spectral) hs.emitter_sp.push_back(spectrum_index(e.radiance_spectrum, "an emitter"));
     }
@@ -645,10 +716,7 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
         const int t = hs.spectra[(size_t) d->sensor.srf - 1].type;
         if (t != MTS_SPECTRUM_UNIFORM && t != MTS_SPECTRUM_DISCRETE) throw std::runtime_error("srf: sample_spectrum is available for uniform and discrete spectra");
         sc.srf = d->sensor.srf - 1;
-        if (t == MTS_SPECTRUM_DISCRETE) {                                                      // srf_weights_of (integrator_dev.h) looks a weight up by its wavelength
-            const std::vector<float> &w = hs.spectrum_wavelengths[(size_t) sc.srf];
-            for (size_t k = 1; k < w.size(); ++k) if (!(w[k] > w[k - 1])) hs.srf_lookup_by_wavelength = false;
-        }
+        hs.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs);
     }
     sc.volume_count = (int) hs.volumes.size(); sc.phase_count = (int) hs.phases.size(); sc.medium_count = (int) hs.media.size();
     sc.bsdf_count = (int) hs.bsdfs.size(); sc.shape_count = (int) hs.shapes.size(); sc.prim_count = (int) hs.prims.size();
@@ -822,6 +890,320 @@ void free_host_scene(HostScene *hs) {
     if (!hs) return;
     if (hs->uploaded) { (void) hipSetDevice(hs->device); for (void *p : hs->device_allocs) (void) hipFree(p); }
     delete hs;
+}
+
+// ---------------------------------------------------------------- update (mts_scene_update)
+namespace {
+[[noreturn]] void refuse(const char *object, int index, const std::string &what) {
+    throw std::runtime_error("mts_scene_update: " + std::string(object) + " " + std::to_string(index) + ": " + what);
+}
+[[noreturn]] void frozen(const char *object, int index, const char *field) {
+    refuse(object, index, std::string("'") + field + "' differs from what the scene was created with (the topology of a scene is frozen)");
+}
+struct StagedSpectrum { DSpectrum rec; SpectrumArrays arrays; };
+struct StagedPhase { DPhase rec; std::vector<float> pdf, cdf; };
+// a medium's description as it was given, read back from its record (media that follow a dirty volume without being dirty themselves)
+mts_medium medium_desc_of(const DMedium &m) {
+    mts_medium d; memset(&d, 0, sizeof(d));
+    d.type = m.type; d.sigma_t_volume = m.sigma_t; d.albedo_volume = m.albedo; d.scale = m.scale; d.phase = m.phase;
+    d.sample_emitters = m.sample_emitters; d.has_spectral_extinction = m.has_spectral_extinction;
+    return d;
+}
+#if !defined(MTSAMD_HOST_ONLY)
+template <typename T> void reupload(const T *device, const std::vector<T> &v, hipStream_t stream) {
+    if (!v.empty()) HIP_CHECK(hipMemcpyAsync((void *) device, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+}
+#endif
+} // namespace
+
+void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *dirty, int32_t n, hipStream_t stream) {
+    if (!d) throw std::runtime_error("mts_scene_update: scene description is NULL");
+    if (d->abi_version != MTS_ABI_VERSION) throw std::runtime_error("mts_scene_update: scene description: ABI version mismatch");
+    if (n < 0) throw std::runtime_error("mts_scene_update: n is negative");
+    if (n > 0 && !dirty) throw std::runtime_error("mts_scene_update: dirty is NULL");
+    const bool spectral = hs.integrator.spectral != 0;
+    // the description's own counts (build_host_scene appends two default BSDFs and, in the spectral variant, their two spectra)
+    const int32_t n_volumes = (int32_t) hs.volumes.size(), n_phases = (int32_t) hs.phases.size(), n_media = (int32_t) hs.media.size(),
+                  n_bsdfs = (int32_t) hs.bsdfs.size() - 2, n_emitters = (int32_t) hs.emitters.size(), n_spectra = spectral ? (int32_t) hs.spectra.size() - 2 : 0;
+    if ((d->integrator.spectral != 0) != spectral || (d->integrator.monochrome != 0) != (hs.scene.integrator.monochrome != 0))
+        throw std::runtime_error("mts_scene_update: the description is of another variant than the scene");
+    if (d->volume_count != n_volumes || d->phase_count != n_phases || d->medium_count != n_media || d->bsdf_count != n_bsdfs ||
+        d->emitter_count != n_emitters || (spectral && d->spectrum_count != n_spectra))
+        throw std::runtime_error("mts_scene_update: the description's record counts differ from what the scene was created with");
+
+    // ---- 1. validate and stage: nothing of the scene is written before every dirty record has passed
+    std::map<int, StagedSpectrum> spectra; std::map<int, StagedPhase> phases; std::map<int, DBsdf> bsdfs; std::map<int, DEmitter> emitters;
+    std::map<int, const float *> volumes;                  // dirty volume -> mts_dirty::device_data
+    std::set<int> media;
+    for (int32_t k = 0; k < n; ++k) {
+        const int i = dirty[k].index;
+        static const char *NAMES[] = { "spectrum", "volume", "phase", "medium", "bsdf", "emitter" };
+        const int32_t counts[] = { n_spectra, n_volumes, n_phases, n_media, n_bsdfs, n_emitters };
+        if (dirty[k].object < MTS_OBJ_SPECTRUM || dirty[k].object > MTS_OBJ_EMITTER) throw std::runtime_error("mts_scene_update: dirty[" + std::to_string(k) + "]: unknown object kind");
+        const char *name = NAMES[dirty[k].object];
+        if (i < 0 || i >= counts[dirty[k].object]) refuse(name, i, "index out of range");
+        if (dirty[k].device_data && !(dirty[k].object == MTS_OBJ_VOLUME && hs.volumes[(size_t) i].type == MTS_VOLUME_GRID))
+            refuse(name, i, "device_data is for grid volumes only");
+        switch (dirty[k].object) {
+        case MTS_OBJ_SPECTRUM: {
+            const mts_spectrum &sp = d->spectra[i]; const DSpectrum &old = hs.spectra[(size_t) i];
+            if (sp.type != old.type) frozen(name, i, "type");
+            if (sp.type != MTS_SPECTRUM_UNIFORM && sp.count != old.count) frozen(name, i, "count");
+            StagedSpectrum &st = spectra[i]; st.arrays = SpectrumArrays();
+            st.rec = build_spectrum(sp, st.arrays);
+            break; }
+        case MTS_OBJ_VOLUME: {
+            const mts_volume &v = d->volumes[i]; const DVolume &old = hs.volumes[(size_t) i]; const DVolumeSp &osp = hs.volume_sp[(size_t) i];
+            if (dirty[k].device_data && !hs.uploaded) refuse(name, i, "device_data needs a scene in device memory");
+            if ((v.type == MTS_VOLUME_GRID_SPECTRAL ? MTS_VOLUME_GRID : v.type) != old.type || (v.type == MTS_VOLUME_GRID_SPECTRAL) != (osp.spectral_grid != 0)) frozen(name, i, "type");
+            if (volume_is_grid(v)) {
+                if (v.nx != old.nx) frozen(name, i, "nx");
+                if (v.ny != old.ny) frozen(name, i, "ny");
+                if (v.nz != old.nz) frozen(name, i, "nz");
+                if (v.channels != old.channels) frozen(name, i, "channels");
+                if (v.filter_type != old.filter) frozen(name, i, "filter_type");
+                if (v.wrap_mode != old.wrap) frozen(name, i, "wrap_mode");
+            }
+            const GridStats none = { 0.f, 0 };
+            DVolume dv; DVolumeSp vsp;
+            build_volume(v, spectral, n_spectra, dirty[k].device_data == nullptr, &none, dv, vsp);
+            if (memcmp(dv.w2l, old.w2l, 64) != 0) frozen(name, i, "to_world");
+            if (vsp.value_sp != osp.value_sp) frozen(name, i, "value_spectrum");
+            if (vsp.lambda_min != osp.lambda_min) frozen(name, i, "lambda_min");
+            if (vsp.lambda_max != osp.lambda_max) frozen(name, i, "lambda_max");
+            volumes[i] = dirty[k].device_data;
+            break; }
+        case MTS_OBJ_PHASE: {
+            const mts_phase &p = d->phases[i]; const DPhase &old = hs.phases[(size_t) i];
+            if (p.type != old.type) frozen(name, i, "type");
+            if (p.type == MTS_PHASE_BLEND && (p.child[0] != old.child[0] || p.child[1] != old.child[1])) frozen(name, i, "child");
+            if (p.type == MTS_PHASE_BLEND && p.weight_volume != old.weight_volume) frozen(name, i, "weight_volume");
+            if (p.type == MTS_PHASE_TABULATED && p.tab_count != old.size) frozen(name, i, "tab_count");
+            StagedPhase &st = phases[i]; st.pdf.clear(); st.cdf.clear();
+            try { st.rec = build_phase(p, i, hs.phases, n_phases, n_volumes, st.pdf, st.cdf); }
+            catch (const std::runtime_error &e) { refuse(name, i, std::string(p.type == MTS_PHASE_HG ? "'g': " : p.type == MTS_PHASE_TABULATED ? "'tab_values': " : "") + e.what()); }
+            break; }
+        case MTS_OBJ_MEDIUM: {
+            const mts_medium &m = d->media[i]; const DMedium &old = hs.media[(size_t) i];
+            if (m.type != old.type) frozen(name, i, "type");
+            if (m.sigma_t_volume != old.sigma_t) frozen(name, i, "sigma_t_volume");
+            if (m.albedo_volume != old.albedo) frozen(name, i, "albedo_volume");
+            if (m.phase != old.phase) frozen(name, i, "phase");
+            media.insert(i);
+            break; }
+        case MTS_OBJ_BSDF: {
+            const mts_bsdf &b = d->bsdfs[i];
+            if (b.type != hs.bsdfs[(size_t) i].type) frozen(name, i, "type");
+            if (spectral)
+                for (int s = 0; s < MTS_BSDF_SP_COUNT; ++s)
+                    if (BSDF_SP_USED[b.type][s] && b.spectrum[s] != hs.bsdf_sp[(size_t) i * MTS_BSDF_SP_COUNT + s]) frozen(name, i, "spectrum");
+            bsdfs[i] = build_bsdf(b);
+            break; }
+        default: {
+            const mts_emitter &e = d->emitters[i]; const DEmitter &old = hs.emitters[(size_t) i];
+            if (e.type != old.type) frozen(name, i, "type");
+            if (e.shape != old.shape) frozen(name, i, "shape");
+            if (spectral && e.radiance_spectrum != hs.emitter_sp[(size_t) i]) frozen(name, i, "radiance_spectrum");
+            const DXf xf = xf_from_abi(e.to_world);          // an emitter's placement is geometry: frozen like a volume's transform
+            if (memcmp(&xf, &old.to_world, sizeof(xf)) != 0) frozen(name, i, "to_world");
+            emitters[i] = build_emitter(e, old.bsphere_center, old.bsphere_radius);
+            break; }
+        }
+    }
+    for (int i = 0; i < n_media; ++i)                      // media follow the volumes they read
+        if (volumes.count(hs.media[(size_t) i].sigma_t) || volumes.count(hs.media[(size_t) i].albedo)) media.insert(i);
+
+    // ---- 2. the new grids and what the constructors derive from their data
+    std::map<int, GridStats> stats;
+#if !defined(MTSAMD_HOST_ONLY)
+    if (hs.uploaded) {
+        HIP_CHECK(hipSetDevice(hs.device));
+        int cus = 0;
+        HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, hs.device));
+        std::vector<int> grids;
+        for (const auto &kv : volumes) if (hs.volumes[(size_t) kv.first].type == MTS_VOLUME_GRID) grids.push_back(kv.first);
+        std::vector<uint32_t> words(2 * grids.size());
+        if (!grids.empty()) {
+            if (!hs.update_stats) {                        // first use: two words per volume of the scene
+                void *p = nullptr;
+                HIP_CHECK(hipMalloc(&p, std::max<size_t>(2 * sizeof(uint32_t) * hs.volumes.size(), 16)));
+                hs.device_allocs.push_back(p); hs.update_stats = (uint32_t *) p;
+            }
+            for (size_t g = 0; g < grids.size(); ++g) { words[2 * g] = 0u; words[2 * g + 1] = 1u; }
+            HIP_CHECK(hipMemcpyAsync(hs.update_stats, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            for (int v : grids) {                          // the scene owns its copy of the data: into the grid's own allocation first
+                const float *src = volumes[v] ? volumes[v] : d->volumes[v].data;
+                if (src != hs.volumes[(size_t) v].data)
+                    HIP_CHECK(hipMemcpyAsync((void *) hs.volumes[(size_t) v].data, src, hs.grid_data[(size_t) v].size() * sizeof(float), volumes[v] ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+            }
+            // one pass per dirty grid: its statistics, fused with the pair grid of a medium that interleaves it (a medium with both grids
+            // dirty is written by its sigma_t's pass; further media sharing the grid get a pass without statistics)
+            for (size_t g = 0; g < grids.size(); ++g) {
+                const DVolume &dv = hs.volumes[(size_t) grids[g]];
+                GridUpdateJob job; memset(&job, 0, sizeof(job));
+                job.grid = dv.data; job.count = (uint32_t) hs.grid_data[(size_t) grids[g]].size(); job.channels = (uint32_t) dv.channels;
+                job.plane = (uint32_t) dv.ny * (uint32_t) dv.nx * (uint32_t) dv.channels; job.nx = (uint32_t) dv.nx;
+                job.stats = hs.update_stats + 2 * g;
+                bool launched = false;
+                for (int m : media) {
+                    const DMedium &dm = hs.media[(size_t) m];
+                    if (hs.pair_data[(size_t) m].empty() || (dm.sigma_t != grids[g] && dm.albedo != grids[g])) continue;
+                    if (dm.albedo == grids[g] && dm.sigma_t != grids[g] && volumes.count(dm.sigma_t)) continue;      // its sigma_t's pass writes it
+                    job.pair = (float *) dm.pair_grid; job.slot = dm.sigma_t == grids[g] ? 0u : 1u;
+                    job.partner = hs.volumes[(size_t) (job.slot == 0 ? dm.albedo : dm.sigma_t)].data;
+                    HIP_CHECK(launch_grid_update(job, cus, stream));
+                    job.stats = nullptr; launched = true;
+                }
+                if (!launched) HIP_CHECK(launch_grid_update(job, cus, stream));
+            }
+            HIP_CHECK(hipMemcpyAsync(words.data(), hs.update_stats, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
+        for (size_t g = 0; g < grids.size(); ++g) stats[grids[g]] = GridStats{ grid_key_to_float(words[2 * g]), words[2 * g + 1] != 0u ? 1 : 0 };
+    } else
+#endif
+    for (const auto &kv : volumes) {
+        const mts_volume &v = d->volumes[kv.first];
+        if (!volume_is_grid(v)) continue;
+        stats[kv.first] = grid_stats(v.data, v.nx, v.ny, v.nz, v.channels);
+        hs.grid_data[(size_t) kv.first].assign(v.data, v.data + hs.grid_data[(size_t) kv.first].size());
+    }
+
+    // ---- 3. the records, through the constructors' own functions; device pointers stay
+    for (const auto &kv : volumes) {
+        const size_t i = (size_t) kv.first;
+        DVolume dv; DVolumeSp vsp;
+        build_volume(d->volumes[i], spectral, n_spectra, false, stats.count(kv.first) ? &stats[kv.first] : nullptr, dv, vsp);
+        dv.data = hs.volumes[i].data;
+        hs.volumes[i] = dv; hs.volume_sp[i] = vsp;
+    }
+    for (auto &kv : phases) {
+        const size_t i = (size_t) kv.first;
+        kv.second.rec.pdf = hs.phases[i].pdf; kv.second.rec.cdf = hs.phases[i].cdf;
+        hs.phases[i] = kv.second.rec; hs.tab_pdf[i].swap(kv.second.pdf); hs.tab_cdf[i].swap(kv.second.cdf);
+    }
+    for (int i : media) {
+        const bool listed = std::any_of(dirty, dirty + n, [i](const mts_dirty &q) { return q.object == MTS_OBJ_MEDIUM && q.index == i; });
+        const mts_medium m = listed ? d->media[i] : medium_desc_of(hs.media[(size_t) i]);
+        DMedium dm;
+        const bool pair = build_medium(m, hs, n_volumes, n_phases, spectral, dm);
+        dm.pair_grid = hs.media[(size_t) i].pair_grid;
+        hs.media[(size_t) i] = dm;
+        if (pair && !hs.uploaded) build_pair_grid(hs.volumes[(size_t) dm.sigma_t], hs.grid_data[(size_t) dm.sigma_t], hs.grid_data[(size_t) dm.albedo], hs.pair_data[(size_t) i]);
+    }
+    for (const auto &kv : bsdfs) hs.bsdfs[(size_t) kv.first] = kv.second;
+    for (const auto &kv : emitters) hs.emitters[(size_t) kv.first] = kv.second;
+    for (auto &kv : spectra) {
+        const size_t i = (size_t) kv.first;
+        DSpectrum &ds = kv.second.rec;
+        ds.values = hs.spectra[i].values; ds.wavelengths = hs.spectra[i].wavelengths; ds.cdf = hs.spectra[i].cdf;
+        hs.spectra[i] = ds;
+        hs.spectrum_values[i].swap(kv.second.arrays.values); hs.spectrum_wavelengths[i].swap(kv.second.arrays.wavelengths); hs.spectrum_cdf[i].swap(kv.second.arrays.cdf);
+    }
+    hs.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs);
+    hs.traits = scene_traits(hs, spectral);                // the next render picks the kernel a fresh scene would
+
+    // ---- 4. the device's copies of what changed
+#if !defined(MTSAMD_HOST_ONLY)
+    if (hs.uploaded) {
+        const DScene &sc = hs.scene;
+        if (!volumes.empty()) { reupload(sc.volumes, hs.volumes, stream); if (spectral) reupload(sc.volume_sp, hs.volume_sp, stream); }
+        if (!media.empty()) reupload(sc.media, hs.media, stream);
+        if (!bsdfs.empty()) reupload(sc.bsdfs, hs.bsdfs, stream);
+        if (!emitters.empty()) reupload(sc.emitters, hs.emitters, stream);
+        for (const auto &kv : phases) {
+            const size_t i = (size_t) kv.first;
+            if (hs.phases[i].type == MTS_PHASE_TABULATED) { reupload(hs.phases[i].pdf, hs.tab_pdf[i], stream); reupload(hs.phases[i].cdf, hs.tab_cdf[i], stream); }
+        }
+        if (!phases.empty()) reupload(sc.phases, hs.phases, stream);
+        for (const auto &kv : spectra) {
+            const size_t i = (size_t) kv.first;
+            if (hs.spectra[i].type == MTS_SPECTRUM_UNIFORM) continue;
+            reupload(hs.spectra[i].values, hs.spectrum_values[i], stream);
+            if (hs.spectra[i].wavelengths) reupload(hs.spectra[i].wavelengths, hs.spectrum_wavelengths[i], stream);
+            if (hs.spectra[i].cdf) reupload(hs.spectra[i].cdf, hs.spectrum_cdf[i], stream);
+        }
+        if (!spectra.empty()) reupload(sc.spectra, hs.spectra, stream);
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+#else
+    (void) stream;
+#endif
+}
+
+// ---------------------------------------------------------------- digest (tests: "the device scene is the fresh one")
+namespace {
+struct Fnv {
+    uint64_t h = 1469598103934665603ull;
+    void add(const void *p, size_t bytes) { const unsigned char *c = (const unsigned char *) p; for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; } }
+};
+#if !defined(MTSAMD_HOST_ONLY)
+template <typename T> std::vector<T> download(const T *device, size_t count) {
+    std::vector<T> v(count);
+    if (count && device) HIP_CHECK(hipMemcpy(v.data(), device, count * sizeof(T), hipMemcpyDeviceToHost));
+    return v;
+}
+#endif
+} // namespace
+
+void digest_host_scene(HostScene &hs, uint64_t out[8]) {
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+#if defined(MTSAMD_HOST_ONLY)
+    throw std::runtime_error("mts_debug_scene_digest: host-only build (no device scene)");
+#else
+    if (!hs.uploaded) throw std::runtime_error("mts_debug_scene_digest: the scene is not in device memory");
+    HIP_CHECK(hipSetDevice(hs.device));
+    HIP_CHECK(hipDeviceSynchronize());
+    const DScene &sc = hs.scene;
+    Fnv rec, grid, pair, tab, spec, head;
+    std::vector<DVolume> volumes = download(sc.volumes, hs.volumes.size());
+    std::vector<DPhase> phases = download(sc.phases, hs.phases.size());
+    std::vector<DMedium> media = download(sc.media, hs.media.size());
+    std::vector<DBsdf> bsdfs = download(sc.bsdfs, hs.bsdfs.size());
+    std::vector<DEmitter> emitters = download(sc.emitters, hs.emitters.size());
+    std::vector<DShape> shapes = download(sc.shapes, hs.shapes.size());
+    for (size_t i = 0; i < volumes.size(); ++i) {
+        if (volumes[i].data != hs.volumes[i].data) throw std::runtime_error("mts_debug_scene_digest: a volume record points elsewhere than the host's copy");
+        grid.add(download(volumes[i].data, hs.grid_data[i].size()).data(), hs.grid_data[i].size() * sizeof(float));
+        volumes[i].data = nullptr;
+    }
+    for (size_t i = 0; i < phases.size(); ++i) {
+        if (phases[i].type == MTS_PHASE_TABULATED) {
+            tab.add(download(phases[i].pdf, hs.tab_pdf[i].size()).data(), hs.tab_pdf[i].size() * sizeof(float));
+            tab.add(download(phases[i].cdf, hs.tab_cdf[i].size()).data(), hs.tab_cdf[i].size() * sizeof(float));
+        }
+        phases[i].pdf = phases[i].cdf = nullptr;
+    }
+    for (size_t i = 0; i < media.size(); ++i) {
+        if (media[i].pair_grid) pair.add(download(media[i].pair_grid, hs.pair_data[i].size()).data(), hs.pair_data[i].size() * sizeof(float));
+        media[i].pair_grid = nullptr;
+    }
+    rec.add(volumes.data(), volumes.size() * sizeof(DVolume)); rec.add(phases.data(), phases.size() * sizeof(DPhase));
+    rec.add(media.data(), media.size() * sizeof(DMedium)); rec.add(bsdfs.data(), bsdfs.size() * sizeof(DBsdf));
+    rec.add(emitters.data(), emitters.size() * sizeof(DEmitter)); rec.add(shapes.data(), shapes.size() * sizeof(DShape));
+    if (hs.integrator.spectral) {
+        std::vector<DSpectrum> spectra = download(sc.spectra, hs.spectra.size());
+        for (size_t i = 0; i < spectra.size(); ++i) {
+            spec.add(download(spectra[i].values, hs.spectrum_values[i].size()).data(), hs.spectrum_values[i].size() * sizeof(float));
+            spec.add(download(spectra[i].wavelengths, hs.spectrum_wavelengths[i].size()).data(), hs.spectrum_wavelengths[i].size() * sizeof(float));
+            spec.add(download(spectra[i].cdf, hs.spectrum_cdf[i].size()).data(), hs.spectrum_cdf[i].size() * sizeof(float));
+            spectra[i].values = spectra[i].wavelengths = spectra[i].cdf = nullptr;
+        }
+        spec.add(spectra.data(), spectra.size() * sizeof(DSpectrum));
+        spec.add(download(sc.bsdf_sp, hs.bsdf_sp.size()).data(), hs.bsdf_sp.size() * sizeof(int32_t));
+        spec.add(download(sc.emitter_sp, hs.emitter_sp.size()).data(), hs.emitter_sp.size() * sizeof(int32_t));
+        spec.add(download(sc.volume_sp, hs.volume_sp.size()).data(), hs.volume_sp.size() * sizeof(DVolumeSp));
+    }
+    DScene h = sc;                                         // the kernel argument: its scalars, every pointer zeroed
+    h.volumes = nullptr; h.phases = nullptr; h.media = nullptr; h.bsdfs = nullptr; h.shapes = nullptr; h.prims = nullptr; h.walk = nullptr; h.emitters = nullptr;
+    h.positions = h.normals = h.texcoords = nullptr; h.faces = nullptr; h.tri = h.tri_attr = h.area_pmf = h.area_cdf = nullptr;
+    h.bvh_nodes = nullptr; h.bvh_prims = nullptr; h.bvh_lds = nullptr; h.sensor.rfilter.values = nullptr; h.sensor.multi = nullptr;
+    h.spectra = nullptr; h.bsdf_sp = nullptr; h.emitter_sp = nullptr; h.volume_sp = nullptr; h.cie = nullptr; h.bin_lo = h.bin_hi = nullptr;
+    head.add(&h, sizeof(h));
+    const int32_t tail[2] = { hs.traits, hs.srf_lookup_by_wavelength ? 1 : 0 };
+    head.add(tail, sizeof(tail));
+    out[0] = rec.h; out[1] = grid.h; out[2] = pair.h; out[3] = tab.h; out[4] = spec.h; out[5] = head.h;
+#endif
 }
 
 } // namespace mtsamd

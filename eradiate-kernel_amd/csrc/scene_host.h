@@ -40,6 +40,9 @@ struct HostScene {
     bool srf_lookup_by_wavelength = true;            // the response function's weights can be recovered from the sampled wavelengths (regrouping kernel)
     std::vector<int32_t> bsdf_sp, emitter_sp; std::vector<DVolumeSp> volume_sp;
     std::vector<void *> device_allocs;
+    // mts_scene_update: two words per volume the grid pass reduces into (launch.h: GridUpdateJob::stats), allocated by the first update
+    // that rewrites a grid.  After an update of an uploaded scene, grid_data / pair_data above keep their sizes, not the device's contents.
+    uint32_t *update_stats = nullptr;
     int traits = 0;                                  // promises of integrator_dev.h's scene traits this scene keeps (MT_* bits; scene_traits())
     int device = 0;
     bool uploaded = false;
@@ -50,5 +53,12 @@ HostScene *build_host_scene(const mts_scene_desc *desc);   // throws std::runtim
 void build_bvh(HostScene &hs);                 // fills bvh_nodes / bvh_prims when the scene has many primitives
 void upload_host_scene(HostScene &hs, int device);          // throws std::runtime_error
 void free_host_scene(HostScene *hs);
+// mts_scene_update: re-runs build_host_scene's per-record work for the dirty records of `desc` and the records derived from them, and
+// scene_traits.  Validates everything before it writes (throws std::runtime_error with the scene untouched).  An uploaded scene is
+// rewritten in place on `stream` (grid statistics and pair grids by grid_update_kernel); a host-only scene through the host functions.
+void update_host_scene(HostScene &hs, const mts_scene_desc *desc, const mts_dirty *dirty, int32_t n, hipStream_t stream);
+// FNV-1a over the device scene's contents, pointer fields zeroed: [0] record arrays, [1] grid data, [2] pair grids, [3] phase tables,
+// [4] spectra, [5] traits and the scalar header of DScene, [6..7] 0
+void digest_host_scene(HostScene &hs, uint64_t out[8]);
 
 } // namespace mtsamd

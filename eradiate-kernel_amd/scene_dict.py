@@ -202,6 +202,7 @@ def _spectrum(v, where, default=None, emitter=False):
         rec.type = A.SPECTRUM_UNIFORM
         rec.value = float(c[0])
     b.spectra.append(rec)
+    b.spectrum_plugins.append(v.get("type") if isinstance(v, dict) else "uniform")      # traverse(): the keys of that plugin
     return len(b.spectra) - 1
 
 
@@ -373,6 +374,33 @@ def parse_fov(p, aspect):
     return float(np.float32(result))
 
 
+def _grid_data(data):
+    """A grid's values as the description holds them: float32, C order, (nz, ny, nx, channels).  Returns (array, mono_max): under the
+    *_mono variants a colour grid becomes its luminance per voxel and keeps the file's maximum as its majorant (grid3d.cpp:157-179)."""
+    data = np.asarray(data, dtype=np.float32)
+    if data.ndim == 3:
+        data = data[..., None]
+    data = np.ascontiguousarray(data, dtype=np.float32)
+    if data.ndim != 4:
+        raise RuntimeError("gridvolume: data must have shape (nz, ny, nx, channels)")
+    mono_max = None
+    if _MONO and data.shape[3] == 3:
+        # grid3d.cpp:178-179: *_mono variants return the luminance of the interpolated colour. Luminance is
+        # linear, so it is applied per voxel here; the majorant stays the file's maximum (volume metadata).
+        mono_max = float(data.max()) if data.size else 0.0
+        f = np.float32
+        data = np.ascontiguousarray(((data[..., 0] * f(0.212671) + data[..., 1] * f(0.715160))
+                                     + data[..., 2] * f(0.072169))[..., None], dtype=np.float32)
+    return data, mono_max
+
+
+def _tab_values(vals):
+    """tabphase "values": a string of numbers (tabphase.cpp:33-40) -> float32 array."""
+    if not isinstance(vals, str):
+        raise RuntimeError("'values' must be a string")
+    return np.array([float(s) for s in vals.replace(",", " ").split()], dtype=np.float32)
+
+
 SHAPE_PLUGINS = ("rectangle", "cube", "sphere", "mesh", "obj", "ply", "disk")
 
 
@@ -387,6 +415,18 @@ class SceneBuilder:
         self.keep = []
         self.instances = {}      # id -> (kind, index)
         self.info = {}
+        self.spectra, self.spectrum_plugins = [], []
+        self.mono = self.spectral = False
+        # traverse() (params.py): what each record exposes, written down while it is built.  nodes[(kind, index)] lists, in the order of
+        # the reference plugin's traverse(), ("param", name, what, field) and ("object", name, node) entries; a colour is a node of its
+        # own (`srgb` / `uniform` texture): ("colour", kind, index, field, where, emitter) in rgb / mono, ("spectrum", index) in spectral
+        self.nodes = {}
+        self.children = []       # the scene's own children: (key, node)
+        self.grids, self.grid_mono_max, self.tabs = {}, {}, {}
+        self.spectrum_arrays = {}    # (spectrum, field) -> the array an update put there (one live array per record; load's own are in `keep`)
+
+    def _colour_node(self, kind, index, field, where, spectrum=-1, emitter=False):
+        return ("spectrum", spectrum) if _SPECTRAL is not None else ("colour", kind, index, field, where, emitter)
 
     # ------------------------------------------------------------ helpers
     def _register(self, d, kind, index):
@@ -450,25 +490,15 @@ class SceneBuilder:
                     rec.file_bbox_max[:] = meta["bbox_max"]
                 elif p.has("data"):
                     # in-memory grid: array of shape (nz, ny, nx[, channels]) (extension; the reference reads a file)
-                    data = np.asarray(p.get("data"), dtype=np.float32)
-                    if data.ndim == 3:
-                        data = data[..., None]
+                    data = p.get("data")
                     rec.file_bbox_min[:] = (0.0, 0.0, 0.0)
                     rec.file_bbox_max[:] = (1.0, 1.0, 1.0)
                 else:
                     raise RuntimeError("gridvolume: property \"filename\" has not been specified!")
-                data = np.ascontiguousarray(data, dtype=np.float32)
-                if data.ndim != 4:
-                    raise RuntimeError("gridvolume: data must have shape (nz, ny, nx, channels)")
-                mono_max = None
-                if _MONO and data.shape[3] == 3:
-                    # grid3d.cpp:178-179: *_mono variants return the luminance of the interpolated colour. Luminance is
-                    # linear, so it is applied per voxel here; the majorant stays the file's maximum (volume metadata).
-                    mono_max = float(data.max()) if data.size else 0.0
-                    f = np.float32
-                    data = np.ascontiguousarray(((data[..., 0] * f(0.212671) + data[..., 1] * f(0.715160))
-                                                 + data[..., 2] * f(0.072169))[..., None], dtype=np.float32)
+                data, mono_max = _grid_data(data)
                 self.keep.append(data)
+                self.grids[len(self.volumes)] = data                     # traverse(): "data"; mono_max follows an update unless "max_value" is set
+                self.grid_mono_max[len(self.volumes)] = mono_max is not None and not p.has("max_value")
                 rec.data = data.ctypes.data_as(A.fp)
                 rec.nz, rec.ny, rec.nx, rec.channels = data.shape
                 ft = str(p.get("filter_type", "trilinear"))
@@ -497,6 +527,10 @@ class SceneBuilder:
                 rec.value_spectrum = _spectrum(v, where)
             else:
                 rec.value[:] = _color(v, where)
+        if rec.type == A.VOLUME_CONST:                                   # constant3d.cpp:39-41
+            self.nodes[("volume", len(self.volumes))] = [("object", "color", self._colour_node("volume", len(self.volumes), "value", where, rec.value_spectrum))]
+        else:                                                            # grid3d.cpp:366-369, gridvolume_spectral.cpp:388-392
+            self.nodes[("volume", len(self.volumes))] = [("param", "data", "grid", "data"), ("param", "size", "size", None)]
         self.volumes.append(rec)
         self._register(v, "volume", len(self.volumes) - 1)
         return len(self.volumes) - 1
@@ -522,10 +556,7 @@ class SceneBuilder:
                 rec.type = A.PHASE_RAYLEIGH
             elif p.type == "tabphase":
                 rec.type = A.PHASE_TABULATED
-                vals = p.get("values")
-                if not isinstance(vals, str):
-                    raise RuntimeError("'values' must be a string")
-                arr = np.array([float(s) for s in vals.replace(",", " ").split()], dtype=np.float32)
+                arr = _tab_values(p.get("values"))
                 self.keep.append(arr)
                 rec.tab_values = arr.ctypes.data_as(A.fp)
                 rec.tab_count = arr.size
@@ -545,6 +576,15 @@ class SceneBuilder:
             else:
                 raise RuntimeError("Unknown / unsupported phase function plugin \"%s\"" % p.type)
             p.finish()
+        node = []
+        if rec.type == A.PHASE_HG:                                       # hg.cpp:86-88
+            node = [("param", "g", "float", "g")]
+        elif rec.type == A.PHASE_TABULATED:                              # tabphase.cpp:97-99
+            node = [("param", "values", "tab", "tab_values")]
+            self.tabs[len(self.phases)] = arr
+        elif rec.type == A.PHASE_BLEND:                                  # blendphase.cpp:141-145
+            node = [("object", "weight", ("volume", rec.weight_volume)), ("object", "phase_0", ("phase", rec.child[0])), ("object", "phase_1", ("phase", rec.child[1]))]
+        self.nodes[("phase", len(self.phases))] = node
         self.phases.append(rec)
         self._register(d, "phase", len(self.phases) - 1)
         return len(self.phases) - 1
@@ -577,6 +617,10 @@ class SceneBuilder:
                 phase = self.add_phase(v, where + "." + k)
         rec.phase = phase if phase is not None else self.add_phase(None, where + ".phase")
         p.finish()
+        # homogeneous.cpp / heterogeneous.cpp:56-61; the phase function under the name Medium::traverse gives it upstream (this fork's Medium
+        # does not list it: without the name the phase parameters of a medium could not be reached)
+        self.nodes[("medium", len(self.media))] = [("param", "scale", "float", "scale"), ("object", "albedo", ("volume", rec.albedo_volume)),
+                                                   ("object", "sigma_t", ("volume", rec.sigma_t_volume)), ("object", "phase_function", ("phase", rec.phase))]
         self.media.append(rec)
         self._register(d, "medium", len(self.media) - 1)
         return len(self.media) - 1
@@ -590,11 +634,13 @@ class SceneBuilder:
         rec = A.Bsdf()
         rec.spectrum[:] = [-1] * 6
         spectral = _SPECTRAL is not None
+        node = []
         def colour(field, slot, key, default):                           # rgb triple, or (spectral variant) the index of the spectrum
             if spectral:
                 rec.spectrum[slot] = _spectrum(p.get(key), where + "." + key, default=default)
             else:
                 getattr(rec, field)[:] = _color(p.get(key), where, default=default)
+            node.append(("object", key, self._colour_node("bsdf", len(self.bsdfs), field, where, rec.spectrum[slot])))
         if p.type == "diffuse":
             rec.type = A.BSDF_DIFFUSE
             colour("reflectance", 0, "reflectance", 0.5)
@@ -614,10 +660,12 @@ class SceneBuilder:
             elif spectral:
                 rec.spectrum[4] = rec.spectrum[1]                        # rpv.cpp:75-79: rho_c defaults to rho_0
             else:
-                rec.rho_c[:] = tuple(rec.rho_0)
+                rec.rho_c[:] = tuple(rec.rho_0)                          # (one texture under two names: traverse() lists it once, an update of rho_0 reaches both)
+                node[0] = ("object", "rho_0", ("colour", "bsdf", len(self.bsdfs), "rho_0+rho_c", where, False))
         else:
             raise RuntimeError("Unknown / unsupported BSDF plugin \"%s\"" % p.type)
         p.finish()
+        self.nodes[("bsdf", len(self.bsdfs))] = node
         self.bsdfs.append(rec)
         self._register(d, "bsdf", len(self.bsdfs) - 1)
         return len(self.bsdfs) - 1
@@ -714,8 +762,21 @@ class SceneBuilder:
             self._emitter_colour(e, ep.get("radiance"), where)
             e.shape = idx
             ep.finish()
+            self.nodes[("emitter", len(self.emitters))] = [("object", "radiance", self._colour_node("emitter", len(self.emitters), "radiance", where, e.radiance_spectrum, True))]
             self.emitters.append(e)
             self.shapes[idx].emitter = len(self.emitters) - 1
+        # shape.cpp:398-413 (+ mesh.cpp:836-848); a shape without a BSDF of its own gets the default one, which the description does not hold
+        node = [("param", "to_world", "geometry", "to_world")]
+        if rec.type == A.SHAPE_MESH:
+            node += [("param", "vertex_count", "geometry", "vertex_count"), ("param", "face_count", "geometry", "face_count"), ("param", "faces_buf", "geometry", "faces"),
+                     ("param", "vertex_positions_buf", "geometry", "vertex_positions")]
+            node += [("param", "vertex_normals_buf", "geometry", "vertex_normals")] if rec.vertex_normals else []
+            node += [("param", "vertex_texcoords_buf", "geometry", "vertex_texcoords")] if rec.vertex_texcoords else []
+        for name, kind, i in (("bsdf", "bsdf", rec.bsdf), ("emitter", "emitter", rec.emitter), ("interior_medium", "medium", rec.interior_medium),
+                              ("exterior_medium", "medium", rec.exterior_medium)):
+            if i >= 0:
+                node.append(("object", name, (kind, i)))
+        self.nodes[("shape", idx)] = node
         self._register(d, "shape", idx)
         return idx
 
@@ -762,6 +823,8 @@ class SceneBuilder:
         else:
             raise RuntimeError("Unknown / unsupported emitter plugin \"%s\"" % p.type)
         p.finish()
+        key = {A.EMITTER_DIRECTIONAL: "irradiance", A.EMITTER_CONSTANT: "radiance", A.EMITTER_POINT: "intensity"}[e.type]
+        self.nodes[("emitter", len(self.emitters))] = [("object", key, self._colour_node("emitter", len(self.emitters), "radiance", where, e.radiance_spectrum, True))]
         self.emitters.append(e)
         return len(self.emitters) - 1
 
@@ -1092,10 +1155,11 @@ class SceneBuilder:
             t = v.get("type")
             if t == "ref":
                 raise RuntimeError("Reference found at the scene level: %s" % k)
+            name = v.get("id", k)                                       # scene.cpp:237-244: a child goes by its id; here a key is one
             if t in SHAPES:
-                self.add_shape(v, k)
+                self.children.append((name, ("shape", self.add_shape(v, k))))
             elif t in ("directional", "constant", "area", "point"):
-                self.add_emitter(v, k)
+                self.children.append((name, ("emitter", self.add_emitter(v, k))))
             elif t in ("perspective", "distant", "mradiancemeter", "mdistant", "distantflux", "radiancemeter"):
                 if self.sensor is not None:
                     raise RuntimeError("this backend supports a single sensor per scene")
@@ -1105,13 +1169,13 @@ class SceneBuilder:
                     raise RuntimeError("Only one integrator can be specified per scene.")
                 self.set_integrator(v, k)
             elif t in ("diffuse", "null", "rpv", "bilambertian"):
-                self.add_bsdf(v, k)
+                self.children.append((name, ("bsdf", self.add_bsdf(v, k))))
             elif t in ("homogeneous", "heterogeneous"):
-                self.add_medium(v, k)
+                self.children.append((name, ("medium", self.add_medium(v, k))))
             elif t in ("isotropic", "hg", "rayleigh", "tabphase", "blendphase"):
-                self.add_phase(v, k)
+                self.children.append((name, ("phase", self.add_phase(v, k))))
             elif t in ("gridvolume", "constvolume"):
-                self.add_volume(v, k)
+                self.children.append((name, ("volume", self.add_volume(v, k))))
             else:
                 raise RuntimeError("Unknown / unsupported plugin \"%s\" (key \"%s\")" % (t, k))
         if self.sensor is None:
@@ -1146,7 +1210,7 @@ def build_scene_desc(d, mono=False, spectral=False):
     mono: build the scene with the semantics of the *_mono variants; spectral: with those of scalar_spectral."""
     global _MONO, _SPECTRAL
     b = SceneBuilder()
-    b.spectra = []
+    b.mono, b.spectral = bool(mono), bool(spectral)
     with _BUILD_LOCK:                    # the variant of the scene being built is module state: one build at a time (threads may load scenes side by side)
         _MONO = bool(mono)
         _SPECTRAL = b if spectral else None

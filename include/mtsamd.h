@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MTS_ABI_VERSION 9
+#define MTS_ABI_VERSION 10
 
 /* Transform4f: row-major 4x4 matrix and its inverse transpose (transform.h:36-50). */
 typedef struct mts_transform {
@@ -296,6 +296,28 @@ int  mts_abi_sizeof(const char *struct_name);   /* sizeof(<struct_name>) as comp
  * constructor-time precomputation, builds the acceleration structure and uploads everything to HBM. */
 int  mts_scene_create(const mts_scene_desc *desc, int device, mts_scene **out);
 int  mts_scene_destroy(mts_scene *scene);
+
+/* Scene parameter updates: what `traverse(scene)` + `params.update()` do in the reference (src/python/python/util.py:14-190: every
+ * plugin's traverse() lists its parameters, parameters_changed() re-runs what its constructor derived from them).  `desc` is the
+ * description the scene was created from with new VALUES in the records `dirty` lists; records that are not listed are not looked at.
+ * The topology is frozen: in a dirty record the `type`, every index into another array, a grid's dimensions / channels / filter /
+ * wrap mode / transform and every table or spectrum `count` must be what the scene was created with -- anything else is an error
+ * that names the record and the field.  Shapes, the sensor, the film and the integrator have no MTS_OBJ_* (no geometry updates).
+ *
+ * For each dirty record the library re-runs the constructor-time work of mts_scene_create for it and for every record derived from
+ * it (a grid's maximum and z-profile property, the majorant / grey flag / interleaved pair grid of the media that read it, a
+ * tabulated distribution's cdf, ...), so the next mts_render sees exactly the scene a fresh mts_scene_create(desc) would build, and
+ * picks the same kernel.  Device allocations keep their addresses; new contents are written on `stream` (NULL = default stream), and
+ * the call returns once they are in place, so the caller's arrays may go away.  Everything is validated before anything is written:
+ * a refused update (also: n < 0, a NULL desc, an ABI mismatch, an index out of range, a device_data on anything but a grid, a render
+ * of this scene in flight) leaves the scene as it was. */
+enum { MTS_OBJ_SPECTRUM = 0, MTS_OBJ_VOLUME = 1, MTS_OBJ_PHASE = 2, MTS_OBJ_MEDIUM = 3, MTS_OBJ_BSDF = 4, MTS_OBJ_EMITTER = 5 };
+typedef struct mts_dirty {
+    int32_t object, index;       /* which record of the description changed: MTS_OBJ_*, index into its array               */
+    const float *device_data;    /* MTS_OBJ_VOLUME, grids only: non-NULL = the new nz*ny*nx*channels floats are read from this
+                                    pointer in the scene's device memory; desc's `data` is ignored                          */
+} mts_dirty;
+int  mts_scene_update(mts_scene *scene, const mts_scene_desc *desc, const mts_dirty *dirty, int32_t n, void *stream);
 
 /* Integrator::render + Film::bitmap(raw=True): renders `sensor.sample_count` samples per pixel and
  * ADDS nothing to previous content: `film` receives crop_height*crop_width*5 floats (X,Y,Z,A,W),
