@@ -209,8 +209,9 @@ class Integrator:
         (integrator_v.cpp:124-156); ctypes releases the GIL for the duration of mts_render, and the
         SIGINT scope of the C ABI (mts_sigint_scope_enter / _exit) does the same here.  Extra keyword arguments are extensions used by the
         multi-GPU path: `shard_*` selects the blocks this rank renders, `device_film` is a device
-        pointer (e.g. torch tensor data_ptr) receiving the film instead of host memory: crop_height x crop_width x (5 + 2 x bins)
-        floats -- X, Y, Z, A, W and, under `nbins` / `bins`, two AOV channels per spectral bin.  `device_film_floats` is the size of
+        pointer (e.g. torch tensor data_ptr) receiving the film instead of host memory: crop_height x crop_width x channels
+        floats -- X, Y, Z, A, W and one channel per name of aov_names(): two per spectral bin under `nbins` / `bins`, six under
+        `moment` (11 channels: the nested integrator's XYZ, then its square).  `device_film_floats` is the size of
         that buffer in floats (default: height x width x 5, the plain XYZAW film); mts_render refuses a buffer that is too small.
         """
         if scene is not self._scene:
@@ -235,7 +236,8 @@ class Integrator:
                 sensor._film._storage = None
                 A.check(A.lib().mts_render(scene._handle, C.byref(opts), C.c_void_p(int(device_film)), C.byref(stats)))
             else:
-                out = np.zeros((h, w, 5 + 2 * scene._desc.integrator.bin_count), dtype=np.float32)    # X, Y, Z, A, W + aov_names()
+                it = scene._desc.integrator
+                out = np.zeros((h, w, 11 if it.moment else 5 + 2 * it.bin_count), dtype=np.float32)    # X, Y, Z, A, W + aov_names()
                 opts.film_on_device = 0
                 opts.film_capacity = out.size
                 sensor._film._storage = out
@@ -251,7 +253,7 @@ class Integrator:
         A.lib().mts_cancel(self._scene._handle)
 
     def aov_names(self):
-        """SamplingIntegrator::aov_names (integrator.cpp:47-49; nbins.cpp:127-134, bins.cpp:112-119)."""
+        """SamplingIntegrator::aov_names (integrator.cpp:47-49; nbins.cpp:127-134, bins.cpp:112-119, moment.cpp:43-52)."""
         return list(getattr(self._scene._keep, "aov_names", []))
 
     def sample(self, scene, origins, directions, seed_offset=0, wavelengths=None):
@@ -344,7 +346,7 @@ def wavefront_sampler(lanes, seed_value, count, device=0):
 def load_dict(d, device=0):
     """mitsuba.core.xml.load_dict (src/libcore/python/xml_v.cpp:23-68,100-272)."""
     _require_variant()
-    if isinstance(d, dict) and d.get("type") in ("nbins", "bins"):
+    if isinstance(d, dict) and d.get("type") in ("nbins", "bins", "moment"):
         # the reference's tests construct these integrators on their own (src/integrators/tests/test_bins.py:10-53): validated like
         # inside a scene, and good for aov_names()
         from . import scene_dict as SD

@@ -12,7 +12,7 @@ from . import _buildid
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTSAMD_LIB") or os.path.join(HERE, "libmtsamd.so")
 
-MTS_ABI_VERSION = 10
+MTS_ABI_VERSION = 11
 
 # enums (include/mtsamd.h)
 VOLUME_CONST, VOLUME_GRID, VOLUME_GRID_SPECTRAL = 0, 1, 2
@@ -95,7 +95,7 @@ class Sensor(C.Structure):
 class Integrator(C.Structure):
     _fields_ = [("type", i32), ("max_depth", i32), ("rr_depth", i32), ("hide_emitters", i32),
                 ("block_size", i32), ("samples_per_pass", i32), ("timeout", f32), ("use_spectral_mis", i32), ("monochrome", i32),
-                ("spectral", i32), ("bin_mode", i32), ("bin_count", i32), ("bin_lo", fp), ("bin_hi", fp)]
+                ("spectral", i32), ("bin_mode", i32), ("bin_count", i32), ("bin_lo", fp), ("bin_hi", fp), ("moment", i32)]
 
 
 class SceneDesc(C.Structure):

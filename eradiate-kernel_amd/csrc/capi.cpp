@@ -187,7 +187,15 @@ int mts_sigint_scope_exit(void) {
 }
 
 // What choose_kernel (render_plan.cpp; DESIGN.md section 4, "kernel table") reads of a scene
-static KernelFacts facts_of(const HostScene &hs) { return { hs.integrator.type, hs.integrator.spectral != 0, hs.integrator.use_spectral_mis != 0, !hs.media.empty(), hs.scene.bin_count > 0, hs.scene.srf >= 0, hs.srf_lookup_by_wavelength, hs.scene.sensor.wavefront != 0, hs.traits }; }
+// (a `moment` scene presents no traits: its kernels are in the general unit)
+static KernelFacts facts_of(const HostScene &hs) { return { hs.integrator.type, hs.integrator.spectral != 0, hs.integrator.use_spectral_mis != 0, !hs.media.empty(), hs.scene.bin_count > 0, hs.scene.srf >= 0, hs.srf_lookup_by_wavelength, hs.scene.sensor.wavefront != 0, hs.integrator.moment ? 0 : hs.traits }; }
+// The kernel that renders a scene: the table's choice, which the `moment` wrapper maps to its own instantiation of that row or to the
+// nested moment kernel (kernel_names.h: kv::moment_variant)
+static KernelChoice kernel_of(const HostScene &hs, uint32_t block_size, const RenderSwitches &sw, bool counters) {
+    KernelChoice kc = choose_kernel(facts_of(hs), block_size, sw);
+    if (hs.integrator.moment) kc.variant = kv::moment_variant(kc.variant, hs.integrator.type, hs.scene.sensor.wavefront != 0, counters);
+    return kc;
+}
 
 // Not part of the ABI either: mts_stats.kernel_variant as mts_render would report it for this description under the environment's
 // switches.  Host only (tests/test_abi.py::test_kernel_choice).
@@ -196,7 +204,7 @@ int mts_debug_kernel_choice(const mts_scene_desc *desc, int32_t *kernel_variant)
     if (!kernel_variant) throw std::runtime_error("mts_debug_kernel_choice: kernel_variant is NULL");
     HostScene *hs = build_host_scene(desc);
     try {
-        const KernelChoice kc = choose_kernel(facts_of(*hs), plan_block_size(hs->integrator.block_size), read_render_switches());
+        const KernelChoice kc = kernel_of(*hs, plan_block_size(hs->integrator.block_size), read_render_switches(), false);
         *kernel_variant = kv::stat(kc.variant, kc.unit);
     } catch (...) { free_host_scene(hs); throw; }
     free_host_scene(hs);
@@ -225,7 +233,7 @@ int mts_debug_update_plan(const mts_scene_desc *before, const mts_scene_desc *af
     HostScene *hs = build_host_scene(before);
     try {
         update_host_scene(*hs, after, dirty, n, nullptr);
-        const KernelChoice kc = choose_kernel(facts_of(*hs), plan_block_size(hs->integrator.block_size), read_render_switches());
+        const KernelChoice kc = kernel_of(*hs, plan_block_size(hs->integrator.block_size), read_render_switches(), false);
         *traits = hs->traits; *kernel_variant = kv::stat(kc.variant, kc.unit);
     } catch (...) { free_host_scene(hs); throw; }
     free_host_scene(hs);
@@ -274,8 +282,9 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
     const uint32_t block_size = plan.block_size; const size_t film_floats = plan.film_floats;
     if (opts.film_capacity > 0 && (uint64_t) opts.film_capacity < (uint64_t) film_floats)
         throw std::runtime_error("mts_render: the film buffer holds " + std::to_string(opts.film_capacity) + " floats, this scene writes " + std::to_string(film_floats) +
-                                 " (crop_width x crop_height x " + std::to_string(hs.scene.film_channels) + " channels: X, Y, Z, A, W + two per spectral bin)");
-    const KernelChoice kc = choose_kernel(facts_of(hs), block_size, sw);
+                                 " (crop_width x crop_height x " + std::to_string(hs.scene.film_channels) + " channels: " +
+                                 (hs.integrator.moment ? "X, Y, Z, A, W + the moment integrator's m1.X, m1.Y, m1.Z, m2.X, m2.Y, m2.Z)" : "X, Y, Z, A, W + two per spectral bin)"));
+    const KernelChoice kc = kernel_of(hs, block_size, sw, opts.collect_counters != 0);
     const int variant = kc.variant;
 #if defined(MTSAMD_HOST_ONLY)
     (void) stream; (void) t0; (void) stats; (void) variant;
@@ -334,7 +343,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
             const size_t ws_records = hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS ? 2 : 1;
             float *d_ws = (float *) rc.get(BUF_WORKSPACE, render_workspace_floats(paths, variant) * ws_records * sizeof(float));
             const RenderArgs args = { &hs.scene, d_blocks, (uint32_t) blocks.size(), block_size, spp, d_target, d_counters, opts.collect_counters != 0, variant,
-                                      d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream };
+                                      d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream, hs.integrator.moment != 0 };
             HIP_CHECK(launcher(args));
             HIP_CHECK(hipEventRecord(rc.ev1, stream));
             for (;;) {

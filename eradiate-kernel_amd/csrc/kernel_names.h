@@ -16,6 +16,16 @@ constexpr int ring_paths(int variant) { return variant - RING_BASE; }
 constexpr int stat(int variant, int unit) { return variant + UNIT_STRIDE * unit; }        // mts_stats.kernel_variant
 constexpr int stat_variant(int kernel_variant) { return kernel_variant % UNIT_STRIDE; }
 constexpr int stat_unit(int kernel_variant) { return kernel_variant / UNIT_STRIDE; }
+// The `moment` integrator (mts_integrator.moment) renders on the general rgb / mono unit.  Its eleven-channel sample tail is built into
+// three formulations -- `volpath` on 1024-path rings, `volpathmis` on 512-path rings, `path` as the flat loop -- with scalar streams and
+// without counters; for every other row of the kernel table the nested moment kernel runs.  `variant`: what choose_kernel gave the
+// scene; `integrator`: MTS_INTEGRATOR_* (0 path, 1 volpath, 2 volpathmis).  Returns the variant that renders it.
+constexpr int moment_variant(int variant, int integrator, bool wavefront, bool counters) {
+    return counters || wavefront ? NESTED
+         : variant == ring(1024) && integrator == 1 ? variant
+         : variant == ring(512) && integrator == 2 ? variant
+         : variant == FLAT && integrator == 0 ? variant : NESTED;
+}
 } // namespace kv
 enum KernelUnit : int { UNIT_GENERAL = 0, UNIT_A = 1, UNIT_B = 2, UNIT_S = 3, UNIT_P = 4, UNIT_PS = 5, UNIT_H = 6, UNIT_C = 7, UNIT_COUNT = 8 };
 

@@ -40,7 +40,8 @@ DEV void flush_counters(unsigned long long *counters, const Counters &cnt) {
 // straight into the film.  With the default box filter a sample lands in its own pixel and is summed
 // in registers in sample order (bit-identical to the reference's block accumulation); the rare
 // sample that falls on the left/top pixel edge (u == 0) goes to the neighbour through an atomic.
-template <bool COUNT, int INTEG>
+// MOMENT (rgb / mono general unit): the `moment` wrapper's tail, eleven accumulators (splat_moment_t, volpath_flat.h)
+template <bool COUNT, int INTEG, bool MOMENT = false>
 __device__ __forceinline__ void render_sample(const DScene &sc, Pcg32 &rng, const DBlock &blk, uint32_t lx, uint32_t ly,
                                               float *__restrict__ film, float acc[5], Counters &cnt) {
     const DSensor &se = sc.sensor;
@@ -69,6 +70,9 @@ __device__ __forceinline__ void render_sample(const DScene &sc, Pcg32 &rng, cons
     bool valid;
 #if MTS_SPEC_N == 3
     F3 L = integrator_sample<COUNT, INTEG>(sc, rng, ray, se.medium, valid, cnt);
+#if !defined(MTS_LEAN)
+    if constexpr (MOMENT) { splat_moment_t<true>(sc, blk, lx, ly, position_sample, L, ray_weight.x, valid, as_global(film), acc); return; }
+#endif
     L = ray_weight * L;
     splat_sample_t<false>(sc, blk, lx, ly, position_sample, L, valid, as_global(film), acc);
 #else
@@ -90,7 +94,7 @@ __device__ __forceinline__ void render_sample(const DScene &sc, Pcg32 &rng, cons
 // same order, and sums its samples in the same order: bit-identical to the nested formulation and to the CPU restatement.
 // Written over the variant's spectrum type: in the spectral build a sample also draws its four wavelengths (from the sensor's response
 // function when there is one), carries the bins' AOV values and reaches the film through spectrum_to_xyz, as render_sample above.
-template <bool COUNT>
+template <bool COUNT, bool MOMENT = false>
 __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, const DBlock &blk, uint32_t lx, uint32_t ly, uint32_t sample_count,
                                                 float *__restrict__ film, float acc[5], Counters &cnt, const uint32_t *stop_flag) {
     const DSensor &se = sc.sensor;
@@ -189,6 +193,10 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
         }
         if (ended) {                                             // integrator.cpp:265-288: splat, next sample of this pixel
 #if MTS_SPEC_N == 3
+#if !defined(MTS_LEAN)
+            if constexpr (MOMENT) splat_moment_t<true>(sc, blk, lx, ly, position_sample, result, ray_weight, valid_ray, as_global(film), acc);
+            else
+#endif
             splat_sample_t<false>(sc, blk, lx, ly, position_sample, f3s(ray_weight) * result, valid_ray, as_global(film), acc);
 #else
             float aov[2 * 64]; const int na = 2 * sc.bin_count;  // nbins / bins: the wrapped integrator's own result, before the ray weight
@@ -294,6 +302,64 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis(D
 }
 
 #if MTS_SPEC_N == 3 && !defined(MTS_LEAN)
+// ---- the `moment` integrator (integrators/moment.cpp): the kernels above with the eleven-channel sample tail (splat_moment_t,
+// volpath_flat.h), under names of their own -- the plain instantiations stay what they are.  launch_render maps a row of the kernel
+// table to one of these (kernel_names.h: kv::moment_variant).
+// Per lane.  FLAT: `path` as the flat loop with regeneration; otherwise the nested formulation of whichever integrator the scene has
+// (decided at run time: one kernel serves the three), which is also the fallback of every row without a moment instantiation.
+template <bool COUNT, bool FLAT>
+__global__ void __launch_bounds__(256, FLAT ? MTS_PATH_WAVES : MTS_NESTED_WAVES) render_kernel_moment(DScene sc, const DBlock *__restrict__ blocks, uint32_t n_blocks, uint32_t block_size,
+                                                     uint32_t sample_count, float *__restrict__ film_base, unsigned long long *__restrict__ counters,
+                                                     const uint32_t *__restrict__ stop_flag) {
+    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];             // as render_kernel
+    {
+        const int staged = min(sc.bvh_node_count, MTS_BVH_LDS_NODES);
+        for (int k = (int) threadIdx.x; k < staged * 8; k += (int) blockDim.x) bvh_top[k] = sc.bvh_nodes[k];
+        pm_tables_to_lds(threadIdx.x);
+        __syncthreads();
+        sc.bvh_lds = bvh_top; sc.bvh_lds_count = staged;
+    }
+    const uint32_t ppb = block_size * block_size;
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t b = gid / ppb, i = gid - b * ppb;
+    if (b >= n_blocks) return;
+    const DBlock blk = blocks[b];
+    float *__restrict__ film = film_base + (((size_t) blk.film_off_hi << 32) | blk.film_off_lo);
+    const uint32_t lx = compact_bits(i), ly = compact_bits(i >> 1);
+    if (lx >= (uint32_t) blk.sx || ly >= (uint32_t) blk.sy) return;
+    Pcg32 rng;
+    rng.seed(sc.sensor.seed + (uint64_t) blk.id * ppb + i, PCG32_DEFAULT_STREAM);
+    Counters cnt = {};
+    float acc[MTS_MOMENT_CHANNELS] = {};
+    if (FLAT) path_pixel_flat<COUNT, true>(sc, rng, blk, lx, ly, sample_count, film, acc, cnt, stop_flag);
+    else
+    for (uint32_t j = 0; j < sample_count; ++j) {
+        if ((j & 63u) == 63u && stop_requested(stop_flag)) break;
+        if (sc.sensor.wavefront) seed_wavefront_sample(rng, sc.sensor, blk, lx, ly, j);
+        render_sample<COUNT, NI_ANY, true>(sc, rng, blk, lx, ly, film, acc, cnt);
+    }
+    float *dst = film_entry_moment(sc, blk, lx, ly, as_global(film));
+    for (int k = 0; k < MTS_MOMENT_CHANNELS; ++k) atomicAdd(dst + k, acc[k]);
+    if (COUNT) flush_counters(counters, cnt);
+}
+// The ring machines (render_kernel_wga / render_kernel_wga_mis) with the moment tail in their NEW block; scalar streams, no counters.
+template <int WG, int NT, int WPE>
+__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_moment(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
+                                                                  uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
+                                                                  unsigned long long *counters, const uint32_t *stop_flag,
+                                                                  const uint32_t *tiles, uint32_t n_tiles) {
+    Counters cnt = {};
+    ring_workgroup_async<VolpathRing<false, WG, false, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+}
+template <bool SPEC, int WG, int NT>
+__global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis_moment(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
+                                                                      uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
+                                                                      unsigned long long *counters, const uint32_t *stop_flag,
+                                                                      const uint32_t *tiles, uint32_t n_tiles) {
+    Counters cnt = {};
+    ring_workgroup_async<VolpathMisRing<false, SPEC, WG, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+}
+
 // SamplingIntegrator::sample for caller-supplied rays (librender/python/integrator_v.cpp:62-78)
 __global__ void __launch_bounds__(256) sample_kernel(DScene sc, int32_t n, uint64_t seed_offset, const float *__restrict__ rays /* 6 SoA rows */,
                                                      float *__restrict__ out_rgb, uint8_t *__restrict__ out_valid) {
@@ -473,6 +539,9 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     if (threads + 1024 >= ((uint64_t) 1 << 32)) return hipErrorInvalidValue;      // thread and path indices are 32 bit (mts_render launches in chunks)
     const int integ = a.sc->integrator.type;
     const bool volpath = integ == MTS_INTEGRATOR_VOLPATH, mis = integ == MTS_INTEGRATOR_VOLPATHMIS, spec_mis = a.sc->integrator.use_spectral_mis != 0;
+#if defined(MTS_LEAN)
+    if (a.moment) return hipErrorInvalidConfiguration;         // a moment scene presents no traits: the general unit renders it
+#endif
 #if defined(MTS_LEAN_PATH)    // kernels_lean_p.hip / _ps.hip: `path` as the flat loop with regeneration, nothing else
     (void) volpath; (void) mis; (void) spec_mis;
     if (a.variant == kv::FLAT && integ == MTS_INTEGRATOR_PATH) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_PATH));
@@ -494,6 +563,13 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     return hipErrorInvalidConfiguration;
 #else                         // the general kernels
 #if MTS_SPEC_N == 3
+    if (a.moment) {                                            // the `moment` wrapper: a.variant is kv::moment_variant() of the table's row (capi.cpp)
+        if (a.variant != kv::moment_variant(a.variant, integ, a.sc->sensor.wavefront != 0, a.count)) return hipErrorInvalidConfiguration;
+        if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, render_kernel_wga_moment<1024, 1024, 4>);
+        if (a.variant == kv::ring(512)) return launch_wg(a, threads, 512, 512, spec_mis ? render_kernel_wga_mis_moment<true, 512, 512> : render_kernel_wga_mis_moment<false, 512, 512>);
+        if (a.variant == kv::FLAT) return launch_lane(a, threads, render_kernel_moment<false, true>);
+        return launch_lane(a, threads, a.count ? render_kernel_moment<true, false> : render_kernel_moment<false, false>);
+    }
     if (kv::is_ring(a.variant) && volpath) {                      // asynchronous regrouping
         if (a.sc->sensor.wavefront)                           // gpu_* streams: the instantiation that recomputes the generator's increment (wg_block, WF)
             return a.variant == kv::ring(1024) ? launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4, true)) : hipErrorInvalidConfiguration;
@@ -510,6 +586,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     }
     if (a.variant != kv::NESTED && volpath) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_VOLPATH));     // the flat state machine per lane
 #else
+    if (a.moment) return hipErrorInvalidConfiguration;         // rgb / mono only (scene_host.cpp refuses the description)
     // four-wide state: `volpath` 42 hot dwords per path; `volpathmis` 69 with spectral MIS (round 4: the path's matrices are parked during
     // walks), 53 without -- 256 paths per workgroup, two or three workgroups per CU
     if (kv::is_ring(a.variant) && volpath)

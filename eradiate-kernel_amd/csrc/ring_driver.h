@@ -120,7 +120,7 @@ DEV void wga_push(int cls, uint32_t pid, bool valid, uint16_t (*q_ids)[WG], uint
 // should_stop(), film->put(block) follows; :213-216).  The sample in flight is dropped, W counts the finished ones.  Runs behind a
 // workgroup barrier, when no wave touches the path state any more; `packed_at` = the hot dword that holds a path's state (S_DONE:
 // already on the film).
-template <int WG, int NT>
+template <int WG, int NT, bool MOMENT = false>
 DEV void wg_flush_unfinished(const MTS_CONST_AS void *kernarg, const uint32_t *hot_lds, int packed_at, uint32_t wg_base) {
     const WgArgs a = cload_k<WgArgs>(kernarg);
 #pragma unroll 1
@@ -128,7 +128,7 @@ DEV void wg_flush_unfinished(const MTS_CONST_AS void *kernarg, const uint32_t *h
         if ((hot_lds[packed_at * WG + pid] & 15u) == S_DONE) continue;
         PathEnvT<ColdStoreHbm> e;
         if (!wg_env<WG>(a, wg_base, pid, e)) continue;
-        float *own = film_entry(a.sc, e.blk, e.lx, e.ly, e.film);
+        float *own = film_entry_of<MOMENT>(a.sc, e.blk, e.lx, e.ly, e.film);       // a `moment` machine's AOV channels are on the film already
         for (int k = 0; k < 5; ++k) atomicAdd(own + k, e.cold.f(C_ACC + k));
     }
 }
@@ -317,7 +317,7 @@ DEV void ring_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt) {
     }
 #endif
     __syncthreads();                                          // every wave has left the loop: the path state is final
-    if (__atomic_load_n(&q_ctl[2 * B_COUNT], __ATOMIC_RELAXED) != STOP_NONE) wg_flush_unfinished<WG, NT>(kernarg, hot_lds, M::PACKED, wg_base);
+    if (__atomic_load_n(&q_ctl[2 * B_COUNT], __ATOMIC_RELAXED) != STOP_NONE) wg_flush_unfinished<WG, NT, M::Machine::MOMENT>(kernarg, hot_lds, M::PACKED, wg_base);
 }
 
 } // inline namespace

@@ -695,6 +695,12 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     sc.integrator.monochrome = it.monochrome != 0;
     hs.integrator = it;
     hs.integrator.bin_lo = hs.integrator.bin_hi = nullptr;                                     // copied: the caller's arrays may go away
+    // ---- moment (moment.cpp:27-58): six AOV channels around the nested integrator; rgb / mono only on this backend, never around the bins
+    if (it.moment != 0) {
+        if (it.moment != 1) throw std::runtime_error("integrator: \"moment\" must be 0 or 1");
+        if (it.bin_mode != 0) throw std::runtime_error("the moment integrator cannot wrap nbins / bins (\"moment\" together with \"bin_mode\")");
+        if (spectral) throw std::runtime_error("the moment integrator is not supported in the spectral variant");
+    }
     // ---- nbins / bins (nbins.cpp:55-98, bins.cpp:23-85) and the sensor's srf (perspective.cpp:113-121, radiancemeter.cpp:62-68)
     sc.srf = -1; sc.bin_mode = 0; sc.bin_count = 0; sc.bin_lo = sc.bin_hi = nullptr; sc.film_channels = 5;
     if (it.bin_mode != 0) {
@@ -709,6 +715,7 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
             }
         sc.bin_mode = it.bin_mode; sc.bin_count = it.bin_count; sc.film_channels = 5 + 2 * it.bin_count;
     } else hs.integrator.bin_count = 0;
+    if (it.moment != 0) sc.film_channels = 11;             // X, Y, Z, A, W, then the nested integrator's XYZ and its square (validated above)
     if (spectral && d->sensor.srf != 0) {
         if (d->sensor.srf < 0 || d->sensor.srf > d->spectrum_count) throw std::runtime_error("index out of range: sensor srf");
         if (d->sensor.type != MTS_SENSOR_PERSPECTIVE && !(d->sensor.type == MTS_SENSOR_MRADIANCEMETER && d->sensor.multi_count == 1))

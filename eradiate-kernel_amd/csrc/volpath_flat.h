@@ -284,11 +284,98 @@ DEV void splat_sample_t(const DScene &sc, const DBlock &blk, uint32_t lx, uint32
     }
 }
 
+#if !defined(MTS_LEAN)
+#define MTS_MOMENT_CHANNELS 11
+// The `moment` integrator's film splat (integrators/moment.cpp:60-90 around the nested integrator's sample(), then
+// librender/integrator.cpp:265-285 + librender/imageblock.cpp:79-172): eleven values per sample -- X, Y, Z, A, W of ray_weight * L as
+// splat_sample_t forms them, then xyz of L itself (BEFORE the sensor's ray weight; mono: L.x three times) and the squares of those
+// three, each rounded once.  A film with AOV channels is created with warn_negative = false (integrator.cpp:114-116), so a sample is
+// dropped iff one of the eleven is not finite; the -1e-5 test of the plain film does not apply.  Every channel takes the same filter
+// weights, eleven floats per film pixel.  A sibling of splat_sample_t on purpose: the plain kernels keep their five-channel copy.
+// OWN_ALL: `own` holds eleven register accumulators (per-lane kernels); otherwise five (the ring machines' cold record), and the six
+// AOV values of a sample that lands in the lane's own pixel join its film entry by atomics -- one path writes them in sample order, so
+// the sum is the block's (as splat_values_bins, integrator_dev.h).
+template <bool OWN_ALL>
+DEV void splat_moment_t(const DScene &sc, const DBlock &blk, uint32_t lx, uint32_t ly, F2 position_sample, F3 L, float ray_weight, bool valid,
+                        MTS_GLOBAL_AS float *film, float *own) {
+    const DSensor &se = sc.sensor;
+    constexpr int C = MTS_MOMENT_CHANNELS;
+    const F3 Lw = f3s(ray_weight) * L;
+    float v[C];                                                 // srgb_to_xyz, core/spectrum.h:221-227
+    v[0] = pm_fma(0.180423f, Lw.z, pm_fma(0.357580f, Lw.y, 0.412453f * Lw.x));
+    v[1] = pm_fma(0.072169f, Lw.z, pm_fma(0.715160f, Lw.y, 0.212671f * Lw.x));
+    v[2] = pm_fma(0.950227f, Lw.z, pm_fma(0.119193f, Lw.y, 0.019334f * Lw.x));
+    v[5] = pm_fma(0.180423f, L.z, pm_fma(0.357580f, L.y, 0.412453f * L.x));      // moment.cpp:74-79
+    v[6] = pm_fma(0.072169f, L.z, pm_fma(0.715160f, L.y, 0.212671f * L.x));
+    v[7] = pm_fma(0.950227f, L.z, pm_fma(0.119193f, L.y, 0.019334f * L.x));
+    if (sc.integrator.monochrome) { v[0] = v[1] = v[2] = Lw.x; v[5] = v[6] = v[7] = L.x; }
+    v[3] = valid ? 1.f : 0.f;
+    v[4] = 1.f;
+    for (int k = 0; k < 3; ++k) v[8 + k] = v[5 + k] * v[5 + k];
+    bool ok = true;
+    for (int k = 0; k < C; ++k) ok = ok && pm_isfinite(v[k]);
+    if (!ok) return;
+    const DRFilter &rf = se.rfilter;
+    const int border = rf.border_size;
+    const int sx = blk.sx + 2 * border, sy = blk.sy + 2 * border;
+    float posx = position_sample.x - ((float) (blk.ox - border) + .5f), posy = position_sample.y - ((float) (blk.oy - border) + .5f);
+    if (rf.radius > 0.5f + MTS_RAY_EPSILON) {
+        int lox = max((int) pm_ceil(posx - rf.radius), 0), loy = max((int) pm_ceil(posy - rf.radius), 0);
+        int hix = min((int) pm_floor(posx + rf.radius), sx - 1), hiy = min((int) pm_floor(posy + rf.radius), sy - 1);
+        uint32_t n = (uint32_t) pm_ceil((rf.radius - 2.f * MTS_RAY_EPSILON) * 2.f);
+        float basex = (float) lox - posx, basey = (float) loy - posy;
+        for (uint32_t yr = 0; yr < n; ++yr) {
+            int y = loy + (int) yr;
+            if (y > hiy) break;
+            float wy = as_global(rf.values)[min((int) pm_abs((basey + (float) yr) * rf.scale_factor), 31)];     // eval_discretized, core/rfilter.h:62-65
+            int fy = blk.oy - border + y - se.crop_y;
+            for (uint32_t xr = 0; xr < n; ++xr) {
+                int x = lox + (int) xr;
+                if (x > hix) break;
+                float wx = as_global(rf.values)[min((int) pm_abs((basex + (float) xr) * rf.scale_factor), 31)];
+                float weight = wy * wx;
+                int fx = blk.ox - border + x - se.crop_x;
+                if (fx >= 0 && fy >= 0 && fx < se.crop_w && fy < se.crop_h) {                         // film clipping, imageblock.cpp:49-77
+                    float *dst = (float *) (film + C * ((size_t) fy * se.crop_w + fx));
+                    for (int k = 0; k < C; ++k) atomicAdd(dst + k, v[k] * weight);
+                }
+            }
+        }
+    } else {
+        int lox = (int) pm_ceil(posx - .5f), loy = (int) pm_ceil(posy - .5f);
+        if (!(lox >= 0 && loy >= 0 && lox < sx && loy < sy)) return;
+        float *dst = (float *) (film + C * ((size_t) (blk.oy + loy - se.crop_y) * se.crop_w + (blk.ox + lox - se.crop_x)));
+        if (lox == (int) lx && loy == (int) ly) {
+            for (int k = 0; k < (OWN_ALL ? C : 5); ++k) own[k] += v[k];
+            if (!OWN_ALL) for (int k = 5; k < C; ++k) atomicAdd(dst + k, v[k]);
+        } else {
+            for (int k = 0; k < C; ++k) atomicAdd(dst + k, v[k]);
+        }
+    }
+}
+#endif // !MTS_LEAN
+
 #endif // MTS_SPEC_N == 3 (the spectral build splats through splat_values_t, integrator_dev.h)
 
 // block -> film (hdrfilm.cpp:207-211): the film entry of pixel (lx, ly) of a block, which its accumulators X, Y, Z, A, W join by atomics
 DEV float *film_entry(const DScene &sc, const DBlock &blk, uint32_t lx, uint32_t ly, MTS_GLOBAL_AS float *film) {
     return (float *) (film + MTS_FILM_STRIDE(sc) * ((size_t) (blk.oy + (int) ly - sc.sensor.crop_y) * sc.sensor.crop_w + (blk.ox + (int) lx - sc.sensor.crop_x)));
+}
+
+#if MTS_SPEC_N == 3 && !defined(MTS_LEAN)
+// the same entry of a `moment` film (eleven floats per pixel, splat_moment_t)
+DEV float *film_entry_moment(const DScene &sc, const DBlock &blk, uint32_t lx, uint32_t ly, MTS_GLOBAL_AS float *film) {
+    return (float *) (film + MTS_MOMENT_CHANNELS * ((size_t) (blk.oy + (int) ly - sc.sensor.crop_y) * sc.sensor.crop_w + (blk.ox + (int) lx - sc.sensor.crop_x)));
+}
+#endif
+// which film a ring machine writes: MOMENT machines (rgb / mono general unit only) the eleven-channel one
+template <bool MOMENT>
+DEV float *film_entry_of(const DScene &sc, const DBlock &blk, uint32_t lx, uint32_t ly, MTS_GLOBAL_AS float *film) {
+#if MTS_SPEC_N == 3 && !defined(MTS_LEAN)
+    if constexpr (MOMENT) return film_entry_moment(sc, blk, lx, ly, film);
+    else
+#endif
+    return film_entry(sc, blk, lx, ly, film);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -425,6 +512,11 @@ struct RingMachine {
         float acc[5];                                          // summed in sample order like the block entry (imageblock.cpp:163-168)
         for (int k = 0; k < 5; ++k) acc[k] = e.cold.f(C_ACC + k);
 #if MTS_SPEC_N == 3
+#if !defined(MTS_LEAN)
+        // M::MOMENT: the `moment` wrapper's tail -- the same five accumulators, the six AOV values straight to the film entry
+        if constexpr (M::MOMENT) splat_moment_t<false>(sc, e.blk, e.lx, e.ly, position_sample, p.res, e.cold.f(C_RAYW), (p.flags & FL_VALID_RAY) != 0, e.film, acc);
+        else
+#endif
         splat_sample_t<false>(sc, e.blk, e.lx, e.ly, position_sample, f3s(e.cold.f(C_RAYW)) * p.res, (p.flags & FL_VALID_RAY) != 0, e.film, acc);
 #else
         {
@@ -440,7 +532,7 @@ struct RingMachine {
 #endif
         const uint32_t sample_idx = __float_as_uint(e.cold.f(C_SAMPLE)) + 1u;
         if (sample_idx == e.sample_count) {                    // block -> film (hdrfilm.cpp:207-211)
-            float *own = film_entry(sc, e.blk, e.lx, e.ly, e.film);
+            float *own = film_entry_of<M::MOMENT>(sc, e.blk, e.lx, e.ly, e.film);
             for (int k = 0; k < 5; ++k) atomicAdd(own + k, acc[k]);
             p.st = S_DONE;
         } else {
@@ -451,9 +543,10 @@ struct RingMachine {
     }
 };
 
-template <bool COUNT>
-struct VolpathMachine : RingMachine<VolpathMachine<COUNT>, PathState, true> {
-    typedef RingMachine<VolpathMachine<COUNT>, PathState, true> Base;
+template <bool COUNT, bool MOMENT_ = false>
+struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_>, PathState, true> {
+    typedef RingMachine<VolpathMachine<COUNT, MOMENT_>, PathState, true> Base;
+    static constexpr bool MOMENT = MOMENT_;                    // RingMachine::blk_new: the `moment` wrapper's eleven-channel tail
     using Base::sc; using Base::cnt; using Base::ctx; using Base::queue_intersection; using Base::wants_int;
     DEV VolpathMachine(const DScene &sc_, Counters &cnt_) : Base(sc_, cnt_) {}
     // The head of a sample (the draws up to the camera ray) stays written out here, in VolpathMisMachine::begin_sample and in render_sample
@@ -1073,7 +1166,7 @@ DEV const MTS_CONST_AS void *block_uniforms(const MTS_CONST_AS void *kernarg_, u
 // generator's 64-bit state; its increment, which for the scalar variants' streams is the default stream's constant, is recomputed here
 // from (pixel, sample index) on every load: a 64-bit TEA of four rounds, ~60 instructions, and one dword of the cold record -- in an
 // instantiation of its own, so that the kernels of the scalar streams do not change by an instruction.
-template <bool COUNT, int WG, int C, bool WF = false>
+template <bool COUNT, int WG, int C, bool WF = false, bool MOMENT = false>
 #ifndef WG_BLOCK_ATTR
 #define WG_BLOCK_ATTR __forceinline__   // a real call costs 48 callee-saved VGPR spills + reloads per block visit (measured: 5 TB of scratch writes per render)
 #endif
@@ -1081,7 +1174,7 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
     uint32_t wg_base;
     const MTS_CONST_AS void *kernarg = block_uniforms(kernarg_, wg_base_, wg_base);
     const WgArgs a = cload_k<WgArgs>(kernarg);
-    VolpathMachine<COUNT> vm(a.sc, *cnt);
+    VolpathMachine<COUNT, MOMENT> vm(a.sc, *cnt);
     PathEnvT<ColdStoreHbm> e; wg_env<WG>(a, wg_base, pid, e);
     HotStore<WG> hs; hs.base = hot_lds + pid;
     typedef ClassFields<C> CF;
@@ -1157,13 +1250,13 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
 
 // Driver 2, the asynchronous regrouping of a workgroup's paths through LDS rings, is ring_driver.h; this is what it needs to know of
 // `volpath`.  WF: wavefront streams (wg_block).
-template <bool COUNT_, int WG_, bool WF>
+template <bool COUNT_, int WG_, bool WF, bool MOMENT = false>
 struct VolpathRing {
     static constexpr bool COUNT = COUNT_;
     static constexpr int WG = WG_, HOT_DWORDS = H_COUNT, PACKED = H_PACKED;
     typedef PathState State;
     typedef HotStore<WG_> Hot;
-    typedef VolpathMachine<COUNT_> Machine;
+    typedef VolpathMachine<COUNT_, MOMENT> Machine;
     template <int NT> DEV static void check_shape() { static_assert(NT <= WG_, "a thread per path at most"); }
     DEV static void init_idle(State &p) {
         p.medium = -1; p.thr = p.res = p.trans = spec_s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;
@@ -1172,7 +1265,7 @@ struct VolpathRing {
 #endif
     }
     // the block function itself, not a forwarding function: one more layer of inlining changed the code of the flagship kernel
-    template <int C> static constexpr auto block = &wg_block<COUNT_, WG_, C, WF>;
+    template <int C> static constexpr auto block = &wg_block<COUNT_, WG_, C, WF, MOMENT>;
 };
 
 } // inline namespace

@@ -43,11 +43,12 @@ struct MisPathState {
     uint32_t depth, channel, st, mode, flags;
 };
 
-template <bool COUNT, bool SPEC>
-struct VolpathMisMachine : RingMachine<VolpathMisMachine<COUNT, SPEC>, MisPathState<SPEC>, false> {
+template <bool COUNT, bool SPEC, bool MOMENT_ = false>
+struct VolpathMisMachine : RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, MisPathState<SPEC>, false> {
+    static constexpr bool MOMENT = MOMENT_;                    // RingMachine::blk_new: the `moment` wrapper's eleven-channel tail
     typedef MisPathState<SPEC> P;
     typedef MisWeights<SPEC> W;
-    typedef RingMachine<VolpathMisMachine<COUNT, SPEC>, P, false> Base;
+    typedef RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, P, false> Base;
     using Base::sc; using Base::cnt; using Base::ctx; using Base::queue_intersection;
     DEV VolpathMisMachine(const DScene &sc_, Counters &cnt_) : Base(sc_, cnt_) {}
     // the parked pair: one 128-byte record per path behind the cold records, written and read by one lane as whole lines
@@ -495,12 +496,12 @@ struct MisHotStore : HotFront<WG, MH_SIX> {
 };
 
 // One block of class C for the path `pid` (the class is wave-uniform, the blocks are inlined as in volpath_flat.h)
-template <bool COUNT, bool SPEC, int WG, int C>
+template <bool COUNT, bool SPEC, int WG, int C, bool MOMENT = false>
 static __device__ __forceinline__ int mis_block(const MTS_CONST_AS void *kernarg_, uint32_t *hot_lds, uint32_t wg_base_, uint32_t pid, Counters *cnt) {
     uint32_t wg_base;
     const MTS_CONST_AS void *kernarg = block_uniforms(kernarg_, wg_base_, wg_base);
     const WgArgs a = cload_k<WgArgs>(kernarg);
-    VolpathMisMachine<COUNT, SPEC> vm(a.sc, *cnt);
+    VolpathMisMachine<COUNT, SPEC, MOMENT> vm(a.sc, *cnt);
     PathEnvT<ColdStoreHbm> e; wg_env<WG>(a, wg_base, pid, e);
     MisHotStore<WG, SPEC> hs; hs.base = hot_lds + pid;
     typedef MisClassFields<C> CF;
@@ -532,13 +533,13 @@ static __device__ __forceinline__ int mis_block(const MTS_CONST_AS void *kernarg
 }
 
 // What the ring driver (ring_driver.h) needs to know of `volpathmis`
-template <bool COUNT_, bool SPEC, int WG_>
+template <bool COUNT_, bool SPEC, int WG_, bool MOMENT = false>
 struct VolpathMisRing {
     static constexpr bool COUNT = COUNT_;
     static constexpr int WG = WG_, HOT_DWORDS = MisHotStore<WG_, SPEC>::MH_COUNT, PACKED = H_PACKED;
     typedef MisPathState<SPEC> State;
     typedef MisHotStore<WG_, SPEC> Hot;
-    typedef VolpathMisMachine<COUNT_, SPEC> Machine;
+    typedef VolpathMisMachine<COUNT_, SPEC, MOMENT> Machine;
     template <int NT> DEV static void check_shape() { static_assert(NT <= 2 * WG_, "up to two threads per path (768 on 512: a third wave per SIMD)"); }
     DEV static void init_idle(State &p) {
         p.medium = -1; p.res = spec_s(0.f); p.lsp = f3s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;
@@ -547,7 +548,7 @@ struct VolpathMisRing {
 #endif
         p.pf = p.pn = p.wn = p.wu = mw_full<SPEC>(1.f);
     }
-    template <int C> static constexpr auto block = &mis_block<COUNT_, SPEC, WG_, C>;
+    template <int C> static constexpr auto block = &mis_block<COUNT_, SPEC, WG_, C, MOMENT>;
 };
 
 } // inline namespace

@@ -1120,6 +1120,28 @@ class SceneBuilder:
             it.bin_lo = self._bins[0].ctypes.data_as(A.fp); it.bin_hi = self._bins[1].ctypes.data_as(A.fp)
             self.aov_names = names
             return
+        if p.type == "moment":
+            # src/integrators/moment.cpp:27-58: six AOV channels around one nested sampling integrator -- its result as XYZ and the square
+            if _SPECTRAL is not None:
+                raise RuntimeError("the moment integrator is not supported in the spectral variant by this backend")
+            nested = [(k, v) for k, v in sorted_items(d) if isinstance(v, dict) and k not in ("type", "id")]
+            if not nested:
+                raise RuntimeError("moment: must specify a nested integrator")
+            if len(nested) > 1:
+                raise RuntimeError("moment: more than one nested integrator (%s) is not supported by this backend" % ", ".join(k for k, _ in nested))
+            name, child = nested[0]
+            if child.get("type") not in ("path", "volpath", "volpathmis"):
+                raise RuntimeError("moment: the nested integrator \"%s\" must be one of path, volpath, volpathmis, not \"%s\"" % (name, child.get("type")))
+            p.get(name)
+            # as for nbins / bins above: the wrapper's block_size, samples_per_pass and timeout drive the render loop
+            outer = (int(p.get("block_size", 0)), int(p.get("samples_per_pass", -1)), float(p.get("timeout", -1.0)))
+            p.finish()
+            self.set_integrator(child, where + "." + name)
+            it = self.integrator
+            it.block_size, it.samples_per_pass, it.timeout = outer
+            it.moment = 1
+            self.aov_names = [name + c for c in (".X", ".Y", ".Z")] + ["m2_" + name + c for c in (".X", ".Y", ".Z")]       # moment.cpp:43-52
+            return
         if p.type == "path":
             it.type = A.INTEGRATOR_PATH
         elif p.type == "volpath":
@@ -1164,7 +1186,7 @@ class SceneBuilder:
                 if self.sensor is not None:
                     raise RuntimeError("this backend supports a single sensor per scene")
                 self.set_sensor(v, k)
-            elif t in ("path", "volpath", "volpathmis", "nbins", "bins"):
+            elif t in ("path", "volpath", "volpathmis", "nbins", "bins", "moment"):
                 if self.integrator is not None:
                     raise RuntimeError("Only one integrator can be specified per scene.")
                 self.set_integrator(v, k)

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MTS_ABI_VERSION 10
+#define MTS_ABI_VERSION 11
 
 /* Transform4f: row-major 4x4 matrix and its inverse transpose (transform.h:36-50). */
 typedef struct mts_transform {
@@ -234,6 +234,13 @@ typedef struct mts_integrator {
        number (nbins.cpp:107-121, bins.cpp:99-107); the film then holds 5 + 2 bin_count floats per pixel.                       */
     int32_t bin_mode, bin_count;
     const float *bin_lo, *bin_hi;
+    /* 1: Eradiate's `moment` integrator wrapped around `type` (src/integrators/moment.cpp; rgb / mono variants, not together with
+       spectral or bin_mode): every sample also adds the nested integrator's result as XYZ -- taken BEFORE the sensor's ray weight;
+       mono: L three times -- and the square of each of the three to the film, as six AOV channels behind X, Y, Z, A, W.  The film
+       then holds 11 floats per pixel: X, Y, Z, A, W, m1.X, m1.Y, m1.Z, m2.X, m2.Y, m2.Z, all splatted with the same filter weights;
+       var = m2 / W - (m1 / W)^2.  Such a film has AOVs, so a sample is dropped iff one of its eleven values is not finite (the plain
+       film also drops values below -1e-5).  block_size / samples_per_pass / timeout are the wrapper's.  0 (a zeroed record): none. */
+    int32_t moment;
 } mts_integrator;
 
 typedef struct mts_scene_desc {
@@ -263,7 +270,8 @@ typedef struct mts_stats {
     int32_t cancelled;        /* 1 if mts_cancel stopped the render (render() == false, integrator.cpp:178) */
     int32_t timed_out;        /* 1 if the "timeout" of the integrator stopped it (should_stop(), integrator.h:143-146;
                                  like the reference, render() still returns true then)            */
-    int32_t kernel_variant;   /* kernel formulation of the last launch: 0 = nested per-lane loops, 1 = per-lane state machine,
+    int32_t kernel_variant;   /* kernel formulation of the last launch (a `moment` scene: of the moment kernel that ran -- the table's row where
+                                 it has a moment instantiation, else 0): 0 = nested per-lane loops, 1 = per-lane state machine,
                                  10000 + P = regrouping machine on LDS rings with P paths per workgroup;
                                  + 100000 U when the kernel came from lean translation unit U (1 a, 2 b, 3 s, 4 p, 5 ps, 6 h, 7 c: the same kernel
                                  compiled without what this scene cannot contain -- same film; MTSAMD_LEAN=0 turns them off) */
@@ -281,7 +289,8 @@ typedef struct mts_render_opts {
     int32_t film_on_device;   /* 0: `film` is host memory; 1: `film` is a device pointer         */
     int32_t collect_counters; /* 1: fill n_iter / n_lookup / n_nee_step (slower kernel variant)  */
     int64_t film_capacity;    /* floats the caller's `film` buffer holds; mts_render refuses a buffer smaller than
-                                 crop_width x crop_height x (5 + 2 x spectral bins).  0: unchecked                */
+                                 crop_width x crop_height x channels, channels = 5 + 2 x spectral bins, or 11 for a
+                                 `moment` integrator.  0: unchecked                                                */
 } mts_render_opts;
 
 /* Library / device queries */
@@ -321,7 +330,9 @@ int  mts_scene_update(mts_scene *scene, const mts_scene_desc *desc, const mts_di
 
 /* Integrator::render + Film::bitmap(raw=True): renders `sensor.sample_count` samples per pixel and
  * ADDS nothing to previous content: `film` receives crop_height*crop_width*5 floats (X,Y,Z,A,W),
- * row-major, exactly the reference's raw film storage.  Returns 0 also when cancelled
+ * row-major, exactly the reference's raw film storage.  With AOV channels a pixel holds more floats, X,Y,Z,A,W first:
+ * 5 + 2 * bin_count with nbins / bins (mts_integrator.bin_mode), 11 with mts_integrator.moment (X,Y,Z,A,W, the first moment's
+ * X,Y,Z, the second moment's X,Y,Z).  Returns 0 also when cancelled
  * (stats->cancelled = 1, like render() returning false). */
 int  mts_render(mts_scene *scene, const mts_render_opts *opts, float *film, mts_stats *stats);
 

@@ -1,0 +1,168 @@
+"""Eradiate's `moment` integrator (src/integrators/moment.cpp), host side: the loaders, the C ABI record, the host validation and the
+kernel a moment scene is given.  The render itself is compared with the CPU restatement in tests/test_gpu_moment.py."""
+import ctypes as C
+import importlib
+
+import pytest
+
+import tests.kernel_rows as kr
+
+A = importlib.import_module("eradiate-kernel_amd._capi")
+SD = importlib.import_module("eradiate-kernel_amd.scene_dict")
+PKG = importlib.import_module("eradiate-kernel_amd")
+scenes = importlib.import_module("eradiate-kernel_amd.scenes")
+
+NAMES = lambda n: [n + ".X", n + ".Y", n + ".Z", "m2_" + n + ".X", "m2_" + n + ".Y", "m2_" + n + ".Z"]       # noqa: E731
+
+
+def wrap(d, name="nested", **outer):
+    """The scene `d` with its integrator inside a `moment` wrapper."""
+    return dict(d, integrator=dict({"type": "moment", name: dict(d["integrator"])}, **outer))
+
+
+def integrator_only(d, spectral=False):
+    b = SD.SceneBuilder(); b.spectra = []
+    SD._SPECTRAL = b if spectral else None
+    try:
+        b.set_integrator(d, "integrator")
+    finally:
+        SD._SPECTRAL = None
+    return b
+
+
+@pytest.fixture(scope="module")
+def L():
+    lib = A.lib()
+    lib.mts_last_error.restype = C.c_char_p
+    lib.mts_debug_scene_traits.argtypes = [C.POINTER(A.SceneDesc), C.POINTER(C.c_int32)]
+    lib.mts_debug_kernel_choice.argtypes = [C.POINTER(A.SceneDesc), C.POINTER(C.c_int32)]
+    return lib
+
+
+# ---------------------------------------------------------------------------------------------- loaders
+@pytest.mark.parametrize("nested", ["path", "volpath", "volpathmis"])
+def test_loader_names_and_record(nested):
+    b = integrator_only({"type": "moment", "radiance": {"type": nested, "max_depth": 7, "rr_depth": 3}})
+    assert b.aov_names == NAMES("radiance")
+    it = b.integrator
+    assert it.moment == 1 and it.type == {"path": A.INTEGRATOR_PATH, "volpath": A.INTEGRATOR_VOLPATH, "volpathmis": A.INTEGRATOR_VOLPATHMIS}[nested]
+    assert (it.max_depth, it.rr_depth, it.bin_mode, it.bin_count) == (7, 3, 0, 0)
+
+
+def test_wrapper_drives_the_render_loop():
+    """moment.cpp: Base(props) -- the wrapper's block_size / samples_per_pass / timeout, not the nested integrator's."""
+    it = integrator_only({"type": "moment", "samples_per_pass": 2, "block_size": 16, "timeout": 3.5,
+                          "sub": {"type": "volpath", "samples_per_pass": 8, "block_size": 64, "timeout": 1.0}}).integrator
+    assert (it.samples_per_pass, it.block_size, it.timeout) == (2, 16, 3.5)
+    it = integrator_only({"type": "moment", "sub": {"type": "volpath", "samples_per_pass": 8, "block_size": 64, "timeout": 1.0}}).integrator
+    assert (it.samples_per_pass, it.block_size, it.timeout) == (-1, 0, -1.0)                      # the wrapper's defaults
+
+
+def test_plain_scene_has_no_moment():
+    desc, keep = SD.build_scene_desc(scenes.c1_cornell(8, 8, 1))
+    assert desc.integrator.moment == 0
+    assert A.Integrator().moment == 0                                                             # a zeroed record has none
+
+
+def test_scene_dict_and_detached_integrator():
+    desc, keep = SD.build_scene_desc(wrap(scenes.c3_heterogeneous(8, 8, 2, res=8), "vp", samples_per_pass=1))
+    assert desc.integrator.moment == 1 and desc.integrator.type == A.INTEGRATOR_VOLPATH and desc.integrator.samples_per_pass == 1
+    assert keep.aov_names == NAMES("vp")
+    PKG.set_variant("gpu_rgb")
+    assert PKG.load_dict({"type": "moment", "li": {"type": "path"}}).aov_names() == NAMES("li")
+
+
+@pytest.mark.parametrize("d, message", [
+    ({"type": "moment"}, "must specify a nested integrator"),
+    ({"type": "moment", "a": {"type": "path"}, "b": {"type": "volpath"}}, "more than one nested integrator (a, b)"),
+    ({"type": "moment", "a": {"type": "nbins", "wavelengths": "500", "integrator": {"type": "path"}}}, "\"a\" must be one of path, volpath, volpathmis, not \"nbins\""),
+    ({"type": "moment", "a": {"type": "bins", "bins": "x:500:600", "integrator": {"type": "path"}}}, "not \"bins\""),
+    ({"type": "moment", "a": {"type": "moment", "b": {"type": "path"}}}, "not \"moment\""),
+])
+def test_refusals(d, message):
+    with pytest.raises(RuntimeError) as e:
+        integrator_only(d)
+    assert message in str(e.value)
+
+
+def test_refused_in_the_spectral_variant():
+    with pytest.raises(RuntimeError) as e:
+        integrator_only({"type": "moment", "a": {"type": "path"}}, spectral=True)
+    assert "moment integrator is not supported in the spectral variant" in str(e.value)
+
+
+def test_xml_with_a_nested_integrator():
+    xml_to_dict = importlib.import_module("eradiate-kernel_amd.xml_io").xml_to_dict
+    d = xml_to_dict("""<scene version="2.1.0">
+        <integrator type="moment">
+            <integer name="samples_per_pass" value="2"/>
+            <integrator type="volpathmis" name="radiance"><integer name="max_depth" value="9"/><boolean name="use_spectral_mis" value="false"/></integrator>
+        </integrator>
+        <sensor type="perspective"><film type="hdrfilm"><integer name="width" value="4"/><integer name="height" value="4"/></film>
+            <sampler type="independent"><integer name="sample_count" value="4"/></sampler></sensor>
+        <shape type="sphere"><bsdf type="diffuse"/></shape>
+        <emitter type="constant"/>
+    </scene>""")
+    desc, keep = SD.build_scene_desc(d)
+    it = desc.integrator
+    assert (it.moment, it.type, it.max_depth, it.use_spectral_mis, it.samples_per_pass) == (1, A.INTEGRATOR_VOLPATHMIS, 9, 0, 2)
+    assert keep.aov_names == NAMES("radiance")
+
+
+# ---------------------------------------------------------------------------------------------- C ABI and host
+def test_abi_record(L):
+    assert L.mts_abi_sizeof(b"mts_integrator") == C.sizeof(A.Integrator)
+    assert A.Integrator._fields_[-1] == ("moment", C.c_int32)                                   # appended: the records before it keep their offsets
+    assert A.MTS_ABI_VERSION == L.mts_abi_version() >= 11
+
+
+def test_host_validation(L):
+    """build_host_scene (the first half of mts_scene_create; no device is touched): a status and a message, never a crash."""
+    t = C.c_int32(-1)
+    desc, keep = SD.build_scene_desc(wrap(scenes.c1_cornell(8, 8, 1)))
+    assert L.mts_debug_scene_traits(C.byref(desc), C.byref(t)) == 0, L.mts_last_error()
+    desc.integrator.moment = 2
+    assert L.mts_debug_scene_traits(C.byref(desc), C.byref(t)) != 0 and b"\"moment\" must be 0 or 1" in L.mts_last_error()
+    desc, keep = SD.build_scene_desc(kr.spectral_cornell(8, 8, 1), spectral=True)
+    assert L.mts_debug_scene_traits(C.byref(desc), C.byref(t)) == 0, L.mts_last_error()
+    desc.integrator.moment = 1
+    assert L.mts_debug_scene_traits(C.byref(desc), C.byref(t)) != 0 and b"moment integrator is not supported in the spectral variant" in L.mts_last_error()
+    d = kr.spectral_cornell(8, 8, 1)
+    d["integrator"] = {"type": "nbins", "wavelengths": "500, 600", "integrator": dict(d["integrator"])}
+    desc, keep = SD.build_scene_desc(d, spectral=True)
+    assert L.mts_debug_scene_traits(C.byref(desc), C.byref(t)) == 0, L.mts_last_error()
+    desc.integrator.moment = 1
+    assert L.mts_debug_scene_traits(C.byref(desc), C.byref(t)) != 0 and b"cannot wrap nbins / bins" in L.mts_last_error()
+
+
+def test_kernel_choice(L, monkeypatch):
+    """mts_stats.kernel_variant of a moment scene: always the general unit (0); the table's row where the moment tail is built into
+    it -- volpath on 1024-path rings, volpathmis on 512-path rings, path as the flat loop -- and the nested moment kernel elsewhere."""
+    for name in kr.SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+
+    def choice(d, **integrator):
+        d = dict(d, integrator=dict(d["integrator"], **integrator))
+        plain = C.c_int32(-1); moment = C.c_int32(-1)
+        desc, keep = SD.build_scene_desc(d)
+        assert L.mts_debug_kernel_choice(C.byref(desc), C.byref(plain)) == 0, L.mts_last_error()
+        desc, keep = SD.build_scene_desc(wrap(d, block_size=d["integrator"]["block_size"]))     # the wrapper's block size is the render's
+        assert L.mts_debug_kernel_choice(C.byref(desc), C.byref(moment)) == 0, L.mts_last_error()
+        return plain.value, moment.value
+
+    c3 = scenes.c3_heterogeneous(64, 64, 4, res=8)
+    assert choice(c3) == (111024, 11024) and choice(c3, type="volpathmis") == (110512, 10512)
+    assert choice(c3, type="volpathmis", use_spectral_mis=False) == (10512, 10512)
+    assert choice(c3, block_size=16) == (10256, 0) and choice(c3, block_size=8) == (1, 0)         # no moment instantiation of these rows: nested
+    box = scenes.c1_cornell(32, 32, 4)
+    assert choice(box) == (400001, 1) and choice(box, type="volpath") == (0, 0)
+    wave = scenes.c3_heterogeneous(64, 64, 4, res=8); wave["sensor"]["sampler"]["wavefront"] = True
+    assert choice(wave) == (11024, 0)                                                             # wavefront streams: nested
+    wave_box = scenes.c1_cornell(32, 32, 4); wave_box["sensor"]["sampler"]["wavefront"] = True
+    assert choice(wave_box)[1] == 0
+    monkeypatch.setenv("MTSAMD_KERNEL", "nested")
+    assert choice(c3)[1] == 0 and choice(box)[1] == 0
+    monkeypatch.setenv("MTSAMD_KERNEL", "flat")
+    assert choice(c3) == (1, 0) and choice(box)[1] == 1
+    monkeypatch.setenv("MTSAMD_KERNEL", "wga256")
+    assert choice(c3) == (10256, 0)
