@@ -79,14 +79,24 @@ PM_HD float pm_invariant_rcp(float d) {
     const uint32_t er = (pm_bits(rd) >> 23) & 0xffu;
     return (d > 0.f && e >= 67u && e <= 187u && er >= 67u && er <= 187u && (b & 0x7fffffu) != 0x7fffffu) ? rd : 0.f;
 }
-PM_HD float pm_div_by_invariant(float x, float d, float rd) {
-    if (rd == 0.f || pm_bits(x) * 2u - 0x41000000u >= 0x7c000000u) return x / d;   // |x| outside [2^-62, 2^62): 2|x|'s bits - 2^-62's
+PM_HD float pm_div_by_invariant_core(float x, float d, float rd) {
     float q = x * rd;
     float r = pm_fma(-q, d, x);
     q = pm_fma(r, rd, q);
     r = pm_fma(-q, d, x);
     q = pm_fma(r, rd, q);
     return q;
+}
+PM_HD float pm_div_by_invariant(float x, float d, float rd) {
+    if (rd == 0.f || pm_bits(x) * 2u - 0x41000000u >= 0x7c000000u) return x / d;   // |x| outside [2^-62, 2^62): 2|x|'s bits - 2^-62's
+    return pm_div_by_invariant_core(x, d, rd);
+}
+// The guard-free form for straight-line code (the tracking step of volpath_flat.h): the same five multiply-adds for every dividend,
+// *ok = the dividend admits them.  The caller has tested rd != 0 (a property of the divisor) and sends a lane whose *ok is false
+// through pm_div_by_invariant instead; the value returned for such a lane is not the quotient.
+PM_HD float pm_div_by_invariant_flag(float x, float d, float rd, bool *ok) {
+    *ok = !(pm_bits(x) * 2u - 0x41000000u >= 0x7c000000u);
+    return pm_div_by_invariant_core(x, d, rd);
 }
 PM_HD float pm_min(float a, float b) { return b < a ? b : a; }   // std::min semantics
 PM_HD float pm_max(float a, float b) { return a < b ? b : a; }   // std::max semantics
@@ -305,6 +315,22 @@ __device__ inline void pm_tables_to_lds(uint32_t) {}      // host pass of a HIP 
 #  define PM_EXP2F_TAB pm_host_exp2f_tab
 #endif
 
+// the arithmetic of pm_log for the bits of a positive normal number
+PM_HD float pm_log_core(uint32_t ix) {
+    // (glibc tests x == 1 first; the arithmetic below returns +0 for it by itself: r = 0, y0 = 0)
+    uint32_t tmp = ix - 0x3f330000u;
+    uint32_t i = (tmp >> 19) & 15u;
+    int k = (int32_t) tmp >> 23;
+    double z = (double) pm_from_bits(ix - (tmp & 0xff800000u));
+    double invc = PM_LOGF_TAB[2 * i], logc = PM_LOGF_TAB[2 * i + 1];
+    double r = pm_fma_d(z, invc, -1.0);
+    double y0 = pm_fma_d((double) k, 0x1.62e42fefa39efp-1, logc);
+    double r2 = r * r;
+    double y = pm_fma_d(0x1.5575b0be00b6ap-2, r, -0x1.ffffef20a4123p-2);
+    y = pm_fma_d(-0x1.00ea348b88334p-2, r2, y);
+    y = pm_fma_d(y, r2, y0 + r);
+    return (float) y;
+}
 // e_logf.c: x = 2^k z, z in [0x1.66p-1, 0x1.66p0) (OFF = 0x3f330000), c near the centre of z's sub-interval;
 // log x = log1p(z / c - 1) + log c + k ln2 with a degree-3 polynomial for log1p(r) - r.
 PM_HD float pm_log(float x) {
@@ -321,19 +347,19 @@ PM_HD float pm_log(float x) {
         if (ix < 0x00800000u) return -pm_inf();           // denormals (DAZ)
         return pm_nan();                                  // negative or NaN
     }
-    // (glibc tests x == 1 first; the arithmetic below returns +0 for it by itself: r = 0, y0 = 0)
-    uint32_t tmp = ix - 0x3f330000u;
-    uint32_t i = (tmp >> 19) & 15u;
-    int k = (int32_t) tmp >> 23;
-    double z = (double) pm_from_bits(ix - (tmp & 0xff800000u));
-    double invc = PM_LOGF_TAB[2 * i], logc = PM_LOGF_TAB[2 * i + 1];
-    double r = pm_fma_d(z, invc, -1.0);
-    double y0 = pm_fma_d((double) k, 0x1.62e42fefa39efp-1, logc);
-    double r2 = r * r;
-    double y = pm_fma_d(0x1.5575b0be00b6ap-2, r, -0x1.ffffef20a4123p-2);
-    y = pm_fma_d(-0x1.00ea348b88334p-2, r2, y);
-    y = pm_fma_d(y, r2, y0 + r);
-    return (float) y;
+    return pm_log_core(ix);
+}
+// pm_log without its branch, for straight-line code: *ok = x is a positive normal number, the one case whose result is the arithmetic
+// alone; the value returned for any other x is not the logarithm (the table index stays inside the table) and the caller sends such
+// a lane through pm_log instead.
+PM_HD float pm_log_flag(float x, bool *ok) {
+#if (defined(PM_USE_LIBM) && !defined(__HIPCC__)) || defined(PM_CORRECTLY_ROUNDED)
+    *ok = true; return pm_log(x);
+#else
+    const uint32_t ix = pm_bits(x);
+    *ok = !(ix - 0x00800000u >= 0x7f000000u);
+    return pm_log_core(ix);
+#endif
 }
 
 // The tail both expf and powf end in (e_expf.c, e_powf.c: exp2_inline): 2^(k/32) from the table, exponent added in place, degree-3
@@ -347,6 +373,17 @@ PM_HD double pm_exp2_tail(uint64_t ki, double r, double c0, double c1, double c2
     return y * s;
 }
 
+// the arithmetic of pm_exp for |x| <= 87.3365402
+PM_HD float pm_exp_core(float x) {
+    double xd = (double) x;
+    double z = 0x1.71547652b82fep+5 * xd;
+    double kd = z + 0x1.8p+52;
+    uint64_t ki = pm_bits_d(kd);
+    kd = kd - 0x1.8p+52;
+    double r = pm_fma_d(0x1.71547652b82fep+5, xd, -kd);   // the FMA build contracts z - kd over the product
+    double y = pm_exp2_tail(ki, r, 0x1.c6af84b912394p-20, 0x1.ebfce50fac4f3p-13, 0x1.62e42ff0c52d6p-6);
+    return y < 1.17549435082228750797e-38 ? 0.0f : (float) y;
+}
 // e_expf.c: x * 32 / ln2 = k + r (round to nearest through the 0x1.8p52 shift), exp x = 2^(k/32) * 2^(r/32).
 // Underflows to +0 below ln(FLT_MIN) (flush-to-zero semantics), overflows to +inf.
 PM_HD float pm_exp(float x) {
@@ -361,14 +398,17 @@ PM_HD float pm_exp(float x) {
         if (x > 88.7228317f) return pm_inf();             // 0x1.62e42ep6f, e_expf.c's overflow bound
         if (x < 0.0f) return 0.0f;                        // below ln(FLT_MIN): glibc returns a denormal here, zero under flush-to-zero
     }
-    double xd = (double) x;
-    double z = 0x1.71547652b82fep+5 * xd;
-    double kd = z + 0x1.8p+52;
-    uint64_t ki = pm_bits_d(kd);
-    kd = kd - 0x1.8p+52;
-    double r = pm_fma_d(0x1.71547652b82fep+5, xd, -kd);   // the FMA build contracts z - kd over the product
-    double y = pm_exp2_tail(ki, r, 0x1.c6af84b912394p-20, 0x1.ebfce50fac4f3p-13, 0x1.62e42ff0c52d6p-6);
-    return y < 1.17549435082228750797e-38 ? 0.0f : (float) y;
+    return pm_exp_core(x);
+}
+// pm_exp without its branch, for straight-line code: *ok = |x| <= 87.3365402 (and not NaN); the value returned for any other x is
+// not the exponential (the table index stays inside the table) and the caller sends such a lane through pm_exp instead.
+PM_HD float pm_exp_flag(float x, bool *ok) {
+#if (defined(PM_USE_LIBM) && !defined(__HIPCC__)) || defined(PM_CORRECTLY_ROUNDED)
+    *ok = true; return pm_exp(x);
+#else
+    *ok = !((pm_bits(x) & 0x7fffffffu) > 0x42aeac4fu);
+    return pm_exp_core(x);
+#endif
 }
 
 // s_sincosf.h: sinf_poly -- the sine (n even) or cosine (n odd) polynomial of glibc's sincos_t; `neg` selects the second table entry

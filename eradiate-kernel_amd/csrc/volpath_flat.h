@@ -65,6 +65,17 @@ enum : uint32_t { S_TOP = 0, S_MED = 1, S_SURF = 2, S_PHASE = 3, S_BSDF = 4, S_D
 enum : uint32_t { M_MAIN = 0, M_NEE = 1, M_DIR = 2 };
 enum : uint32_t { FL_ALIVE = 1, FL_VALID_RAY = 2, FL_SPEC_CHAIN = 4, FL_NEEDS_INT = 8, FL_FROM_MEDIUM = 16 };
 
+// The tracking step of the ring driver as straight-line code (VolpathMachine::step_fast): the units whose media are all of one kind
+// (MT_MEDIA in the rgb / mono build: lean units a, b, c).  Every other unit keeps blk_med + top + classify in wg_block: the spectral
+// units' step evaluates two four-channel spectral grids and divides per channel, the homogeneous unit (h) has no lookup to make
+// unconditional, and the general units choose the medium's kind per step -- a select-committed form of those was not built.
+// -DMTS_STEP_GENERAL: the general step everywhere (A/B measurements).
+#if (MTS_TRAITS & MT_MEDIA) && MTS_SPEC_N == 3 && !defined(MTSAMD_BLOCKSTATS) && !defined(MTS_STEP_GENERAL)
+#define MTS_STEP_FAST 1
+#else
+#define MTS_STEP_FAST 0
+#endif
+
 // Result of one free-flight sample (librender/medium.cpp:34-75); sigma_n is derived by the caller
 // (heterogeneous.cpp:46: combined - sigma_t, homogeneous.cpp:44: 0).
 struct MedStep { float t, mint; F3 p; Spec sigma_t, sigma_s, combined; uint32_t info; float inv_combined /* DMedium::inv_max_density */; };
@@ -732,6 +743,147 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_>, PathState, t
         p.ray.o = mi.p;                                        // scattering position; ray.d stays the incident direction
         p.st = sample_emitters ? S_SCATTER : S_PHASE;
     }
+#if MTS_STEP_FAST
+    // ================================================================= MEDIUM + loop head as straight-line code (ring driver, lean units a / b / c)
+    // blk_med<true, MODEK> followed by top<true> and classify for a path of class B_MED (MODEK 0) or B_MEDW (MODEK 1), where the unit
+    // promises the kind of every medium (MT_MEDIA, rgb / mono: heterogeneous, grey, on a pair grid).  Every such path has st == S_MED,
+    // no pending intersection and the class's mode(s), in the first round (classify put it in the ring) and in every repeat (wg_block
+    // repeats only the lanes that classify sent back here), so none of blk_med's state tests can fail and they are not made.
+    // The arithmetic, its order and the draws are blk_med's and top's; what changes is the control structure: no early return, every lane
+    // runs the same instructions, the grid lookup of a lane without a collision reads the voxels around its ray origin and drops them,
+    // the outcome (escaped / null collision / real collision) picks the new state with selects, and the class follows from the outcome.
+    // What blk_med meets on its uncommon paths makes a lane RARE: a medium whose majorant has no invariant reciprocal (a scalar branch
+    // around the whole form), an argument outside the common range of pm_log / pm_exp / pm_div_by_invariant (their *_flag forms), the
+    // depth limit at a real collision, a walk whose transmittance became zero.  A rare lane commits nothing -- p still holds the state
+    // it came with -- and one wave-uniform branch at the end runs blk_med, top and classify themselves for the rare lanes.  So a lane
+    // either runs the general code, or instructions that are the general code's common path.
+    template <int MODEK, class E> DEV int step_fast(PathState &p, const E &e) const {
+        static_assert(MODEK == 0 || MODEK == 1, "one class of the ring driver");
+        constexpr bool is_main = MODEK == 0;
+        const uint32_t max_depth = (uint32_t) sc.integrator.max_depth, rr_depth = (uint32_t) sc.integrator.rr_depth;
+        Pcg32 rng = p.rng;
+        const float u = rng.next_1d();                         // volpath.cpp:105 / :294 / :391
+        bool rare = false, valid_mi = false, sample_emitters = false;
+        float mint = 0.f, mext = 0.f, rd = 0.f, mi_t = pm_inf(), sig_t = 0.f, sig_s = 0.f;
+        F3 mi_p = f3s(0.f);
+        WATERFALL_BEGIN(p.medium, mu)
+            const DMedium m = cload(sc.media + mu);            // medium_step, pair-grid arm
+            if (m.inv_max_density == 0.f) rare = true;         // wave-uniform: the plain division of div_by_invariant
+            else {
+                float bmint, bmaxt;
+                bool active = bbox_ray_intersect(m.aabb, p.ray, bmint, bmaxt);
+                active = active && (pm_isfinite(bmint) || pm_isfinite(bmaxt));
+                bmint = active ? bmint : 0.f; bmaxt = active ? bmaxt : pm_inf();
+                mint = pm_max(p.ray.mint, bmint);
+                const float maxt = pm_min(p.ray.maxt, bmaxt);
+                mext = m.max_density; rd = m.inv_max_density;
+                bool ok_log, ok_div;
+                const float sampled_t = mint + pm_div_by_invariant_flag(-pm_log_flag(1.f - u, &ok_log), mext, rd, &ok_div);
+                rare = !(ok_log && ok_div);
+                valid_mi = active && (sampled_t <= maxt);
+                mi_t = valid_mi ? sampled_t : pm_inf();
+                mi_p = ray_at(p.ray, sampled_t);
+                const bool look = valid_mi && !rare;           // every other lane looks up the cell of its ray origin: a valid address, value unused
+                const F3 at = f3(look ? mi_p.x : p.ray.o.x, look ? mi_p.y : p.ray.o.y, look ? mi_p.z : p.ray.o.z);
+                const int sx = m.pair_nx < 2 ? 2 : m.pair_nx;
+                const GridCell c = grid_cell_clamp(m.pair_w2l, m.pair_affine & 1, m.pair_nx, m.pair_ny, m.pair_nz, sx, at);
+                float st_raw, al_raw;
+                grid_fetch_pair(as_global(m.pair_grid), c, sx, (m.pair_affine & 2) != 0, st_raw, al_raw);
+                sig_t = m.scale * st_raw;
+                if (is_main) sig_s = sig_t * al_raw;
+                sample_emitters = m.sample_emitters != 0;
+            }
+        WATERFALL_END
+        const float si_t = p.si.t;
+        mi_t = si_t < mi_t ? pm_inf() : mi_t;                  // volpath.cpp:112 / :300 / :397
+        const bool is_nee = !is_main && p.mode == M_NEE;
+        const float remaining_dist = is_nee ? p.ray.maxt : pm_inf();
+        Spec weight = is_main ? p.thr : p.trans;
+        float t = pm_min(mi_t, si_t);
+        if (!is_main) t = is_nee ? pm_min(remaining_dist, t) : t;
+        t = t - mint;
+        const bool surface_first = si_t < mi_t || mi_t > remaining_dist;
+        bool ok_exp;
+        const float tr = pm_exp_flag(-t * mext, &ok_exp);
+        rare = rare || !ok_exp;
+        const float tr_pdf = surface_first ? tr : tr * mext;
+        weight = weight * (tr_pdf > 0.f ? tr * pm_rcp(tr_pdf) : 0.f);
+        float u2 = 0.f;
+        if (is_main) u2 = rng.next_1d();                       // volpath.cpp:123 (drawn even when the medium was left)
+        float wa = p.wa;
+        if (!is_main) {                                        // volpath.cpp:313-315 (a direct-light walk has no bound: both tests fail)
+            wa = (mi_t > remaining_dist && mi_t != pm_inf()) ? p.wb : wa;
+            mi_t = mi_t > remaining_dist ? pm_inf() : mi_t;
+        }
+        const bool valid = mi_t != pm_inf();                   // false: escaped_medium, the surface part of this iteration
+        const float sigma_n = mext - sig_t;
+        int cls;
+        if (is_main) {
+            bool ok_div2;
+            const float ratio = pm_div_by_invariant_flag(sig_t, mext, rd, &ok_div2);
+            const bool real = valid && !(u2 >= ratio);         // real scattering event, volpath.cpp:133-160 -- else a null collision, :128-131,140-144
+            const uint32_t depth1 = p.depth + 1u;
+            rare = rare || (valid && !ok_div2) || (real && !(depth1 < max_depth));
+            const float factor = real ? (sig_s * mext) * pm_rcp(sig_t) : (sigma_n * mext) * pm_rcp(sigma_n);
+            const Spec stepped = weight * factor;
+            Spec thr = f3(valid ? stepped.x : weight.x, valid ? stepped.y : weight.y, valid ? stepped.z : weight.z);
+            // the loop head of a null collision: top(), main arm (volpath.cpp:79-87)
+            bool alive = (p.flags & FL_ALIVE) && any_nonzero(thr);
+            const float q = pm_min(hmax(thr) * (p.eta * p.eta), .95f);
+            const bool perform_rr = p.depth > rr_depth;
+            Pcg32 rng_head = rng;
+            alive = alive && (rng_head.next_1d() < q || !perform_rr);
+            const Spec thr_rr = thr * pm_rcp(q);
+            const bool null_c = valid && !real, rr_c = null_c && perform_rr;
+            const bool ends = !alive || p.depth >= max_depth;
+            thr = f3(rr_c ? thr_rr.x : thr.x, rr_c ? thr_rr.y : thr.y, rr_c ? thr_rr.z : thr.z);
+            const uint32_t fl = p.flags | FL_VALID_RAY;
+            const uint32_t st_real = sample_emitters ? S_SCATTER : S_PHASE, st_null = ends ? S_NEW : S_MED;
+            const int cls_real = sample_emitters ? B_SCATTER : B_PHASE, cls_null = ends ? B_NEW : B_MED;
+            cls = valid ? (real ? cls_real : cls_null) : B_SURF;
+            if (!rare) {                                       // commit
+                if (COUNT) { cnt.n_lookup += valid_mi ? 1u : 0u; cnt.n_iter += (null_c && !ends) ? 1u : 0u; }
+                p.thr = thr;
+                p.rng.state = null_c ? rng_head.state : rng.state;
+                p.ray.o = f3(valid ? mi_p.x : p.ray.o.x, valid ? mi_p.y : p.ray.o.y, valid ? mi_p.z : p.ray.o.z);
+                p.ray.mint = null_c ? 0.f : p.ray.mint;
+                p.si.t = null_c ? si_t - mi_t : si_t;
+                p.depth = real ? depth1 : p.depth;
+                p.flags = real ? (sample_emitters ? (fl & ~FL_SPEC_CHAIN) : (fl | FL_SPEC_CHAIN)) : p.flags;
+                p.st = valid ? (real ? st_real : st_null) : S_SURF;
+            }
+        } else {
+            // a step of a walk, volpath.cpp:322-333 / :411-420, and its loop head: top(), NEE and direct arms (:283-287, :385-388)
+            const Spec stepped = weight * sigma_n;
+            rare = rare || (valid && !any_nonzero(stepped));   // volpath.cpp:358 / :456: the walk is dead
+            const float wa_step = is_nee ? wa + mi_t : wa;
+            const float left = p.wb * (1.f - MTS_SHADOW_EPSILON) - wa_step;
+            const bool ends = is_nee && !(left > 0.f);
+            cls = valid ? (ends ? B_NEW /* classify(S_ENDNEE); wg_block's deferred tail ends the walk */ : B_MEDW) : B_WSURF;
+            if (!rare) {                                       // commit
+                if (COUNT) { cnt.n_lookup += valid_mi ? 1u : 0u; cnt.n_nee_step += (valid && !ends) ? 1u : 0u; }
+                p.trans = f3(valid ? stepped.x : weight.x, valid ? stepped.y : weight.y, valid ? stepped.z : weight.z);
+                p.rng.state = rng.state;
+                p.wa = valid ? wa_step : wa;
+                p.ray.o = f3(valid ? mi_p.x : p.ray.o.x, valid ? mi_p.y : p.ray.o.y, valid ? mi_p.z : p.ray.o.z);
+                p.ray.mint = valid ? 0.f : p.ray.mint;
+                p.ray.maxt = (valid && is_nee) ? left : p.ray.maxt;
+                p.si.t = valid ? si_t - mi_t : si_t;
+                p.st = valid ? (ends ? S_ENDNEE : S_MED) : S_SURF;
+            }
+        }
+        // the one rare path: the general step from the state the lane came with.  Marked unlikely, so that its blocks leave the loop's layout.
+        // (tools/step_loop_stats.py tells the common path from the rare one by the text `__ballot(rare)` of this line.)
+        if (__builtin_expect(__ballot(rare) != 0ull, 0)) {
+            if (rare) {
+                blk_med<true, MODEK>(p, e);
+                top<true>(p, e);
+                cls = Base::classify(p);
+            }
+        }
+        return cls;
+    }
+#endif // MTS_STEP_FAST
     // ================================================================= SCATTER: emitter sampling at a medium interaction
     // (volpath.cpp:162-167 -> sample_emitter :261-281); the walk itself runs as M_NEE steps
     template <class E> DEV void blk_scatter(PathState &p, const E &e) const {
@@ -1190,15 +1342,21 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
     // 546 / 255, from 16 lanes 526 / 255, always 397 / 239.
 #pragma nounroll
     for (int rounds = 0;; ++rounds) {
-        vm.template run<CF::defer, true>(p, e, C);
-        if (COUNT && C == B_MED) MTS_SEG(*cnt, 3);
-        vm.template top<CF::defer>(p, e);
-        if (MTS_FUSE_INT && (C == B_PHASE || C == B_SCATTER || C == B_WSURF || C == B_SURF || C == B_NEW) && a.sc.bvh_node_count == 0) {
-            vm.blk_int(p, e);                                // acts on the lanes whose new ray can reach the scene (wants_int)
-            vm.template top<CF::defer>(p, e);                // start_direct() leaves a direct-light walk at its loop head
+#if MTS_STEP_FAST
+        if constexpr (C == B_MED || C == B_MEDW) cls = vm.template step_fast<C == B_MED ? 0 : 1>(p, e);      // step, loop head and class in one
+        else
+#endif
+        {
+            vm.template run<CF::defer, true>(p, e, C);
+            if (COUNT && C == B_MED) MTS_SEG(*cnt, 3);
+            vm.template top<CF::defer>(p, e);
+            if (MTS_FUSE_INT && (C == B_PHASE || C == B_SCATTER || C == B_WSURF || C == B_SURF || C == B_NEW) && a.sc.bvh_node_count == 0) {
+                vm.blk_int(p, e);                            // acts on the lanes whose new ray can reach the scene (wants_int)
+                vm.template top<CF::defer>(p, e);            // start_direct() leaves a direct-light walk at its loop head
+            }
+            if (COUNT && C == B_MED) MTS_SEG(*cnt, 4);
+            cls = vm.classify(p);
         }
-        if (COUNT && C == B_MED) MTS_SEG(*cnt, 4);
-        cls = vm.classify(p);
         if ((MTS_CHAIN & 16) && C == B_SURF) {                 // the same for the main path (its second visit finds no hit: the sample ends)
             if (cls != C || rounds >= 1) break;
             continue;
@@ -1208,6 +1366,9 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
             continue;
         }
         if (!(C == B_MED || C == B_MEDW) || cls != C || rounds >= 16) break;
+        // tools/step_loop_stats.py finds the repeat loops in the assembly by the text of the next line (`MTS_REPEAT_MIN_W : MTS_REPEAT_MIN`), and
+        // tells B_MED from B_MEDW by the text of the lines that form the roulette probability (`(p.eta * p.eta), .95f)`) and an NEE walk's
+        // remaining distance (`(1.f - MTS_SHADOW_EPSILON) - `) in top() and step_fast: reword those lines and its anchors together.
         if (__popcll(__ballot(true)) < (C == B_MEDW ? MTS_REPEAT_MIN_W : MTS_REPEAT_MIN)) break;
     }
     bool chained = false;
