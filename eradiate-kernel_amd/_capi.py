@@ -167,9 +167,10 @@ def lib():
     L.mts_sample_tea.argtypes = [C.c_int, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), fp]
     L.mts_wavefront_sampler.argtypes = [C.c_int, i32, C.c_uint64, i32, fp]
     L.mts_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Dirty), i32, C.c_void_p]
-    # debug entries (not in the header): the host half of an update, and a hash of the device scene
+    # debug entries (not in the header): the host half of an update, a hash of the device scene, and the same hash of a description's host scene
     L.mts_debug_update_plan.argtypes = [C.POINTER(SceneDesc), C.POINTER(SceneDesc), C.POINTER(Dirty), i32, C.POINTER(i32), C.POINTER(i32)]
     L.mts_debug_scene_digest.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mts_debug_desc_digest.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint64)]
     L.mts_abi_sizeof.argtypes = [C.c_char_p]
     L.mts_abi_sizeof.restype = C.c_int
     if L.mts_abi_version() != MTS_ABI_VERSION:

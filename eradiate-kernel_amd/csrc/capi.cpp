@@ -245,7 +245,18 @@ int mts_debug_scene_digest(mts_scene *scene, uint64_t *out8) {
     API_TRY
     if (!scene || !out8) throw std::runtime_error("mts_debug_scene_digest: NULL argument");
     std::lock_guard<std::mutex> guard(scene->render_mutex);
-    digest_host_scene(*scene->hs, out8);
+    digest_host_scene(*scene->hs, true, out8);
+    API_CATCH
+}
+
+// Not part of the ABI: the same hash of the host scene a description builds, taken from the host's own arrays.  No device is touched, so
+// the CPU test-suite can tell whether a change of the host side altered what the kernels receive (tests/test_host_digest.py).
+int mts_debug_desc_digest(const mts_scene_desc *desc, uint64_t *out8) {
+    API_TRY
+    if (!out8) throw std::runtime_error("mts_debug_desc_digest: out8 is NULL");
+    HostScene *hs = build_host_scene(desc);
+    try { digest_host_scene(*hs, false, out8); } catch (...) { free_host_scene(hs); throw; }
+    free_host_scene(hs);
     API_CATCH
 }
 

@@ -455,158 +455,159 @@ static bool srf_lookup_by_wavelength(const HostScene &hs) {
     return true;
 }
 
-HostScene *build_host_scene(const mts_scene_desc *d) {
-    if (!d) throw std::runtime_error("scene description is NULL");
-    if (d->abi_version != MTS_ABI_VERSION) throw std::runtime_error("scene description: ABI version mismatch");
-    std::unique_ptr<HostScene> hsp(new HostScene());
-    HostScene &hs = *hsp;
-    DScene &sc = hs.scene; memset(&sc, 0, sizeof(sc));
-    const bool spectral = d->integrator.spectral != 0;
-    // ---- spectra (spectral variant; uniform.cpp:34-52, regular.cpp:27-58 + distr_1d.h:318-345)
-    if (spectral) {
-        if (d->integrator.monochrome) throw std::runtime_error("a scene is either monochromatic or spectral");
-        for (int i = 0; i < d->spectrum_count; ++i) {
-            SpectrumArrays arrays;
-            const DSpectrum ds = build_spectrum(d->spectra[i], arrays);
-            hs.spectrum_values.push_back(std::move(arrays.values)); hs.spectrum_wavelengths.push_back(std::move(arrays.wavelengths)); hs.spectrum_cdf.push_back(std::move(arrays.cdf));
-            hs.spectra.push_back(ds);
-        }
+// ---------------------------------------------------------------- sections of a description
+// build_host_scene runs one function per section, in a fixed order: the order decides which of two faults of a description is reported.
+static int32_t spectrum_index(const mts_scene_desc &d, int idx, const char *what) {
+    if (idx < 0 || idx >= d.spectrum_count) throw std::runtime_error(std::string("spectral variant: missing spectrum for ") + what);
+    return idx;
+}
+static void build_spectra(const mts_scene_desc &d, HostScene &hs) {
+    if (d.integrator.monochrome) throw std::runtime_error("a scene is either monochromatic or spectral");
+    for (int i = 0; i < d.spectrum_count; ++i) {
+        SpectrumArrays arrays;
+        hs.spectra.push_back(build_spectrum(d.spectra[i], arrays));
+        hs.spectrum_values.push_back(std::move(arrays.values)); hs.spectrum_wavelengths.push_back(std::move(arrays.wavelengths)); hs.spectrum_cdf.push_back(std::move(arrays.cdf));
     }
-    auto spectrum_index = [&](int idx, const char *what) {
-        if (idx < 0 || idx >= d->spectrum_count) throw std::runtime_error(std::string("spectral variant: missing spectrum for ") + what);
-        return idx;
-    };
-    auto add_uniform_spectrum = [&](float value) {
-        DSpectrum ds; memset(&ds, 0, sizeof(ds)); ds.type = MTS_SPECTRUM_UNIFORM; ds.value = value; ds.lambda_min = 280.f; ds.lambda_max = 2400.f;
-        hs.spectra.push_back(ds); hs.spectrum_values.emplace_back(); hs.spectrum_wavelengths.emplace_back(); hs.spectrum_cdf.emplace_back();
-        return (int32_t) hs.spectra.size() - 1;
-    };
-
-    // ---- volumes (texture.cpp:89-92, texture.h:262-269, grid3d.cpp:137-161, volume_data.h:24-33,86-98)
-    for (int i = 0; i < d->volume_count; ++i) {
-        const mts_volume &v = d->volumes[i];
+}
+static int32_t add_uniform_spectrum(HostScene &hs, float value) {
+    DSpectrum ds; memset(&ds, 0, sizeof(ds)); ds.type = MTS_SPECTRUM_UNIFORM; ds.value = value; ds.lambda_min = 280.f; ds.lambda_max = 2400.f;
+    hs.spectra.push_back(ds); hs.spectrum_values.emplace_back(); hs.spectrum_wavelengths.emplace_back(); hs.spectrum_cdf.emplace_back();
+    return (int32_t) hs.spectra.size() - 1;
+}
+static void build_volumes(const mts_scene_desc &d, bool spectral, HostScene &hs) {
+    for (int i = 0; i < d.volume_count; ++i) {
+        const mts_volume &v = d.volumes[i];
         DVolume dv; DVolumeSp vsp;
-        build_volume(v, spectral, d->spectrum_count, true, nullptr, dv, vsp);
-        hs.volume_sp.push_back(vsp);
+        build_volume(v, spectral, d.spectrum_count, true, nullptr, dv, vsp);
+        hs.volumes.push_back(dv); hs.volume_sp.push_back(vsp);
         if (volume_is_grid(v)) hs.grid_data.emplace_back(v.data, v.data + (size_t) v.nx * v.ny * v.nz * v.channels);
         else hs.grid_data.emplace_back();
-        hs.volumes.push_back(dv);
     }
-    // ---- phase functions (hg.cpp:43-49, tabphase.cpp:33-51, distr_1d.h:293-345, blendphase.cpp:33-56)
-    for (int i = 0; i < d->phase_count; ++i) {
+}
+static void build_phases(const mts_scene_desc &d, HostScene &hs) {
+    for (int i = 0; i < d.phase_count; ++i) {
         hs.tab_pdf.emplace_back(); hs.tab_cdf.emplace_back();
-        const DPhase dp = build_phase(d->phases[i], i, hs.phases, d->phase_count, d->volume_count, hs.tab_pdf.back(), hs.tab_cdf.back());
-        hs.phases.push_back(dp);
+        hs.phases.push_back(build_phase(d.phases[i], i, hs.phases, d.phase_count, d.volume_count, hs.tab_pdf.back(), hs.tab_cdf.back()));
     }
-    // ---- media (medium.cpp:12-29, homogeneous.cpp:21-28, heterogeneous.cpp:21-31)
-    for (int i = 0; i < d->medium_count; ++i) {
-        const mts_medium &m = d->media[i];
-        DMedium dm;
-        std::vector<float> pair;
-        if (build_medium(m, hs, d->volume_count, d->phase_count, spectral, dm))
+}
+static void build_media(const mts_scene_desc &d, bool spectral, HostScene &hs) {
+    for (int i = 0; i < d.medium_count; ++i) {
+        const mts_medium &m = d.media[i];
+        DMedium dm; std::vector<float> pair;
+        if (build_medium(m, hs, d.volume_count, d.phase_count, spectral, dm))
             build_pair_grid(hs.volumes[(size_t) m.sigma_t_volume], hs.grid_data[(size_t) m.sigma_t_volume], hs.grid_data[(size_t) m.albedo_volume], pair);
-        hs.pair_data.push_back(std::move(pair));
-        hs.media.push_back(dm);
+        hs.pair_data.push_back(std::move(pair)); hs.media.push_back(dm);
     }
-    // ---- BSDFs
-    for (int i = 0; i < d->bsdf_count; ++i) {
-        const mts_bsdf &b = d->bsdfs[i];
-        const DBsdf db = build_bsdf(b);
-        hs.bsdfs.push_back(db);
-        if (spectral) {                                                  // which of the six colour parameters each plugin reads
-            for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(BSDF_SP_USED[b.type][k] ? spectrum_index(b.spectrum[k], "a BSDF parameter") : 0);
-        }
+}
+// BSDFs, and the default ones appended after the user's (shape.cpp:74-80): diffuse 0.5, and diffuse 0 for emitters
+struct DefaultBsdfs { int plain, emitter; };
+static DefaultBsdfs build_bsdfs(const mts_scene_desc &d, bool spectral, HostScene &hs) {
+    for (int i = 0; i < d.bsdf_count; ++i) {
+        const mts_bsdf &b = d.bsdfs[i];
+        hs.bsdfs.push_back(build_bsdf(b));
+        if (spectral)                                                    // which of the six colour parameters each plugin reads
+            for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(BSDF_SP_USED[b.type][k] ? spectrum_index(d, b.spectrum[k], "a BSDF parameter") : 0);
     }
-    // default BSDFs appended after the user's (shape.cpp:74-80): diffuse 0.5, and diffuse 0 for emitters
-    DBsdf def; memset(&def, 0, sizeof(def)); def.type = MTS_BSDF_DIFFUSE; def.flags = bsdf_flags(MTS_BSDF_DIFFUSE);
-    def.reflectance[0] = def.reflectance[1] = def.reflectance[2] = .5f;
-    const int default_bsdf = (int) hs.bsdfs.size(); hs.bsdfs.push_back(def);
-    def.reflectance[0] = def.reflectance[1] = def.reflectance[2] = 0.f;
-    const int default_emitter_bsdf = (int) hs.bsdfs.size(); hs.bsdfs.push_back(def);
+    DefaultBsdfs ids; DBsdf def; memset(&def, 0, sizeof(def)); def.type = MTS_BSDF_DIFFUSE; def.flags = bsdf_flags(MTS_BSDF_DIFFUSE);
+    def.reflectance[0] = def.reflectance[1] = def.reflectance[2] = .5f; ids.plain = (int) hs.bsdfs.size(); hs.bsdfs.push_back(def);
+    def.reflectance[0] = def.reflectance[1] = def.reflectance[2] = 0.f; ids.emitter = (int) hs.bsdfs.size(); hs.bsdfs.push_back(def);
     if (spectral) {
-        const int32_t half = add_uniform_spectrum(.5f), zero = add_uniform_spectrum(0.f);
+        const int32_t half = add_uniform_spectrum(hs, .5f), zero = add_uniform_spectrum(hs, 0.f);
         for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(half);
         for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(zero);
     }
-    // ---- shapes + scene bounding box (scene.cpp:31-40)
-    bbox_reset(sc.bbox);
-    for (int i = 0; i < d->shape_count; ++i) {
-        const mts_shape &s = d->shapes[i];
-        check_index(s.bsdf, d->bsdf_count, "shape bsdf", true);
-        check_index(s.interior_medium, d->medium_count, "shape interior", true);
-        check_index(s.exterior_medium, d->medium_count, "shape exterior", true);
-        check_index(s.emitter, d->emitter_count, "shape emitter", true);
-        DBBox sb; int prim_count;
-        DShape ds = build_shape(s, hs, sb, prim_count);
-        if (ds.bsdf < 0) ds.bsdf = ds.emitter >= 0 ? default_emitter_bsdf : default_bsdf;
-        ds.bsdf_type = hs.bsdfs[(size_t) ds.bsdf].type; ds.bsdf_flags = hs.bsdfs[(size_t) ds.bsdf].flags;
-        ds.prim_offset = (int32_t) hs.prims.size();
-        hs.shapes.push_back(ds);
-        bbox_expand(sc.bbox, sb);
-        for (int k = 0; k < prim_count; ++k) {
-            DPrim p; p.shape = i; p.index = k; hs.prims.push_back(p);
-            float rec[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-            if (ds.type == MTS_SHAPE_CUBE || ds.type == MTS_SHAPE_MESH) {        // mesh.h:201-207: p0, e1 = p1 - p0, e2 = p2 - p0
-                const uint32_t *fi = &hs.faces[3 * (ds.face_offset + k)];
-                const float *P = &hs.positions[3 * ds.vertex_offset];
-                F3 p0 = f3(P + 3 * fi[0]), e1 = f3(P + 3 * fi[1]) - p0, e2 = f3(P + 3 * fi[2]) - p0;
-                store3(rec, p0); store3(rec + 3, e1); store3(rec + 6, e2);
+    return ids;
+}
+// one shape of the description: its record, its primitives and their rows in the per-primitive tables; the scene's bounding box grows (scene.cpp:31-40)
+static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaults, HostScene &hs) {
+    const mts_shape &s = d.shapes[i];
+    check_index(s.bsdf, d.bsdf_count, "shape bsdf", true); check_index(s.interior_medium, d.medium_count, "shape interior", true);
+    check_index(s.exterior_medium, d.medium_count, "shape exterior", true); check_index(s.emitter, d.emitter_count, "shape emitter", true);
+    DBBox sb; int prim_count;
+    DShape ds = build_shape(s, hs, sb, prim_count);
+    if (ds.bsdf < 0) ds.bsdf = ds.emitter >= 0 ? defaults.emitter : defaults.plain;
+    ds.bsdf_type = hs.bsdfs[(size_t) ds.bsdf].type; ds.bsdf_flags = hs.bsdfs[(size_t) ds.bsdf].flags;
+    ds.prim_offset = (int32_t) hs.prims.size();
+    hs.shapes.push_back(ds); bbox_expand(hs.scene.bbox, sb);
+    const bool triangles = ds.type == MTS_SHAPE_CUBE || ds.type == MTS_SHAPE_MESH;
+    for (int k = 0; k < prim_count; ++k) {
+        DPrim p; p.shape = i; p.index = k; hs.prims.push_back(p);
+        float rec[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, attr[24] = { 0 };
+        if (triangles) {                                                     // mesh.h:201-207: p0, e1 = p1 - p0, e2 = p2 - p0
+            const uint32_t *fi = &hs.faces[3 * (ds.face_offset + k)];
+            const float *P = &hs.positions[3 * ds.vertex_offset];
+            F3 p0 = f3(P + 3 * fi[0]), e1 = f3(P + 3 * fi[1]) - p0, e2 = f3(P + 3 * fi[2]) - p0;
+            store3(rec, p0); store3(rec + 3, e1); store3(rec + 6, e2);
+            for (int c = 0; c < 3; ++c) {
+                memcpy(attr + 3 * c, &hs.positions[3 * (ds.vertex_offset + fi[c])], 12);
+                memcpy(attr + 9 + 3 * c, &hs.normals[3 * (ds.vertex_offset + fi[c])], 12);
+                memcpy(attr + 18 + 2 * c, &hs.texcoords[2 * (ds.vertex_offset + fi[c])], 8);
             }
-            hs.tri.insert(hs.tri.end(), rec, rec + 9);
-            float attr[24] = { 0 };
-            if (ds.type == MTS_SHAPE_CUBE || ds.type == MTS_SHAPE_MESH) {
-                const uint32_t *fi = &hs.faces[3 * (ds.face_offset + k)];
-                for (int c = 0; c < 3; ++c) {
-                    memcpy(attr + 3 * c, &hs.positions[3 * (ds.vertex_offset + fi[c])], 12);
-                    memcpy(attr + 9 + 3 * c, &hs.normals[3 * (ds.vertex_offset + fi[c])], 12);
-                    memcpy(attr + 18 + 2 * c, &hs.texcoords[2 * (ds.vertex_offset + fi[c])], 8);
-                }
-            }
-            hs.tri_attr.insert(hs.tri_attr.end(), attr, attr + 24);
-            DWalkPrim w; memset(&w, 0, sizeof(w));
-            w.type = ds.type; w.shape = i; w.index = k;
-            if (ds.type == MTS_SHAPE_RECTANGLE || ds.type == MTS_SHAPE_DISK) memcpy(w.f, ds.to_object.m, 48);
-            else if (ds.type == MTS_SHAPE_SPHERE) { memcpy(w.f, ds.center, 12); w.f[3] = ds.radius; }
-            else memcpy(w.f, rec, 36);
-            hs.walk.push_back(w);
-            // mesh.h:108-116: face area
-            hs.area_pmf.push_back((ds.type == MTS_SHAPE_CUBE || ds.type == MTS_SHAPE_MESH) ? 0.5f * norm(cross(f3(rec + 3), f3(rec + 6))) : 0.f);
         }
-        if (ds.type == MTS_SHAPE_CUBE || ds.type == MTS_SHAPE_MESH) {
-            // Mesh::build_pmf (mesh.cpp:285-312) + DiscreteDistribution::update (distr_1d.h:49-83): running sum in double precision
-            DShape &sh = hs.shapes.back();
-            double sum = 0.0; sh.area_lo = sh.area_hi = -1;
-            for (int k = 0; k < prim_count; ++k) {
-                float a = hs.area_pmf[(size_t) sh.prim_offset + k];
-                sum += (double) a; hs.area_cdf.push_back((float) sum);
-                if (a > 0.f) { if (sh.area_lo < 0) sh.area_lo = k; sh.area_hi = k; }
-            }
-            sh.surface_area = (float) sum; sh.inv_surface_area = (float) (1.0 / sum);         // mesh.cpp:346-350,373
-        } else for (int k = 0; k < prim_count; ++k) hs.area_cdf.push_back(0.f);
+        hs.tri.insert(hs.tri.end(), rec, rec + 9); hs.tri_attr.insert(hs.tri_attr.end(), attr, attr + 24);
+        DWalkPrim w; memset(&w, 0, sizeof(w)); w.type = ds.type; w.shape = i; w.index = k;
+        if (ds.type == MTS_SHAPE_RECTANGLE || ds.type == MTS_SHAPE_DISK) memcpy(w.f, ds.to_object.m, 48);
+        else if (ds.type == MTS_SHAPE_SPHERE) { memcpy(w.f, ds.center, 12); w.f[3] = ds.radius; }
+        else memcpy(w.f, rec, 36);
+        hs.walk.push_back(w);
+        hs.area_pmf.push_back(triangles ? 0.5f * norm(cross(f3(rec + 3), f3(rec + 6))) : 0.f);      // mesh.h:108-116: face area
     }
-    // ---- emitters + set_scene (scene.cpp:41-52,95-97; directional.cpp:68-73; constant.cpp:35-39; bbox.h:329-332)
-    sc.environment = -1;
-    build_bvh(hs);
-    F3 center = (f3(sc.bbox.max) + f3(sc.bbox.min)) * .5f;
-    float bsphere_radius = pm_max(MTS_RAY_EPSILON, norm(center - f3(sc.bbox.max)) * (1.f + MTS_RAY_EPSILON));
-    for (int i = 0; i < d->emitter_count; ++i) {
-        const mts_emitter &e = d->emitters[i];
-        const float c3[3] = { center.x, center.y, center.z };
-        const DEmitter de = build_emitter(e, c3, bsphere_radius);
+    if (triangles) {
+        // Mesh::build_pmf (mesh.cpp:285-312) + DiscreteDistribution::update (distr_1d.h:49-83): running sum in double precision
+        DShape &sh = hs.shapes.back();
+        double sum = 0.0; sh.area_lo = sh.area_hi = -1;
+        for (int k = 0; k < prim_count; ++k) {
+            float a = hs.area_pmf[(size_t) sh.prim_offset + k];
+            sum += (double) a; hs.area_cdf.push_back((float) sum);
+            if (a > 0.f) { if (sh.area_lo < 0) sh.area_lo = k; sh.area_hi = k; }
+        }
+        sh.surface_area = (float) sum; sh.inv_surface_area = (float) (1.0 / sum);         // mesh.cpp:346-350,373
+    } else for (int k = 0; k < prim_count; ++k) hs.area_cdf.push_back(0.f);
+}
+// the scene's bounding sphere, which set_scene hands to the emitters and the distant sensors (scene.cpp:95-97, bbox.h:329-332)
+struct BSphere { float center[3], radius; };
+static BSphere scene_bsphere(const DBBox &bbox) {
+    const F3 c = (f3(bbox.max) + f3(bbox.min)) * .5f;
+    return { { c.x, c.y, c.z }, pm_max(MTS_RAY_EPSILON, norm(c - f3(bbox.max)) * (1.f + MTS_RAY_EPSILON)) };
+}
+// emitters (scene.cpp:41-52; directional.cpp:68-73; constant.cpp:35-39)
+static void build_emitters(const mts_scene_desc &d, bool spectral, const BSphere &bsphere, HostScene &hs) {
+    hs.scene.environment = -1;
+    for (int i = 0; i < d.emitter_count; ++i) {
+        const mts_emitter &e = d.emitters[i];
         if (e.type == MTS_EMITTER_AREA) {
-            check_index(e.shape, d->shape_count, "area emitter shape", false);
+            check_index(e.shape, d.shape_count, "area emitter shape", false);
             if ((hs.shapes[e.shape].type == MTS_SHAPE_CUBE || hs.shapes[e.shape].type == MTS_SHAPE_MESH) && hs.shapes[e.shape].area_lo < 0)
                 throw std::runtime_error("DiscreteDistribution: no probability mass found!");   // distr_1d.h:78-79
         } else if (e.type == MTS_EMITTER_CONSTANT) {
-            if (sc.environment >= 0) throw std::runtime_error("Only one environment emitter can be specified per scene.");
-            sc.environment = i;
+            if (hs.scene.environment >= 0) throw std::runtime_error("Only one environment emitter can be specified per scene.");
+            hs.scene.environment = i;
         } else if (e.type != MTS_EMITTER_DIRECTIONAL && e.type != MTS_EMITTER_POINT) throw std::runtime_error("unknown emitter type");
-        hs.emitters.push_back(de);
-        if (spectral) hs.emitter_sp.push_back(spectrum_index(e.radiance_spectrum, "an emitter"));
+        hs.emitters.push_back(build_emitter(e, bsphere.center, bsphere.radius));
+        if (spectral) hs.emitter_sp.push_back(spectrum_index(d, e.radiance_spectrum, "an emitter"));
     }
-    // ---- sensor, film, sampler
-    const mts_sensor &s = d->sensor;
-    DSensor &se = sc.sensor;
+}
+// A sensor's own rectangle, disk or sphere (a distant sensor's target or ray origin), built outside the scene; `refusal`: for any other kind
+static DShape build_sensor_shape(const mts_shape &shape, const std::string &refusal) {
+    HostScene scratch; DBBox sb; int pc;
+    if (shape.type != MTS_SHAPE_RECTANGLE && shape.type != MTS_SHAPE_SPHERE && shape.type != MTS_SHAPE_DISK) throw std::runtime_error(refusal);
+    return build_shape(shape, scratch, sb, pc);
+}
+// The target of distant, distantflux (both "distant", key "ray_target") and mdistant (key "target"): none, a point, or a shape and its area
+static void build_ray_target(const mts_sensor &s, const std::string &name, const char *key, DSensor &se) {
+    se.target_type = s.distant_target_type;
+    memcpy(se.target_point, s.distant_target_point, 12);
+    if (se.target_type == MTS_DISTANT_TARGET_SHAPE) {
+        const DShape &t = se.target_shape = build_sensor_shape(s.distant_target_shape, name + " " + key + " shape must be a rectangle, a disk or a sphere in this backend");
+        se.target_area = t.type == MTS_SHAPE_DISK ? t.surface_area : t.type == MTS_SHAPE_RECTANGLE ? norm(cross(f3(t.frame_s), f3(t.frame_t)))
+                                                                   : 4.f * MTS_PI * t.radius * t.radius;
+    } else if (se.target_type != MTS_DISTANT_TARGET_NONE && se.target_type != MTS_DISTANT_TARGET_POINT)
+        throw std::runtime_error(name + " sensor: unknown " + key + " type");
+}
+// sensor, film, sampler.  Fills hs.rfilter_values and hs.multi_transforms next to the record it returns
+static DSensor build_sensor(const mts_scene_desc &d, const BSphere &bsphere, HostScene &hs) {
+    const mts_sensor &s = d.sensor;
+    DSensor se; memset(&se, 0, sizeof(se));
     se.type = s.type; se.to_world = xf_from_abi(s.to_world);
     se.width = s.film_width; se.height = s.film_height;
     se.crop_x = s.crop_offset[0]; se.crop_y = s.crop_offset[1]; se.crop_w = s.crop_size[0]; se.crop_h = s.crop_size[1];
@@ -618,9 +619,9 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     se.sample_count = s.sample_count; se.seed = s.sampler_seed; se.medium = s.medium; se.shutter_open_time = s.shutter_open_time;
     se.wavefront = s.sampler_wavefront != 0;
     // (mts_render clamps samples_per_pass to sample_count as integrator.cpp:58-65 does: a larger value is one pass as well)
-    if (se.wavefront && d->integrator.samples_per_pass >= 0 && d->integrator.samples_per_pass < s.sample_count)
+    if (se.wavefront && d.integrator.samples_per_pass >= 0 && d.integrator.samples_per_pass < s.sample_count)
         throw std::runtime_error("wavefront streams (mts_sensor.sampler_wavefront): samples_per_pass must cover the whole sample_count (one pass)");
-    check_index(s.medium, d->medium_count, "sensor medium", true);
+    check_index(s.medium, d.medium_count, "sensor medium", true);
     if (s.type == MTS_SENSOR_PERSPECTIVE) {
         se.near_clip = s.near_clip; se.far_clip = s.far_clip;
         float fsx = (float) se.width, fsy = (float) se.height;
@@ -638,26 +639,12 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     } else if (s.type == MTS_SENSOR_DISTANT || s.type == MTS_SENSOR_DISTANTFLUX) {             // distant.cpp:225-297, distantflux.cpp:141-187
         se.direction_type = (se.width == 1 && se.height == 1) ? 0 : (se.height == 1 ? 1 : 2);
         se.flip_directions = s.distant_flip_directions != 0;
-        se.target_type = s.distant_target_type;
-        memcpy(se.target_point, s.distant_target_point, 12);
-        if (se.target_type == MTS_DISTANT_TARGET_SHAPE) {
-            HostScene scratch; DBBox sb; int pc;
-            if (s.distant_target_shape.type != MTS_SHAPE_RECTANGLE && s.distant_target_shape.type != MTS_SHAPE_SPHERE && s.distant_target_shape.type != MTS_SHAPE_DISK)
-                throw std::runtime_error("distant ray_target shape must be a rectangle, a disk or a sphere in this backend");
-            se.target_shape = build_shape(s.distant_target_shape, scratch, sb, pc);
-            se.target_area = se.target_shape.type == MTS_SHAPE_DISK ? se.target_shape.surface_area : se.target_shape.type == MTS_SHAPE_RECTANGLE
-                ? norm(cross(f3(se.target_shape.frame_s), f3(se.target_shape.frame_t)))
-                : 4.f * MTS_PI * se.target_shape.radius * se.target_shape.radius;
-        } else if (se.target_type != MTS_DISTANT_TARGET_NONE && se.target_type != MTS_DISTANT_TARGET_POINT)
-            throw std::runtime_error("distant sensor: unknown ray_target type");
+        build_ray_target(s, "distant", "ray_target", se);
         if (s.distant_origin_type != 0) {                                                      // distant.cpp:280-289, distantflux.cpp:172-184
-            HostScene scratch; DBBox sb; int pc;
-            if (s.distant_origin_shape.type != MTS_SHAPE_RECTANGLE && s.distant_origin_shape.type != MTS_SHAPE_SPHERE && s.distant_origin_shape.type != MTS_SHAPE_DISK)
-                throw std::runtime_error("distant sensor: the ray origin shape must be a rectangle, a disk or a sphere in this backend");
             se.origin_type = 1;
-            se.origin_shape = build_shape(s.distant_origin_shape, scratch, sb, pc);
+            se.origin_shape = build_sensor_shape(s.distant_origin_shape, "distant sensor: the ray origin shape must be a rectangle, a disk or a sphere in this backend");
         }
-        store3(se.bsphere_center, center); se.bsphere_radius = bsphere_radius;
+        memcpy(se.bsphere_center, bsphere.center, 12); se.bsphere_radius = bsphere.radius;
         se.needs_aperture_sample = 1;                                                          // endpoint.h:244
     } else if (s.type == MTS_SENSOR_MRADIANCEMETER || s.type == MTS_SENSOR_MDISTANT) {        // mradiancemeter.cpp:72-132, mdistant.cpp:147-203
         if (s.multi_count <= 0 || s.multi_transforms == nullptr) throw std::runtime_error("multi-sensor: no sub-sensors given");
@@ -667,23 +654,16 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
         se.needs_aperture_sample = s.type == MTS_SENSOR_MDISTANT ? 1 : 0;                        // m_needs_sample_3
         se.target_type = MTS_DISTANT_TARGET_NONE;
         if (s.type == MTS_SENSOR_MDISTANT) {
-            se.target_type = s.distant_target_type;
-            memcpy(se.target_point, s.distant_target_point, 12);
-            if (se.target_type == MTS_DISTANT_TARGET_SHAPE) {
-                HostScene scratch; DBBox sb; int pc;
-                if (s.distant_target_shape.type != MTS_SHAPE_RECTANGLE && s.distant_target_shape.type != MTS_SHAPE_SPHERE && s.distant_target_shape.type != MTS_SHAPE_DISK)
-                    throw std::runtime_error("mdistant target shape must be a rectangle, a disk or a sphere in this backend");
-                se.target_shape = build_shape(s.distant_target_shape, scratch, sb, pc);
-                se.target_area = se.target_shape.type == MTS_SHAPE_DISK ? se.target_shape.surface_area : se.target_shape.type == MTS_SHAPE_RECTANGLE
-                    ? norm(cross(f3(se.target_shape.frame_s), f3(se.target_shape.frame_t)))
-                    : 4.f * MTS_PI * se.target_shape.radius * se.target_shape.radius;
-            } else if (se.target_type != MTS_DISTANT_TARGET_NONE && se.target_type != MTS_DISTANT_TARGET_POINT)
-                throw std::runtime_error("mdistant sensor: unknown target type");
-            store3(se.bsphere_center, center); se.bsphere_radius = bsphere_radius;               // mdistant.cpp:205-210
+            build_ray_target(s, "mdistant", "target", se);
+            memcpy(se.bsphere_center, bsphere.center, 12); se.bsphere_radius = bsphere.radius;   // mdistant.cpp:205-210
         }
     } else throw std::runtime_error("unknown sensor type");
-    // ---- integrator (integrator.cpp:23-39,302-315)
-    const mts_integrator &it = d->integrator;
+    return se;
+}
+// integrator (integrator.cpp:23-39,302-315), the wrappers around it, the film's channels and the sensor's response function
+static void build_integrator(const mts_scene_desc &d, bool spectral, HostScene &hs) {
+    DScene &sc = hs.scene;
+    const mts_integrator &it = d.integrator;
     if (it.type != MTS_INTEGRATOR_PATH && it.type != MTS_INTEGRATOR_VOLPATH && it.type != MTS_INTEGRATOR_VOLPATHMIS) throw std::runtime_error("unknown integrator type");
     if (it.rr_depth <= 0) throw std::runtime_error("\"rr_depth\" must be set to a value greater than zero!");
     if (it.max_depth < 0 && it.max_depth != -1) throw std::runtime_error("\"max_depth\" must be set to -1 (infinite) or a value >= 0");
@@ -716,15 +696,35 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
         sc.bin_mode = it.bin_mode; sc.bin_count = it.bin_count; sc.film_channels = 5 + 2 * it.bin_count;
     } else hs.integrator.bin_count = 0;
     if (it.moment != 0) sc.film_channels = 11;             // X, Y, Z, A, W, then the nested integrator's XYZ and its square (validated above)
-    if (spectral && d->sensor.srf != 0) {
-        if (d->sensor.srf < 0 || d->sensor.srf > d->spectrum_count) throw std::runtime_error("index out of range: sensor srf");
-        if (d->sensor.type != MTS_SENSOR_PERSPECTIVE && !(d->sensor.type == MTS_SENSOR_MRADIANCEMETER && d->sensor.multi_count == 1))
+    if (spectral && d.sensor.srf != 0) {
+        if (d.sensor.srf < 0 || d.sensor.srf > d.spectrum_count) throw std::runtime_error("index out of range: sensor srf");
+        if (d.sensor.type != MTS_SENSOR_PERSPECTIVE && !(d.sensor.type == MTS_SENSOR_MRADIANCEMETER && d.sensor.multi_count == 1))
             throw std::runtime_error("srf: only perspective and radiancemeter sensors sample their wavelengths from a response function");
-        const int t = hs.spectra[(size_t) d->sensor.srf - 1].type;
+        const int t = hs.spectra[(size_t) d.sensor.srf - 1].type;
         if (t != MTS_SPECTRUM_UNIFORM && t != MTS_SPECTRUM_DISCRETE) throw std::runtime_error("srf: sample_spectrum is available for uniform and discrete spectra");
-        sc.srf = d->sensor.srf - 1;
+        sc.srf = d.sensor.srf - 1;
         hs.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs);
     }
+}
+
+HostScene *build_host_scene(const mts_scene_desc *d) {
+    if (!d) throw std::runtime_error("scene description is NULL");
+    if (d->abi_version != MTS_ABI_VERSION) throw std::runtime_error("scene description: ABI version mismatch");
+    std::unique_ptr<HostScene> hsp(new HostScene());
+    HostScene &hs = *hsp; DScene &sc = hs.scene; memset(&sc, 0, sizeof(sc));
+    const bool spectral = d->integrator.spectral != 0;
+    if (spectral) build_spectra(*d, hs);
+    build_volumes(*d, spectral, hs);
+    build_phases(*d, hs);
+    build_media(*d, spectral, hs);
+    const DefaultBsdfs defaults = build_bsdfs(*d, spectral, hs);
+    bbox_reset(sc.bbox);
+    for (int i = 0; i < d->shape_count; ++i) add_shape(*d, i, defaults, hs);
+    build_bvh(hs);
+    const BSphere bsphere = scene_bsphere(sc.bbox);
+    build_emitters(*d, spectral, bsphere, hs);
+    sc.sensor = build_sensor(*d, bsphere, hs);
+    build_integrator(*d, spectral, hs);
     sc.volume_count = (int) hs.volumes.size(); sc.phase_count = (int) hs.phases.size(); sc.medium_count = (int) hs.media.size();
     sc.bsdf_count = (int) hs.bsdfs.size(); sc.shape_count = (int) hs.shapes.size(); sc.prim_count = (int) hs.prims.size();
     sc.emitter_count = (int) hs.emitters.size();
@@ -808,7 +808,7 @@ struct BvhLayout {
 }
 
 void build_bvh(HostScene &hs) {
-    hs.bvh_nodes.clear(); hs.bvh_prims.clear();
+    hs.bvh_nodes.clear(); hs.bvh_prims.clear(); hs.scene.bvh_node_count = 0;
     int threshold = 40;                                                    // at or below this the scalar walk over the list is faster (measured: 31 primitives 584 vs 562 Msamples/s)
     if (const char *e = getenv("MTSAMD_BVH_THRESHOLD")) threshold = atoi(e);
     const int n = (int) hs.prims.size();
@@ -839,6 +839,7 @@ void build_bvh(HostScene &hs) {
     layout.assign(root, MTS_BVH_TOP_DEPTH);
     hs.bvh_nodes.assign(8 * tmp.size(), 0.f);
     layout.emit(root, (int) tmp.size(), 1e-5f * norm(diag) + 1e-7f, hs.bvh_nodes);
+    hs.scene.bvh_node_count = (int32_t) tmp.size();
 }
 
 // ---------------------------------------------------------------- upload
@@ -871,8 +872,7 @@ void upload_host_scene(HostScene &hs, int device) {
     sc.tri = upload(hs, hs.tri);
     sc.tri_attr = upload(hs, hs.tri_attr);
     sc.area_pmf = upload(hs, hs.area_pmf); sc.area_cdf = upload(hs, hs.area_cdf);
-    sc.bvh_nodes = nullptr; sc.bvh_prims = nullptr; sc.bvh_node_count = (int32_t) (hs.bvh_nodes.size() / 8);
-    sc.bvh_lds = nullptr; sc.bvh_lds_count = 0;
+    sc.bvh_nodes = nullptr; sc.bvh_prims = nullptr; sc.bvh_lds = nullptr; sc.bvh_lds_count = 0;
     if (sc.bvh_node_count > 0) { sc.bvh_nodes = upload(hs, hs.bvh_nodes); sc.bvh_prims = upload(hs, hs.bvh_prims); }
     sc.sensor.rfilter.values = upload(hs, hs.rfilter_values);
     sc.sensor.multi = upload(hs, hs.multi_transforms);
@@ -1138,68 +1138,71 @@ void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *
 #endif
 }
 
-// ---------------------------------------------------------------- digest (tests: "the device scene is the fresh one")
+// ---------------------------------------------------------------- digest (tests: "the device scene is the fresh one", "the host scene is the parent's")
 namespace {
 struct Fnv {
     uint64_t h = 1469598103934665603ull;
     void add(const void *p, size_t bytes) { const unsigned char *c = (const unsigned char *) p; for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; } }
+    template <typename T> void add(const std::vector<T> &v) { add(v.data(), v.size() * sizeof(T)); }
 };
+// Where the walk takes an array from: the device's copy (as many elements as the host's vector holds), or the host's vector itself
+struct DigestSource {
+    bool device;
+    template <typename T> std::vector<T> operator()(const T *device_copy, const std::vector<T> &host) const {
+        if (!device) return host;
+        std::vector<T> v(host.size());
 #if !defined(MTSAMD_HOST_ONLY)
-template <typename T> std::vector<T> download(const T *device, size_t count) {
-    std::vector<T> v(count);
-    if (count && device) HIP_CHECK(hipMemcpy(v.data(), device, count * sizeof(T), hipMemcpyDeviceToHost));
-    return v;
-}
+        if (!v.empty() && device_copy) HIP_CHECK(hipMemcpy(v.data(), device_copy, v.size() * sizeof(T), hipMemcpyDeviceToHost));
+#else
+        (void) device_copy;
 #endif
+        return v;
+    }
+};
 } // namespace
 
-void digest_host_scene(HostScene &hs, uint64_t out[8]) {
+void digest_host_scene(HostScene &hs, bool device, uint64_t out[8]) {
     for (int k = 0; k < 8; ++k) out[k] = 0;
+    if (device) {
 #if defined(MTSAMD_HOST_ONLY)
-    throw std::runtime_error("mts_debug_scene_digest: host-only build (no device scene)");
+        throw std::runtime_error("mts_debug_scene_digest: host-only build (no device scene)");
 #else
-    if (!hs.uploaded) throw std::runtime_error("mts_debug_scene_digest: the scene is not in device memory");
-    HIP_CHECK(hipSetDevice(hs.device));
-    HIP_CHECK(hipDeviceSynchronize());
+        if (!hs.uploaded) throw std::runtime_error("mts_debug_scene_digest: the scene is not in device memory");
+        HIP_CHECK(hipSetDevice(hs.device));
+        HIP_CHECK(hipDeviceSynchronize());
+#endif
+    }
+    const DigestSource from{ device };
     const DScene &sc = hs.scene;
-    Fnv rec, grid, pair, tab, spec, head;
-    std::vector<DVolume> volumes = download(sc.volumes, hs.volumes.size());
-    std::vector<DPhase> phases = download(sc.phases, hs.phases.size());
-    std::vector<DMedium> media = download(sc.media, hs.media.size());
-    std::vector<DBsdf> bsdfs = download(sc.bsdfs, hs.bsdfs.size());
-    std::vector<DEmitter> emitters = download(sc.emitters, hs.emitters.size());
-    std::vector<DShape> shapes = download(sc.shapes, hs.shapes.size());
+    Fnv rec, grid, pair, tab, spec, head, geom, sens;
+    std::vector<DVolume> volumes = from(sc.volumes, hs.volumes);
+    std::vector<DPhase> phases = from(sc.phases, hs.phases);
+    std::vector<DMedium> media = from(sc.media, hs.media);
     for (size_t i = 0; i < volumes.size(); ++i) {
         if (volumes[i].data != hs.volumes[i].data) throw std::runtime_error("mts_debug_scene_digest: a volume record points elsewhere than the host's copy");
-        grid.add(download(volumes[i].data, hs.grid_data[i].size()).data(), hs.grid_data[i].size() * sizeof(float));
+        grid.add(from(volumes[i].data, hs.grid_data[i]));
         volumes[i].data = nullptr;
     }
     for (size_t i = 0; i < phases.size(); ++i) {
-        if (phases[i].type == MTS_PHASE_TABULATED) {
-            tab.add(download(phases[i].pdf, hs.tab_pdf[i].size()).data(), hs.tab_pdf[i].size() * sizeof(float));
-            tab.add(download(phases[i].cdf, hs.tab_cdf[i].size()).data(), hs.tab_cdf[i].size() * sizeof(float));
-        }
+        if (phases[i].type == MTS_PHASE_TABULATED) { tab.add(from(phases[i].pdf, hs.tab_pdf[i])); tab.add(from(phases[i].cdf, hs.tab_cdf[i])); }
         phases[i].pdf = phases[i].cdf = nullptr;
     }
     for (size_t i = 0; i < media.size(); ++i) {
-        if (media[i].pair_grid) pair.add(download(media[i].pair_grid, hs.pair_data[i].size()).data(), hs.pair_data[i].size() * sizeof(float));
+        if (!hs.pair_data[i].empty()) pair.add(from(media[i].pair_grid, hs.pair_data[i]));
         media[i].pair_grid = nullptr;
     }
-    rec.add(volumes.data(), volumes.size() * sizeof(DVolume)); rec.add(phases.data(), phases.size() * sizeof(DPhase));
-    rec.add(media.data(), media.size() * sizeof(DMedium)); rec.add(bsdfs.data(), bsdfs.size() * sizeof(DBsdf));
-    rec.add(emitters.data(), emitters.size() * sizeof(DEmitter)); rec.add(shapes.data(), shapes.size() * sizeof(DShape));
+    rec.add(volumes); rec.add(phases); rec.add(media);
+    rec.add(from(sc.bsdfs, hs.bsdfs)); rec.add(from(sc.emitters, hs.emitters)); rec.add(from(sc.shapes, hs.shapes));
     if (hs.integrator.spectral) {
-        std::vector<DSpectrum> spectra = download(sc.spectra, hs.spectra.size());
+        std::vector<DSpectrum> spectra = from(sc.spectra, hs.spectra);
         for (size_t i = 0; i < spectra.size(); ++i) {
-            spec.add(download(spectra[i].values, hs.spectrum_values[i].size()).data(), hs.spectrum_values[i].size() * sizeof(float));
-            spec.add(download(spectra[i].wavelengths, hs.spectrum_wavelengths[i].size()).data(), hs.spectrum_wavelengths[i].size() * sizeof(float));
-            spec.add(download(spectra[i].cdf, hs.spectrum_cdf[i].size()).data(), hs.spectrum_cdf[i].size() * sizeof(float));
+            spec.add(from(spectra[i].values, hs.spectrum_values[i]));
+            spec.add(from(spectra[i].wavelengths, hs.spectrum_wavelengths[i]));
+            spec.add(from(spectra[i].cdf, hs.spectrum_cdf[i]));
             spectra[i].values = spectra[i].wavelengths = spectra[i].cdf = nullptr;
         }
-        spec.add(spectra.data(), spectra.size() * sizeof(DSpectrum));
-        spec.add(download(sc.bsdf_sp, hs.bsdf_sp.size()).data(), hs.bsdf_sp.size() * sizeof(int32_t));
-        spec.add(download(sc.emitter_sp, hs.emitter_sp.size()).data(), hs.emitter_sp.size() * sizeof(int32_t));
-        spec.add(download(sc.volume_sp, hs.volume_sp.size()).data(), hs.volume_sp.size() * sizeof(DVolumeSp));
+        spec.add(spectra);
+        spec.add(from(sc.bsdf_sp, hs.bsdf_sp)); spec.add(from(sc.emitter_sp, hs.emitter_sp)); spec.add(from(sc.volume_sp, hs.volume_sp));
     }
     DScene h = sc;                                         // the kernel argument: its scalars, every pointer zeroed
     h.volumes = nullptr; h.phases = nullptr; h.media = nullptr; h.bsdfs = nullptr; h.shapes = nullptr; h.prims = nullptr; h.walk = nullptr; h.emitters = nullptr;
@@ -1209,8 +1212,14 @@ void digest_host_scene(HostScene &hs, uint64_t out[8]) {
     head.add(&h, sizeof(h));
     const int32_t tail[2] = { hs.traits, hs.srf_lookup_by_wavelength ? 1 : 0 };
     head.add(tail, sizeof(tail));
-    out[0] = rec.h; out[1] = grid.h; out[2] = pair.h; out[3] = tab.h; out[4] = spec.h; out[5] = head.h;
-#endif
+    geom.add(from(sc.prims, hs.prims)); geom.add(from(sc.walk, hs.walk));
+    geom.add(from(sc.positions, hs.positions)); geom.add(from(sc.normals, hs.normals)); geom.add(from(sc.texcoords, hs.texcoords));
+    geom.add(from(sc.faces, hs.faces)); geom.add(from(sc.tri, hs.tri)); geom.add(from(sc.tri_attr, hs.tri_attr));
+    geom.add(from(sc.area_pmf, hs.area_pmf)); geom.add(from(sc.area_cdf, hs.area_cdf));
+    geom.add(from(sc.bvh_nodes, hs.bvh_nodes)); geom.add(from(sc.bvh_prims, hs.bvh_prims));
+    sens.add(from(sc.sensor.rfilter.values, hs.rfilter_values)); sens.add(from(sc.sensor.multi, hs.multi_transforms));
+    sens.add(from(sc.bin_lo, hs.bin_lo)); sens.add(from(sc.bin_hi, hs.bin_hi));
+    out[0] = rec.h; out[1] = grid.h; out[2] = pair.h; out[3] = tab.h; out[4] = spec.h; out[5] = head.h; out[6] = geom.h; out[7] = sens.h;
 }
 
 } // namespace mtsamd

@@ -57,8 +57,11 @@ void free_host_scene(HostScene *hs);
 // scene_traits.  Validates everything before it writes (throws std::runtime_error with the scene untouched).  An uploaded scene is
 // rewritten in place on `stream` (grid statistics and pair grids by grid_update_kernel); a host-only scene through the host functions.
 void update_host_scene(HostScene &hs, const mts_scene_desc *desc, const mts_dirty *dirty, int32_t n, hipStream_t stream);
-// FNV-1a over the device scene's contents, pointer fields zeroed: [0] record arrays, [1] grid data, [2] pair grids, [3] phase tables,
-// [4] spectra, [5] traits and the scalar header of DScene, [6..7] 0
-void digest_host_scene(HostScene &hs, uint64_t out[8]);
+// FNV-1a over the scene's contents, pointer fields zeroed: [0] record arrays, [1] grid data, [2] pair grids, [3] phase tables,
+// [4] spectra, [5] traits and the scalar header of DScene, [6] geometry (prims, walk, vertex and triangle tables, area tables, BVH),
+// [7] the sensor's and the bins' arrays (filter table, sub-sensor matrices, bin bounds).  One walk, two sources: `device` reads the
+// uploaded copy back (throws for a scene that is not in device memory), otherwise the walk reads HostScene's own vectors -- no
+// device is touched, and a fresh scene gives the same eight words either way.
+void digest_host_scene(HostScene &hs, bool device, uint64_t out[8]);
 
 } // namespace mtsamd

@@ -402,6 +402,7 @@ def _tab_values(vals):
 
 
 SHAPE_PLUGINS = ("rectangle", "cube", "sphere", "mesh", "obj", "ply", "disk")
+SAMPLING_INTEGRATORS = {"path": A.INTEGRATOR_PATH, "volpath": A.INTEGRATOR_VOLPATH, "volpathmis": A.INTEGRATOR_VOLPATHMIS}
 
 
 class SceneBuilder:
@@ -833,17 +834,28 @@ class SceneBuilder:
         p = Props(d, where)
         s = A.Sensor()
         s.medium = -1
-        s.distant_target_shape.bsdf = s.distant_target_shape.interior_medium = -1
-        s.distant_target_shape.exterior_medium = s.distant_target_shape.emitter = -1
-        s.distant_origin_shape.bsdf = s.distant_origin_shape.interior_medium = -1
-        s.distant_origin_shape.exterior_medium = s.distant_origin_shape.emitter = -1
-        # film (src/librender/film.cpp:14-50, src/films/hdrfilm.cpp)
-        fd = p.get("film", {"type": "hdrfilm"})
-        fp_ = Props(fd, where + ".film")
+        for shape in (s.distant_target_shape, s.distant_origin_shape):
+            shape.bsdf = shape.interior_medium = shape.exterior_medium = shape.emitter = -1
+        self._film(p, s, where)
+        self._sampler(p, s, where)
+        shutter_open, shutter_close = float(p.get("shutter_open", 0.0)), float(p.get("shutter_close", 0.0))      # sensor.cpp:20-27
+        if shutter_close < shutter_open:
+            raise RuntimeError("Shutter opening time must be less than or equal to the shutter closing time!")
+        s.shutter_open_time = shutter_close - shutter_open
+        if p.has("medium"):
+            s.medium = self.add_medium(p.get("medium"), where + ".medium")
+        if p.type not in SENSOR_PLUGINS:
+            raise RuntimeError("Unknown / unsupported sensor plugin \"%s\"" % p.type)
+        SENSOR_PLUGINS[p.type](self, p, s, where)
+        p.finish()
+        self.sensor = s
+
+    def _film(self, p, s, where):
+        """film (src/librender/film.cpp:14-50, src/films/hdrfilm.cpp) and its reconstruction filter"""
+        fp_ = Props(p.get("film", {"type": "hdrfilm"}), where + ".film")
         if fp_.type != "hdrfilm":
             raise RuntimeError("Unknown / unsupported film plugin \"%s\"" % fp_.type)
-        s.film_width = int(fp_.get("width", 768))
-        s.film_height = int(fp_.get("height", 576))
+        s.film_width, s.film_height = int(fp_.get("width", 768)), int(fp_.get("height", 576))
         s.crop_offset[:] = (int(fp_.get("crop_offset_x", 0)), int(fp_.get("crop_offset_y", 0)))
         s.crop_size[:] = (int(fp_.get("crop_width", s.film_width)), int(fp_.get("crop_height", s.film_height)))
         if (s.crop_offset[0] < 0 or s.crop_offset[1] < 0 or s.crop_size[0] <= 0 or s.crop_size[1] <= 0 or
@@ -865,8 +877,7 @@ class SceneBuilder:
             pf = "rgb"                                                     # hdrfilm.cpp:153-176
         self.film_pixel_format = "luminance" if _MONO else pf             # hdrfilm.cpp:122-128
         fp_.get("high_quality_edges"); fp_.get("filename")
-        rf = fp_.get("rfilter", {"type": "gaussian"})
-        rp = Props(rf, where + ".film.rfilter")
+        rp = Props(fp_.get("rfilter", {"type": "gaussian"}), where + ".film.rfilter")
         s.rfilter_radius, s.rfilter_stddev = 0.5, 0.5
         if rp.type == "box":
             s.rfilter_type = A.RFILTER_BOX
@@ -878,173 +889,153 @@ class SceneBuilder:
             raise RuntimeError("Unknown / unsupported reconstruction filter plugin \"%s\"" % rp.type)
         rp.finish()
         fp_.finish()
-        # sampler (src/librender/sensor.cpp:44-49, src/librender/sampler.cpp:11-18)
-        sd = p.get("sampler", {"type": "independent", "sample_count": 4})
-        sp = Props(sd, where + ".sampler")
+
+    def _sampler(self, p, s, where):
+        """sampler (src/librender/sensor.cpp:44-49, src/librender/sampler.cpp:11-18)"""
+        sp = Props(p.get("sampler", {"type": "independent", "sample_count": 4}), where + ".sampler")
         if sp.type != "independent":
             raise RuntimeError("Unknown / unsupported sampler plugin \"%s\" (parity target is 'independent')" % sp.type)
-        s.sample_count = int(sp.get("sample_count", 4))
-        s.sampler_seed = int(sp.get("seed", 0))
+        s.sample_count, s.sampler_seed = int(sp.get("sample_count", 4)), int(sp.get("seed", 0))
         # Extension of this backend (the reference picks the seeding by variant): "wavefront": True gives the streams of the gpu_* variants --
         # one TEA-seeded PCG32 per (pixel, sample), librender/sampler.cpp:89-92 -- instead of scalar_rgb's one stream per pixel
         s.sampler_wavefront = int(bool(sp.get("wavefront", False)))
         sp.finish()
-        shutter_open, shutter_close = float(p.get("shutter_open", 0.0)), float(p.get("shutter_close", 0.0))      # sensor.cpp:20-27
-        if shutter_close < shutter_open:
-            raise RuntimeError("Shutter opening time must be less than or equal to the shutter closing time!")
-        s.shutter_open_time = shutter_close - shutter_open
-        if p.has("medium"):
-            s.medium = self.add_medium(p.get("medium"), where + ".medium")
-        if p.type == "perspective":
-            s.type = A.SENSOR_PERSPECTIVE
-            tw = p.get("to_world")
-            tw = ScalarTransform4f() if tw is None else tw
-            m = tw.matrix[:3, :3].astype(np.float64)
-            if np.any(np.abs(m @ m.T - np.eye(3)) > 1e-3):                 # transform.h:300-312, perspective.cpp:85-86
-                raise RuntimeError("Scale factors in the camera-to-world transformation are not allowed!")
-            s.to_world = _xf(tw)
-            s.near_clip = float(p.get("near_clip", 1e-2))
-            s.far_clip = float(p.get("far_clip", 1e4))
-            p.get("focus_distance")
-            self._srf(p, s, where)                                         # perspective.cpp:113-121
-            if s.near_clip <= 0:
-                raise RuntimeError("The 'near_clip' parameter must be greater than zero!")
-            if s.far_clip <= s.near_clip:
-                raise RuntimeError("The 'far_clip' parameter must be greater than 'near_clip'.")
-            s.fov_x = parse_fov(p, s.film_width / float(s.film_height))
-            s.principal_point_offset[:] = (float(p.get("principal_point_offset_x", 0.0)),
-                                           float(p.get("principal_point_offset_y", 0.0)))
-        elif p.type == "distant":
-            s.type = A.SENSOR_DISTANT
-            if p.has("direction"):                                         # distant.cpp:243-259
-                if p.has("to_world"):
-                    raise RuntimeError("Only one of the parameters 'direction' and 'to_world'can be specified at the same time!'")
-                direction = np.asarray(p.get("direction"), dtype=np.float32)
-                direction = normalize32(direction)
-                if p.has("orientation"):
-                    up = np.cross(direction, np.asarray(p.get("orientation"), dtype=np.float32)).astype(np.float32)
-                    up = normalize32(up)
-                else:
-                    _, up = coordinate_system(direction)
-                s.to_world = _xf(ScalarTransform4f.look_at([0, 0, 0], direction, up))
-            else:
-                s.to_world = _xf(p.get("to_world"))
-            s.distant_flip_directions = int(bool(p.get("flip_directions", False)))
-            s.distant_target_type = A.DISTANT_TARGET_NONE
-            if p.has("ray_target"):
-                rt = p.get("ray_target")
-                if isinstance(rt, dict):
-                    s.distant_target_type = A.DISTANT_TARGET_SHAPE
-                    rec, _ = self.make_shape(rt, where + ".ray_target", in_scene=False)
-                    s.distant_target_shape = rec
-                else:
-                    s.distant_target_type = A.DISTANT_TARGET_POINT
-                    s.distant_target_point[:] = tuple(float(x) for x in np.asarray(rt, dtype=np.float32))
-            if p.has("ray_origin"):                                         # distant.cpp:280-289
-                ro = p.get("ray_origin")
-                if not isinstance(ro, dict) or ro.get("type") not in SHAPE_PLUGINS:
-                    raise RuntimeError("Invalid parameter ray_origin, must be a Shape.")
-                s.distant_origin_type = 1
-                rec, _ = self.make_shape(ro, where + ".ray_origin", in_scene=False)
-                s.distant_origin_shape = rec
-        elif p.type == "radiancemeter":
-            # src/sensors/radiancemeter.cpp:60-98: one ray along +z of to_world (or of look_at(origin, origin + direction)); it is the
-            # one-sub-sensor case of mradiancemeter (same ray arithmetic, :124-127 vs mradiancemeter.cpp:150-153)
-            s.type = A.SENSOR_MRADIANCEMETER
-            self._srf(p, s, where)                                         # radiancemeter.cpp:61-68
-            if p.has("to_world"):
-                p.get("direction"); p.get("origin")
-                m = p.get("to_world").matrix
-            else:
-                if p.has("direction") != p.has("origin"):
-                    raise RuntimeError("If the sensor is specified through origin and direction both values must be set!")
-                if p.has("direction"):
-                    origin = np.asarray(p.get("origin"), dtype=np.float32)
-                    direction = np.asarray(p.get("direction"), dtype=np.float32)
-                    up, _ = coordinate_system(direction)
-                    m = ScalarTransform4f.look_at(origin, (origin + direction).astype(np.float32), up).matrix
-                else:
-                    m = ScalarTransform4f().matrix
-            if (s.film_width, s.film_height) != (1, 1):
-                raise RuntimeError("This sensor only supports films of size 1x1 Pixels!")
-            buf = np.ascontiguousarray(np.asarray(m, dtype=np.float32).reshape(-1))
-            self.keep.append(buf)
-            s.multi_transforms = buf.ctypes.data_as(C.POINTER(C.c_float))
-            s.multi_count = 1
-            s.to_world = _xf(ScalarTransform4f())
-            s.distant_target_type = A.DISTANT_TARGET_NONE
-        elif p.type == "distantflux":                                      # src/sensors/distantflux.cpp:60-105,141-187
-            s.type = A.SENSOR_DISTANTFLUX
-            tw = p.get("to_world")
-            s.to_world = _xf(ScalarTransform4f() if tw is None else tw)
-            s.distant_target_type = A.DISTANT_TARGET_NONE
-            if p.has("target"):
-                tg = p.get("target")
-                if isinstance(tg, dict):
-                    s.distant_target_type = A.DISTANT_TARGET_SHAPE
-                    rec, _ = self.make_shape(tg, where + ".target", in_scene=False)
-                    s.distant_target_shape = rec
-                else:
-                    s.distant_target_type = A.DISTANT_TARGET_POINT
-                    s.distant_target_point[:] = tuple(float(x) for x in np.asarray(tg, dtype=np.float32))
-            if p.has("origin"):                                             # distantflux.cpp:172-184
-                ro = p.get("origin")
-                if not isinstance(ro, dict) or ro.get("type") not in SHAPE_PLUGINS:
-                    raise RuntimeError("Invalid parameter origin, must be a Shape.")
-                s.distant_origin_type = 1
-                rec, _ = self.make_shape(ro, where + ".origin", in_scene=False)
-                s.distant_origin_shape = rec
-        elif p.type in ("mradiancemeter", "mdistant"):
-            # src/sensors/mradiancemeter.cpp:72-132 / src/sensors/mdistant.cpp:60-98,147-203: N sub-sensors, one per film column
-            multi = p.type == "mradiancemeter"
-            s.type = A.SENSOR_MRADIANCEMETER if multi else A.SENSOR_MDISTANT
-            if multi and p.has("to_world"):
-                raise RuntimeError("This sensor is specified through a set of origin and direction values and cannot use the to_world transform.")
 
-            def tokens(key):                                                   # string::tokenize(props.string(key), " ,")
-                return [t for t in str(p.get(key)).replace(",", " ").split() if t]
-            dirs = tokens("directions")
-            if len(dirs) % 3 != 0:
-                raise RuntimeError("Invalid specification! Number of parameters %d, is not a multiple of three." % len(dirs))
-            count = len(dirs) // 3
-            mats = np.zeros((count, 4, 4), dtype=np.float32)
-            if multi:
-                origs = tokens("origins")
-                if len(origs) % 3 != 0:
-                    raise RuntimeError("Invalid specification! Number of parameters %d, is not a multiple of three." % len(origs))
-                if len(origs) != len(dirs):
-                    raise RuntimeError("Invalid specification! Number of parameters for origins and directions (%d, %d) are not equal."
-                                       % (len(origs), len(dirs)))
-            for i in range(count):
-                direction = np.array([np.float32(x) for x in dirs[3 * i:3 * i + 3]], dtype=np.float32)    # std::stof
-                if multi:
-                    origin = np.array([np.float32(x) for x in origs[3 * i:3 * i + 3]], dtype=np.float32)
-                    up, _ = coordinate_system(direction)                                               # mradiancemeter.cpp:109: first vector
-                    mats[i] = ScalarTransform4f.look_at(origin, (origin + direction).astype(np.float32), up).matrix
-                else:
-                    _, up = coordinate_system(direction)                                               # mdistant.cpp:166-167: second vector
-                    mats[i] = ScalarTransform4f.look_at([0, 0, 0], direction, up).matrix
-            if (s.film_width, s.film_height) != (count, 1):
-                raise RuntimeError("Film size must be [sensor_count, 1]. Expected [%d, 1], got [%d, %d]" % (count, s.film_width, s.film_height))
-            buf = np.ascontiguousarray(mats.reshape(-1), dtype=np.float32)
-            self.keep.append(buf)
-            s.multi_transforms = buf.ctypes.data_as(C.POINTER(C.c_float))
-            s.multi_count = count
-            s.to_world = _xf(ScalarTransform4f())
-            s.distant_target_type = A.DISTANT_TARGET_NONE
-            if not multi and p.has("target"):                                  # mdistant.cpp:71-88,188-198
-                tg = p.get("target")
-                if isinstance(tg, dict):
-                    s.distant_target_type = A.DISTANT_TARGET_SHAPE
-                    rec, _ = self.make_shape(tg, where + ".target", in_scene=False)
-                    s.distant_target_shape = rec
-                else:
-                    s.distant_target_type = A.DISTANT_TARGET_POINT
-                    s.distant_target_point[:] = tuple(float(x) for x in np.asarray(tg, dtype=np.float32))
+    def _ray_target(self, p, key, s, where):
+        """`ray_target` of distant, `target` of distantflux and mdistant: a shape (a dictionary) or a point"""
+        s.distant_target_type = A.DISTANT_TARGET_NONE
+        if not p.has(key):
+            return
+        target = p.get(key)
+        if isinstance(target, dict):
+            s.distant_target_type = A.DISTANT_TARGET_SHAPE
+            s.distant_target_shape, _ = self.make_shape(target, where + "." + key, in_scene=False)
         else:
-            raise RuntimeError("Unknown / unsupported sensor plugin \"%s\"" % p.type)
-        p.finish()
-        self.sensor = s
+            s.distant_target_type = A.DISTANT_TARGET_POINT
+            s.distant_target_point[:] = tuple(float(x) for x in np.asarray(target, dtype=np.float32))
+
+    def _ray_origin(self, p, key, s, where):
+        """`ray_origin` of distant (distant.cpp:280-289), `origin` of distantflux (distantflux.cpp:172-184): a shape the rays start from"""
+        if not p.has(key):
+            return
+        origin = p.get(key)
+        if not isinstance(origin, dict) or origin.get("type") not in SHAPE_PLUGINS:
+            raise RuntimeError("Invalid parameter %s, must be a Shape." % key)
+        s.distant_origin_type = 1
+        s.distant_origin_shape, _ = self.make_shape(origin, where + "." + key, in_scene=False)
+
+    def _multi_transforms(self, s, mats):
+        """The sub-sensors of radiancemeter / mradiancemeter / mdistant: a (count, 4, 4) float32 array of their to_world matrices"""
+        buf = np.ascontiguousarray(mats.reshape(-1), dtype=np.float32)
+        self.keep.append(buf)
+        s.multi_transforms = buf.ctypes.data_as(C.POINTER(C.c_float))
+        s.multi_count = mats.shape[0]
+        s.to_world = _xf(ScalarTransform4f())
+        s.distant_target_type = A.DISTANT_TARGET_NONE
+
+    def _perspective(self, p, s, where):
+        s.type = A.SENSOR_PERSPECTIVE
+        tw = p.get("to_world")
+        tw = ScalarTransform4f() if tw is None else tw
+        m = tw.matrix[:3, :3].astype(np.float64)
+        if np.any(np.abs(m @ m.T - np.eye(3)) > 1e-3):                 # transform.h:300-312, perspective.cpp:85-86
+            raise RuntimeError("Scale factors in the camera-to-world transformation are not allowed!")
+        s.to_world = _xf(tw)
+        s.near_clip = float(p.get("near_clip", 1e-2))
+        s.far_clip = float(p.get("far_clip", 1e4))
+        p.get("focus_distance")
+        self._srf(p, s, where)                                         # perspective.cpp:113-121
+        if s.near_clip <= 0:
+            raise RuntimeError("The 'near_clip' parameter must be greater than zero!")
+        if s.far_clip <= s.near_clip:
+            raise RuntimeError("The 'far_clip' parameter must be greater than 'near_clip'.")
+        s.fov_x = parse_fov(p, s.film_width / float(s.film_height))
+        s.principal_point_offset[:] = (float(p.get("principal_point_offset_x", 0.0)), float(p.get("principal_point_offset_y", 0.0)))
+
+    def _distant(self, p, s, where):
+        s.type = A.SENSOR_DISTANT
+        if p.has("direction"):                                         # distant.cpp:243-259
+            if p.has("to_world"):
+                raise RuntimeError("Only one of the parameters 'direction' and 'to_world'can be specified at the same time!'")
+            direction = normalize32(np.asarray(p.get("direction"), dtype=np.float32))
+            if p.has("orientation"):
+                up = normalize32(np.cross(direction, np.asarray(p.get("orientation"), dtype=np.float32)).astype(np.float32))
+            else:
+                _, up = coordinate_system(direction)
+            s.to_world = _xf(ScalarTransform4f.look_at([0, 0, 0], direction, up))
+        else:
+            s.to_world = _xf(p.get("to_world"))
+        s.distant_flip_directions = int(bool(p.get("flip_directions", False)))
+        self._ray_target(p, "ray_target", s, where)
+        self._ray_origin(p, "ray_origin", s, where)
+
+    def _radiancemeter(self, p, s, where):
+        # src/sensors/radiancemeter.cpp:60-98: one ray along +z of to_world (or of look_at(origin, origin + direction)); it is the
+        # one-sub-sensor case of mradiancemeter (same ray arithmetic, :124-127 vs mradiancemeter.cpp:150-153)
+        s.type = A.SENSOR_MRADIANCEMETER
+        self._srf(p, s, where)                                         # radiancemeter.cpp:61-68
+        if p.has("to_world"):
+            p.get("direction"); p.get("origin")
+            m = p.get("to_world").matrix
+        else:
+            if p.has("direction") != p.has("origin"):
+                raise RuntimeError("If the sensor is specified through origin and direction both values must be set!")
+            if p.has("direction"):
+                origin = np.asarray(p.get("origin"), dtype=np.float32)
+                direction = np.asarray(p.get("direction"), dtype=np.float32)
+                up, _ = coordinate_system(direction)
+                m = ScalarTransform4f.look_at(origin, (origin + direction).astype(np.float32), up).matrix
+            else:
+                m = ScalarTransform4f().matrix
+        if (s.film_width, s.film_height) != (1, 1):
+            raise RuntimeError("This sensor only supports films of size 1x1 Pixels!")
+        self._multi_transforms(s, np.asarray(m, dtype=np.float32).reshape(1, 4, 4))
+
+    def _distantflux(self, p, s, where):                               # src/sensors/distantflux.cpp:60-105,141-187
+        s.type = A.SENSOR_DISTANTFLUX
+        tw = p.get("to_world")
+        s.to_world = _xf(ScalarTransform4f() if tw is None else tw)
+        self._ray_target(p, "target", s, where)
+        self._ray_origin(p, "origin", s, where)
+
+    def _sub_sensors(self, p, s, with_origins):
+        """src/sensors/mradiancemeter.cpp:72-132 / src/sensors/mdistant.cpp:60-98,147-203: N sub-sensors, one per film column"""
+        def tokens(key):                                                   # string::tokenize(props.string(key), " ,")
+            return [t for t in str(p.get(key)).replace(",", " ").split() if t]
+        dirs = tokens("directions")
+        if len(dirs) % 3 != 0:
+            raise RuntimeError("Invalid specification! Number of parameters %d, is not a multiple of three." % len(dirs))
+        count = len(dirs) // 3
+        mats = np.zeros((count, 4, 4), dtype=np.float32)
+        if with_origins:
+            origs = tokens("origins")
+            if len(origs) % 3 != 0:
+                raise RuntimeError("Invalid specification! Number of parameters %d, is not a multiple of three." % len(origs))
+            if len(origs) != len(dirs):
+                raise RuntimeError("Invalid specification! Number of parameters for origins and directions (%d, %d) are not equal." % (len(origs), len(dirs)))
+        for i in range(count):
+            direction = np.array([np.float32(x) for x in dirs[3 * i:3 * i + 3]], dtype=np.float32)    # std::stof
+            if with_origins:
+                origin = np.array([np.float32(x) for x in origs[3 * i:3 * i + 3]], dtype=np.float32)
+                up, _ = coordinate_system(direction)                                               # mradiancemeter.cpp:109: first vector
+                mats[i] = ScalarTransform4f.look_at(origin, (origin + direction).astype(np.float32), up).matrix
+            else:
+                _, up = coordinate_system(direction)                                               # mdistant.cpp:166-167: second vector
+                mats[i] = ScalarTransform4f.look_at([0, 0, 0], direction, up).matrix
+        if (s.film_width, s.film_height) != (count, 1):
+            raise RuntimeError("Film size must be [sensor_count, 1]. Expected [%d, 1], got [%d, %d]" % (count, s.film_width, s.film_height))
+        self._multi_transforms(s, mats)
+
+    def _mradiancemeter(self, p, s, where):
+        s.type = A.SENSOR_MRADIANCEMETER
+        if p.has("to_world"):
+            raise RuntimeError("This sensor is specified through a set of origin and direction values and cannot use the to_world transform.")
+        self._sub_sensors(p, s, True)
+
+    def _mdistant(self, p, s, where):
+        s.type = A.SENSOR_MDISTANT
+        self._sub_sensors(p, s, False)
+        self._ray_target(p, "target", s, where)                         # mdistant.cpp:71-88,188-198
 
     def _srf(self, p, s, where):
         """"srf" of perspective / radiancemeter: the spectral response function the wavelengths are sampled from.  Outside the spectral
@@ -1061,95 +1052,96 @@ class SceneBuilder:
     # ------------------------------------------------------------ integrator
     def set_integrator(self, d, where):
         p = Props(d, where)
-        it = A.Integrator()
         self.aov_names = []
-        if p.type in ("nbins", "bins"):
-            # src/integrators/nbins.cpp:55-98, bins.cpp:23-85: wavelength-bin AOVs around one nested sampling integrator
-            if _SPECTRAL is None:
-                raise RuntimeError("This integrator can only be used with a spectral variant!")
-            nested = [(k, v) for k, v in sorted_items(d) if isinstance(v, dict) and k not in ("type", "id")]
-            for k, v in nested:
-                if v.get("type") not in ("path", "volpath", "volpathmis", "nbins", "bins"):
-                    raise RuntimeError("Child objects must be of type 'SamplingIntegrator'!")
-            if len(nested) > 1:
-                raise RuntimeError("More than one sub-integrator specified!")
-            if not nested:
-                raise RuntimeError("Must specify a sub-integrator!")
-            if nested[0][1].get("type") in ("nbins", "bins"):
-                raise RuntimeError("nested bin integrators are not supported by this backend")
-            lo, hi, names = [], [], []
-            if p.type == "nbins":
-                spec = p.get("wavelengths")
-                if spec is None:
-                    raise RuntimeError("Property \"wavelengths\" has not been specified!")
-                tol = float(p.get("tolerance", 1e-5))
-                for tok in str(spec).replace(",", " ").split():
-                    try:
-                        lo.append(float(tok))
-                    except ValueError:
-                        raise RuntimeError("Could not parse floating point value '%s'" % tok)
-                    hi.append(tol); names += [tok, tok + "_pop"]
-                mode = 1
-            else:
-                spec = p.get("bins")
-                if spec is None:
-                    raise RuntimeError("Property \"bins\" has not been specified!")
-                for tok in str(spec).replace(",", " ").split():
-                    item = tok.split(":")
-                    if len(item) != 3 or not all(item):
-                        continue                                            # bins.cpp:47-51: warn and skip
-                    try:
-                        lo.append(float(item[1])); hi.append(float(item[2]))
-                    except ValueError as e:
-                        raise RuntimeError("Could not parse floating point value '%s'" % str(e).split("'")[-2])
-                    names += [item[0], item[0] + "_weights"]
-                mode = 2
-            p.get(nested[0][0])
-            # the wrapper is the SamplingIntegrator that renders (nbins.cpp / bins.cpp: Base(props)): ITS block_size, samples_per_pass and
-            # timeout drive the render loop (integrator.cpp:29-48); of the nested integrator only sample() is used
-            outer = (int(p.get("block_size", 0)), int(p.get("samples_per_pass", -1)), float(p.get("timeout", -1.0)))
-            p.finish()
-            self.set_integrator(nested[0][1], where + "." + nested[0][0])
-            it = self.integrator
-            it.block_size, it.samples_per_pass, it.timeout = outer
-            if len(lo) > 64:
-                raise RuntimeError("this backend supports at most 64 spectral bins")
-            it.bin_mode, it.bin_count = mode, len(lo)
-            self._bins = (np.ascontiguousarray(lo, np.float32), np.ascontiguousarray(hi, np.float32))
-            self.keep += list(self._bins)
-            it.bin_lo = self._bins[0].ctypes.data_as(A.fp); it.bin_hi = self._bins[1].ctypes.data_as(A.fp)
-            self.aov_names = names
-            return
-        if p.type == "moment":
-            # src/integrators/moment.cpp:27-58: six AOV channels around one nested sampling integrator -- its result as XYZ and the square
-            if _SPECTRAL is not None:
-                raise RuntimeError("the moment integrator is not supported in the spectral variant by this backend")
-            nested = [(k, v) for k, v in sorted_items(d) if isinstance(v, dict) and k not in ("type", "id")]
-            if not nested:
-                raise RuntimeError("moment: must specify a nested integrator")
-            if len(nested) > 1:
-                raise RuntimeError("moment: more than one nested integrator (%s) is not supported by this backend" % ", ".join(k for k, _ in nested))
-            name, child = nested[0]
-            if child.get("type") not in ("path", "volpath", "volpathmis"):
-                raise RuntimeError("moment: the nested integrator \"%s\" must be one of path, volpath, volpathmis, not \"%s\"" % (name, child.get("type")))
-            p.get(name)
-            # as for nbins / bins above: the wrapper's block_size, samples_per_pass and timeout drive the render loop
-            outer = (int(p.get("block_size", 0)), int(p.get("samples_per_pass", -1)), float(p.get("timeout", -1.0)))
-            p.finish()
-            self.set_integrator(child, where + "." + name)
-            it = self.integrator
-            it.block_size, it.samples_per_pass, it.timeout = outer
-            it.moment = 1
-            self.aov_names = [name + c for c in (".X", ".Y", ".Z")] + ["m2_" + name + c for c in (".X", ".Y", ".Z")]       # moment.cpp:43-52
-            return
-        if p.type == "path":
-            it.type = A.INTEGRATOR_PATH
-        elif p.type == "volpath":
-            it.type = A.INTEGRATOR_VOLPATH
-        elif p.type == "volpathmis":
-            it.type = A.INTEGRATOR_VOLPATHMIS
-        else:
+        if p.type not in INTEGRATOR_PLUGINS:
             raise RuntimeError("Unknown / unsupported integrator plugin \"%s\"" % p.type)
+        INTEGRATOR_PLUGINS[p.type](self, d, p, where)
+
+    @staticmethod
+    def _nested_integrators(d):
+        """The child objects of a wrapper (nbins, bins, moment), in props.objects() order"""
+        return [(k, v) for k, v in sorted_items(d) if isinstance(v, dict) and k not in ("type", "id")]
+
+    def _wrap(self, p, name, child, where):
+        """The wrapper is the SamplingIntegrator that renders (nbins.cpp / bins.cpp / moment.cpp: Base(props)): ITS block_size,
+        samples_per_pass and timeout drive the render loop (integrator.cpp:29-48); of the nested integrator only sample() is used.
+        Builds the nested integrator and returns its record with the wrapper's three values."""
+        p.get(name)
+        outer = (int(p.get("block_size", 0)), int(p.get("samples_per_pass", -1)), float(p.get("timeout", -1.0)))
+        p.finish()
+        self.set_integrator(child, where + "." + name)
+        it = self.integrator
+        it.block_size, it.samples_per_pass, it.timeout = outer
+        return it
+
+    def _bin_integrator(self, d, p, where):
+        # src/integrators/nbins.cpp:55-98, bins.cpp:23-85: wavelength-bin AOVs around one nested sampling integrator
+        if _SPECTRAL is None:
+            raise RuntimeError("This integrator can only be used with a spectral variant!")
+        nested = self._nested_integrators(d)
+        for k, v in nested:
+            if v.get("type") not in tuple(SAMPLING_INTEGRATORS) + ("nbins", "bins"):
+                raise RuntimeError("Child objects must be of type 'SamplingIntegrator'!")
+        if len(nested) > 1:
+            raise RuntimeError("More than one sub-integrator specified!")
+        if not nested:
+            raise RuntimeError("Must specify a sub-integrator!")
+        if nested[0][1].get("type") in ("nbins", "bins"):
+            raise RuntimeError("nested bin integrators are not supported by this backend")
+        lo, hi, names = [], [], []
+        if p.type == "nbins":
+            spec = p.get("wavelengths")
+            if spec is None:
+                raise RuntimeError("Property \"wavelengths\" has not been specified!")
+            tol = float(p.get("tolerance", 1e-5))
+            for tok in str(spec).replace(",", " ").split():
+                try:
+                    lo.append(float(tok))
+                except ValueError:
+                    raise RuntimeError("Could not parse floating point value '%s'" % tok)
+                hi.append(tol); names += [tok, tok + "_pop"]
+            mode = 1
+        else:
+            spec = p.get("bins")
+            if spec is None:
+                raise RuntimeError("Property \"bins\" has not been specified!")
+            for tok in str(spec).replace(",", " ").split():
+                item = tok.split(":")
+                if len(item) != 3 or not all(item):
+                    continue                                            # bins.cpp:47-51: warn and skip
+                try:
+                    lo.append(float(item[1])); hi.append(float(item[2]))
+                except ValueError as e:
+                    raise RuntimeError("Could not parse floating point value '%s'" % str(e).split("'")[-2])
+                names += [item[0], item[0] + "_weights"]
+            mode = 2
+        it = self._wrap(p, nested[0][0], nested[0][1], where)
+        if len(lo) > 64:
+            raise RuntimeError("this backend supports at most 64 spectral bins")
+        it.bin_mode, it.bin_count = mode, len(lo)
+        self._bins = (np.ascontiguousarray(lo, np.float32), np.ascontiguousarray(hi, np.float32))
+        self.keep += list(self._bins)
+        it.bin_lo = self._bins[0].ctypes.data_as(A.fp); it.bin_hi = self._bins[1].ctypes.data_as(A.fp)
+        self.aov_names = names
+
+    def _moment(self, d, p, where):
+        # src/integrators/moment.cpp:27-58: six AOV channels around one nested sampling integrator -- its result as XYZ and the square
+        if _SPECTRAL is not None:
+            raise RuntimeError("the moment integrator is not supported in the spectral variant by this backend")
+        nested = self._nested_integrators(d)
+        if not nested:
+            raise RuntimeError("moment: must specify a nested integrator")
+        if len(nested) > 1:
+            raise RuntimeError("moment: more than one nested integrator (%s) is not supported by this backend" % ", ".join(k for k, _ in nested))
+        name, child = nested[0]
+        if child.get("type") not in SAMPLING_INTEGRATORS:
+            raise RuntimeError("moment: the nested integrator \"%s\" must be one of path, volpath, volpathmis, not \"%s\"" % (name, child.get("type")))
+        self._wrap(p, name, child, where).moment = 1
+        self.aov_names = [name + c for c in (".X", ".Y", ".Z")] + ["m2_" + name + c for c in (".X", ".Y", ".Z")]       # moment.cpp:43-52
+
+    def _sampling_integrator(self, d, p, where):
+        it = A.Integrator()
+        it.type = SAMPLING_INTEGRATORS[p.type]
         it.use_spectral_mis = int(bool(p.get("use_spectral_mis", True))) if p.type == "volpathmis" else 1
         it.max_depth = int(p.get("max_depth", -1))
         it.rr_depth = int(p.get("rr_depth", 5))
@@ -1168,7 +1160,6 @@ class SceneBuilder:
     def load(self, d):
         if not isinstance(d, dict) or d.get("type") != "scene":
             raise RuntimeError("load_dict(): the top-level dictionary must have type 'scene' in this backend")
-        SHAPES = ("rectangle", "cube", "sphere", "mesh", "obj", "ply", "disk")
         for k, v in sorted_items(d):          # scene.cpp:23: props.objects() order
             if k in ("type", "id"):
                 continue
@@ -1178,15 +1169,15 @@ class SceneBuilder:
             if t == "ref":
                 raise RuntimeError("Reference found at the scene level: %s" % k)
             name = v.get("id", k)                                       # scene.cpp:237-244: a child goes by its id; here a key is one
-            if t in SHAPES:
+            if t in SHAPE_PLUGINS:
                 self.children.append((name, ("shape", self.add_shape(v, k))))
             elif t in ("directional", "constant", "area", "point"):
                 self.children.append((name, ("emitter", self.add_emitter(v, k))))
-            elif t in ("perspective", "distant", "mradiancemeter", "mdistant", "distantflux", "radiancemeter"):
+            elif t in SENSOR_PLUGINS:
                 if self.sensor is not None:
                     raise RuntimeError("this backend supports a single sensor per scene")
                 self.set_sensor(v, k)
-            elif t in ("path", "volpath", "volpathmis", "nbins", "bins", "moment"):
+            elif t in INTEGRATOR_PLUGINS:
                 if self.integrator is not None:
                     raise RuntimeError("Only one integrator can be specified per scene.")
                 self.set_integrator(v, k)
@@ -1225,6 +1216,13 @@ class SceneBuilder:
         desc.spectra, desc.spectrum_count = arr(A.Spectrum, self.spectra), len(self.spectra)
         self.keep.append(desc)
         return desc
+
+
+# plugin name -> the SceneBuilder method that builds it: what load() accepts and what set_sensor / set_integrator dispatch through
+SENSOR_PLUGINS = {"perspective": SceneBuilder._perspective, "distant": SceneBuilder._distant, "radiancemeter": SceneBuilder._radiancemeter,
+                  "distantflux": SceneBuilder._distantflux, "mradiancemeter": SceneBuilder._mradiancemeter, "mdistant": SceneBuilder._mdistant}
+INTEGRATOR_PLUGINS = dict({name: SceneBuilder._sampling_integrator for name in SAMPLING_INTEGRATORS},
+                          nbins=SceneBuilder._bin_integrator, bins=SceneBuilder._bin_integrator, moment=SceneBuilder._moment)
 
 
 def build_scene_desc(d, mono=False, spectral=False):

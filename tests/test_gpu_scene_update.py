@@ -1,7 +1,7 @@
 """mts_scene_update on the device (run with -m gpu on an MI355X): a scene updated in place is the scene a fresh load builds -- same
 film (the oracle's, bit for bit with the fresh load's), same kernel, same device contents (mts_debug_scene_digest) -- for grids given
 as host arrays and as device tensors, at the grid shapes where the fused reduction / pair-grid pass can go wrong, and a refused update
-leaves the scene alone."""
+leaves the scene alone.  And without a render: the uploaded copy of a fresh scene is the host scene, word for word of the digest."""
 import copy
 import ctypes as C
 import importlib
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import tests.oracle_binding as ob
-from tests import update_cases
+from tests import sensor_cases, update_cases
 
 pytestmark = pytest.mark.gpu
 A = importlib.import_module("eradiate-kernel_amd._capi")
@@ -354,3 +354,19 @@ def test_description_after_a_device_update(gpu_rgb):
     assert bool(vol.data)
     half["slab"]["interior"]["sigma_t"]["data"] = sets_b[key]
     assert_is_fresh(gpu_rgb, scene, half, ob.OracleScene(half).render())
+
+
+# ---------------------------------------------------------------- the uploaded copy is the host scene
+@pytest.mark.parametrize("case", sensor_cases.UPLOAD_CASES)
+def test_uploaded_scene_is_the_host_scene(gpu_rgb, case):
+    """upload_host_scene and the two modes of the digest walk (device memory, the host's own arrays) against each other: all eight slots.
+    No render is launched."""
+    builder, kw = sensor_cases.CASES[case]
+    gpu_rgb.set_variant("gpu_spectral" if kw.get("spectral") else "gpu_rgb")
+    try:
+        scene = gpu_rgb.load_dict(builder())
+        host = (C.c_uint64 * 8)()
+        A.check(A.lib().mts_debug_desc_digest(C.byref(scene._desc), host))
+        assert digest(scene) == list(host)
+    finally:
+        gpu_rgb.set_variant("gpu_rgb")

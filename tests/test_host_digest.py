@@ -1,0 +1,241 @@
+"""The host scene a description builds, as its digest (mts_debug_desc_digest: csrc/scene_host.cpp, digest_host_scene in host mode) -- no GPU.
+
+  * every case of tests/sensor_cases.py builds, and hashes to the same eight words twice in one process and in a fresh process
+    (uninitialised padding in a record would show up here);
+  * a change of one input changes the slots that hold it and no slot that holds unrelated data;
+  * the refusals of the sensor / integrator construction, on both sides of the ABI, with their texts.
+
+Slots: [0] record arrays, [1] grid data, [2] pair grids, [3] phase tables, [4] spectra, [5] the scalar header of DScene (sensor, integrator,
+counts, bounding box) and the traits, [6] geometry tables and BVH, [7] filter table, sub-sensor matrices, bin bounds."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import sensor_cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+A = importlib.import_module("eradiate-kernel_amd._capi")
+SD = importlib.import_module("eradiate-kernel_amd.scene_dict")
+T = importlib.import_module("eradiate-kernel_amd.transform").ScalarTransform4f
+
+
+def describe(case, edit=None):
+    builder, kw = sensor_cases.CASES[case]
+    d = builder()
+    if edit is not None:
+        edit(d)
+    return SD.build_scene_desc(d, **kw)
+
+
+def desc_digest(desc):
+    out = (C.c_uint64 * 8)()
+    A.check(A.lib().mts_debug_desc_digest(C.byref(desc), out))
+    return tuple(out)
+
+
+def digest(case, edit=None):
+    desc, keep = describe(case, edit)
+    return desc_digest(desc)
+
+
+@pytest.fixture(scope="module")
+def digests():
+    """computed once; the tests below compare with it and leave it alone"""
+    return {case: digest(case) for case in sensor_cases.CASES}
+
+
+CHILD = """
+import sys
+sys.path.insert(0, %r)
+import tests.test_host_digest as t
+for case in t.sensor_cases.CASES:
+    print(case, *t.digest(case))
+"""
+
+
+def test_cases_cover_the_branches():
+    names = set(sensor_cases.CASES)
+    for sensor in ("distant", "distantflux", "mdistant"):
+        assert {"%s_target_%s" % (sensor, t) for t in ("none", "point", "rectangle", "disk", "sphere")} <= names
+    for sensor in ("distant", "distantflux"):
+        assert {"%s_origin_%s" % (sensor, t) for t in ("rectangle", "disk", "sphere")} <= names
+    assert set(sensor_cases.UPLOAD_CASES) <= names
+
+
+@pytest.mark.parametrize("case", sorted(sensor_cases.CASES))
+def test_digest_repeats_in_process(digests, case):
+    assert digest(case) == digests[case]
+    assert all(w != 0 for w in digests[case])                   # every slot is an FNV state, never the untouched zero
+
+
+def test_digest_repeats_in_a_fresh_process(digests):
+    r = subprocess.run([sys.executable, "-c", CHILD % ROOT], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    child = {line.split()[0]: tuple(int(w) for w in line.split()[1:]) for line in r.stdout.splitlines()}
+    assert child == digests
+
+
+def test_bvh_case_has_a_bvh_and_the_others_none(digests):
+    A.lib().mts_debug_scene_traits.argtypes = [C.POINTER(A.SceneDesc), C.POINTER(C.c_int32)]
+    NO_BVH = 2                                                   # MT_NO_BVH (csrc/dscene.h)
+    for case, expect in (("bvh_mesh", 0), ("heterogeneous_medium", NO_BVH)):
+        desc, keep = describe(case)
+        t = C.c_int32()
+        A.check(A.lib().mts_debug_scene_traits(C.byref(desc), C.byref(t)))
+        assert t.value & NO_BVH == expect, case
+
+
+# ---------------------------------------------------------------- sensitivity: (case, edit, slots that must change, slots that must not)
+def _set(path, value):
+    def edit(d):
+        node = d
+        for k in path[:-1]:
+            node = node[k]
+        node[path[-1]] = value
+    return edit
+
+
+def _move_vertex(d):
+    v = sensor_cases.mesh_vertices()
+    v[17, 2] += np.float32(0.0625)
+    d["sheet"]["vertex_positions"] = v
+
+
+ALL = set(range(8))
+SENSITIVITY = {
+    "sampler_seed": ("perspective_gaussian", _set(("sensor", "sampler"), {"type": "independent", "sample_count": 2, "seed": 4}), {5}, ALL - {5}),
+    "crop_offset": ("perspective_crop_box_ppo", _set(("sensor", "film", "crop_offset_x"), 2), {5}, ALL - {5}),
+    "filter_stddev": ("perspective_gaussian_stddev", _set(("sensor", "film", "rfilter", "stddev"), 0.625), {5, 7}, ALL - {5, 7}),
+    "point_target": ("distant_target_point", _set(("sensor", "ray_target"), [0.25, -0.5, 0.25]), {5}, ALL - {5}),
+    "target_rectangle_scale": ("mdistant_target_rectangle", _set(("sensor", "target"), dict(sensor_cases.RECTANGLE, to_world=T.translate([0, 0, 1]) @ T.scale(0.75))), {5}, ALL - {5}),
+    "mradiancemeter_origin": ("mradiancemeter", _set(("sensor", "origins"), "0, 0, 2, 1, 0.5, 2, 0, 1, 2"), {7}, ALL - {7}),
+    "bin_bound": ("bins", _set(("integrator", "bins"), "blue:400:500, red:600:710"), {7}, ALL - {7}),
+    "rr_depth": ("perspective_gaussian", _set(("integrator", "rr_depth"), 4), {5}, ALL - {5}),
+    # a vertex moves: the geometry tables, and with them the mesh's area in its record ([0]); the bounding box ([5]) may or may not follow
+    "mesh_vertex": ("bvh_mesh", _move_vertex, {0, 6}, {1, 2, 3, 4, 7}),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SENSITIVITY))
+def test_sensitivity(digests, name):
+    case, edit, changes, keeps = SENSITIVITY[name]
+    before, after = digests[case], digest(case, edit)
+    changed = {k for k in range(8) if before[k] != after[k]}
+    print(name, "changed slots", sorted(changed))
+    assert changes <= changed
+    assert not (keeps & changed)
+
+
+# ---------------------------------------------------------------- refusals, with the texts of the parent's source
+def library_refusal(case, edit=None, poke=None):
+    """The message mts_debug_desc_digest comes back with: for a dictionary edited by `edit`, or a description hand-filled by `poke`"""
+    desc, keep = describe(case, edit)
+    if poke is not None:
+        poke(desc, keep)
+    with pytest.raises(RuntimeError) as e:
+        desc_digest(desc)
+    return str(e.value)
+
+
+CUBE = {"type": "cube"}
+SHAPE_KIND = " shape must be a rectangle, a disk or a sphere in this backend"
+
+
+def test_target_and_origin_shape_kinds():
+    assert library_refusal("distant_target_rectangle", _set(("sensor", "ray_target"), CUBE)) == "distant ray_target" + SHAPE_KIND
+    assert library_refusal("distantflux_target_rectangle", _set(("sensor", "target"), CUBE)) == "distant ray_target" + SHAPE_KIND
+    assert library_refusal("mdistant_target_rectangle", _set(("sensor", "target"), CUBE)) == "mdistant target" + SHAPE_KIND
+    for case, key in (("distant_origin_disk", "ray_origin"), ("distantflux_origin_disk", "origin")):
+        assert library_refusal(case, _set(("sensor", key), CUBE)) == "distant sensor: the ray origin shape must be a rectangle, a disk or a sphere in this backend"
+        with pytest.raises(RuntimeError) as e:
+            describe(case, _set(("sensor", key), [0, 0, 1]))
+        assert str(e.value) == "Invalid parameter %s, must be a Shape." % key
+
+
+def test_unknown_target_types():
+    def poke(desc, keep):
+        desc.sensor.distant_target_type = 7
+    assert library_refusal("distant_target_point", poke=poke) == "distant sensor: unknown ray_target type"
+    assert library_refusal("distantflux_target_none", poke=poke) == "distant sensor: unknown ray_target type"
+    assert library_refusal("mdistant_target_point", poke=poke) == "mdistant sensor: unknown target type"
+    desc, keep = describe("mradiancemeter")                        # mradiancemeter has no target: the field is not read
+    desc.sensor.distant_target_type = 7
+    desc_digest(desc)
+
+
+def test_film_filter_and_sampler_refusals():
+    with pytest.raises(RuntimeError) as e:
+        describe("perspective_crop_box_ppo", _set(("sensor", "film", "crop_width"), 4))
+    assert str(e.value) == "Invalid crop window specification!"
+
+    def crop(desc, keep):
+        desc.sensor.crop_size[0] = 4
+    assert library_refusal("perspective_crop_box_ppo", poke=crop) == "film: invalid size / crop window"
+    assert library_refusal("perspective_crop_box_ppo", _set(("sensor", "film", "rfilter", "radius"), 16.5)) == "reconstruction filter radius too large"
+    assert library_refusal("wavefront", _set(("integrator", "samples_per_pass"), 1)) == \
+        "wavefront streams (mts_sensor.sampler_wavefront): samples_per_pass must cover the whole sample_count (one pass)"
+    digest("wavefront", _set(("integrator", "samples_per_pass"), 2))          # one pass: accepted
+
+
+def test_integrator_refusals():
+    assert library_refusal("perspective_gaussian", _set(("integrator", "max_depth"), 32768)) == "\"max_depth\" must be -1 (infinite) or at most 32767 on this backend"
+    digest("perspective_gaussian", _set(("integrator", "max_depth"), 32767))
+
+    def many_bins(desc, keep):
+        desc.integrator.bin_count = 65
+    assert library_refusal("nbins", poke=many_bins) == "bins: between 0 and 64 bins with their bounds"
+
+    def no_bounds(desc, keep):
+        desc.integrator.bin_hi = C.POINTER(C.c_float)()
+    assert library_refusal("bins", poke=no_bounds) == "bins: between 0 and 64 bins with their bounds"
+    assert library_refusal("bins", _set(("integrator", "bins"), "blue:400:500, red:700:600")) == "UniformSpectrum: 'lambda_min' must be less than 'lambda_max'"
+    with pytest.raises(RuntimeError) as e:
+        describe("nbins", _set(("integrator", "wavelengths"), ", ".join(str(400 + k) for k in range(65))))
+    assert str(e.value) == "this backend supports at most 64 spectral bins"
+
+
+def test_srf_refusals():
+    def srf_on_a_distant_sensor(desc, keep):
+        desc.sensor.type = A.SENSOR_DISTANT
+    assert library_refusal("srf_uniform", poke=srf_on_a_distant_sensor) == "srf: only perspective and radiancemeter sensors sample their wavelengths from a response function"
+
+    def regular_srf(desc, keep):
+        desc.sensor.srf = 1 + next(i for i in range(desc.spectrum_count) if desc.spectra[i].type == A.SPECTRUM_REGULAR)
+    assert library_refusal("srf_uniform", _set(("sun", "irradiance"), {"type": "regular", "lambda_min": 400.0, "lambda_max": 700.0, "values": [1.0, 2.0]}),
+                           poke=regular_srf) == "srf: sample_spectrum is available for uniform and discrete spectra"
+
+
+def test_plugin_names():
+    builder, kw = sensor_cases.CASES["perspective_gaussian"]
+    for key, plugin in (("sensor", "fisheye"), ("integrator", "ptracer"), ("ground", "cylinder")):
+        d = builder()
+        d[key] = dict(d[key], type=plugin)
+        with pytest.raises(RuntimeError) as e:
+            SD.build_scene_desc(d)
+        assert str(e.value) == "Unknown / unsupported plugin \"%s\" (key \"%s\")" % (plugin, key)
+    b = SD.SceneBuilder()
+    with pytest.raises(RuntimeError) as e:
+        b.set_sensor({"type": "fisheye", "film": sensor_cases.film(2, 2)}, "sensor")
+    assert str(e.value) == "Unknown / unsupported sensor plugin \"fisheye\""
+    with pytest.raises(RuntimeError) as e:
+        b.set_integrator({"type": "ptracer"}, "integrator")
+    assert str(e.value) == "Unknown / unsupported integrator plugin \"ptracer\""
+    assert set(SD.SENSOR_PLUGINS) == {"perspective", "distant", "mradiancemeter", "mdistant", "distantflux", "radiancemeter"}
+    assert set(SD.INTEGRATOR_PLUGINS) == {"path", "volpath", "volpathmis", "nbins", "bins", "moment"}
+
+
+def test_wrappers_without_a_nested_integrator():
+    with pytest.raises(RuntimeError) as e:
+        describe("nbins", _set(("integrator",), {"type": "nbins", "wavelengths": "450, 650"}))
+    assert str(e.value) == "Must specify a sub-integrator!"
+    with pytest.raises(RuntimeError) as e:
+        describe("bins", _set(("integrator",), {"type": "bins", "bins": "blue:400:500"}))
+    assert str(e.value) == "Must specify a sub-integrator!"
+    with pytest.raises(RuntimeError) as e:
+        describe("moment", _set(("integrator",), {"type": "moment"}))
+    assert str(e.value) == "moment: must specify a nested integrator"
