@@ -321,8 +321,47 @@ DEV Hit ray_intersect_preliminary(const DScene &sc, DRay ray) {
     return h;
 }
 
+// ---------------------------------------------------------------- geometry table (ring kernels of the lean units a, h)
+// A scene without a BVH and with at most MTS_GEOM_LDS_PRIMS primitives keeps a copy of its triangles' attribute rows (tri_attr: 24
+// floats per primitive, prim order) in LDS.  ring_workgroup_async fills the table in front of its first barrier (geom_table_to_lds);
+// it is read-only afterwards.  hit_point / complete_surface read a triangle's vertices, normals and texture coordinates from it per
+// lane, indexed by s.prim_offset + h.prim, instead of through per-lane global loads behind the scalar load of the shape record
+// (profiles/geom_table_ab.txt).  The rows are MTS_GEOM_ATTR_STRIDE = 25 dwords apart: an odd stride puts the rows of the sixteen
+// primitives on distinct banks (24 would map primitives k and k + 8 to the same ones), lanes on one primitive broadcast.  A unit
+// asks for the table with MTS_GEOM_LDS (kernels_lean_{a,h}.hip); only functions instantiated with TAB = true reference it, so no
+// other kernel's LDS changes.  The primitive list itself stays on scalar loads: walked from LDS records it measured slower.
+#ifndef MTS_GEOM_LDS
+#define MTS_GEOM_LDS 0
+#endif
+#define MTS_GEOM_LDS_PRIMS 16
+#define MTS_GEOM_ATTR_STRIDE 25
+#define MTS_GEOM_LDS_BYTES (MTS_GEOM_LDS_PRIMS * MTS_GEOM_ATTR_STRIDE * 4)
+__shared__ float mts_geom_attr[MTS_GEOM_LDS_PRIMS * MTS_GEOM_ATTR_STRIDE];
+DEV bool geom_table_holds(const DScene &sc) { return sc.bvh_node_count == 0 && sc.prim_count <= MTS_GEOM_LDS_PRIMS; }
+DEV void geom_table_to_lds(const DScene &sc, uint32_t tid, uint32_t nt) {
+    if (!geom_table_holds(sc)) return;
+    const uint32_t n = (uint32_t) sc.prim_count;
+    const MTS_GLOBAL_AS float *A = as_global(sc.tri_attr);
+    for (uint32_t k = tid; k < (uint32_t) (MTS_GEOM_LDS_PRIMS * 24); k += nt) {
+        const uint32_t prim = k / 24u, j = k - prim * 24u;
+        mts_geom_attr[prim * MTS_GEOM_ATTR_STRIDE + j] = prim < n ? A[k] : 0.f;
+    }
+}
+// a triangle's attribute row: floats [from, from + count) of p0 p1 p2, n0 n1 n2, uv0 uv1 uv2, from the table (`tab`, wave-uniform) or the scene
+template <bool TAB, int COUNT>
+DEV void tri_attr_load(const DScene &sc, const DShape &s, const Hit &h, bool tab, int from, float *out) {
+    if (TAB && tab) {
+        const float *A = mts_geom_attr + MTS_GEOM_ATTR_STRIDE * (s.prim_offset + h.prim) + from;
+        for (int k = 0; k < COUNT; ++k) out[k] = A[k];
+    } else {
+        const MTS_GLOBAL_AS float *A = as_global(sc.tri_attr) + 24 * (s.prim_offset + h.prim) + from;
+        for (int k = 0; k < COUNT; ++k) out[k] = A[k];
+    }
+}
+
 // Hit point: rectangle.cpp:181-185, mesh.cpp:470-483, sphere.cpp:325-327
-DEV void hit_point(const DScene &sc, const DShape &s, const DRay &ray, Hit &h) {
+template <bool TAB = false>
+DEV void hit_point(const DScene &sc, const DShape &s, const DRay &ray, Hit &h, bool tab = false) {
     if (s.type == MTS_SHAPE_RECTANGLE || s.type == MTS_SHAPE_DISK) {                          // rectangle.cpp:181-185 == disk.cpp:186-188
         F3 p = ray_at(ray, h.t), n = f3(s.frame_n);
         float dist = dot(f3(s.to_world.m[3], s.to_world.m[7], s.to_world.m[11]) - p, n);
@@ -332,7 +371,7 @@ DEV void hit_point(const DScene &sc, const DShape &s, const DRay &ray, Hit &h) {
         h.p = fmadd(n, s.radius, f3(s.center));
         h.uv.x = n.x; h.uv.y = n.y; h.prim = (int32_t) pm_bits(n.z);     // keep the exact normal for complete_surface()
     } else {
-        const MTS_GLOBAL_AS float *A = as_global(sc.tri_attr) + 24 * (s.prim_offset + h.prim);
+        float A[9]; tri_attr_load<TAB, 9>(sc, s, h, tab, 0, A);
         F3 p0 = f3(A), p1 = f3(A + 3), p2 = f3(A + 6);
         float b1 = h.uv.x, b2 = h.uv.y, b0 = 1.f - b1 - b2;
         h.p = p0 * b0 + p1 * b1 + p2 * b2;
@@ -340,11 +379,13 @@ DEV void hit_point(const DScene &sc, const DShape &s, const DRay &ray, Hit &h) {
 }
 
 // librender/scene_native.inl:23-41
+template <bool TAB = false>
 DEV Hit ray_intersect(const DScene &sc, const DRay &ray) {
+    const bool tab = TAB && geom_table_holds(sc);              // wave-uniform
     Hit h = ray_intersect_preliminary<false>(sc, ray);
     if (hit_valid(h)) {
         WATERFALL_BEGIN(h.shape, su)
-            hit_point(sc, cload(sc.shapes + su), ray, h);
+            hit_point<TAB>(sc, cload(sc.shapes + su), ray, h, tab);
         WATERFALL_END
     }
     return h;
@@ -353,7 +394,9 @@ DEV bool ray_test(const DScene &sc, const DRay &ray) { return hit_valid(ray_inte
 
 // Rebuild n, shading frame and wi: rectangle.cpp:186-193, mesh.cpp:485-545, sphere.cpp:328-371,
 // interaction.h:153-156,571-596.  `d` is the direction of the ray that produced the hit.
+template <bool TAB = false>
 DEV void complete_surface(const DScene &sc, const DShape &s, const Hit &h, F3 d, Surf &sf) {
+    const bool tab = TAB && geom_table_holds(sc);              // wave-uniform
     F3 dp_du, dp_dv, shn;
     if (s.type == MTS_SHAPE_RECTANGLE) {
         sf.n = f3(s.frame_n); shn = sf.n; dp_du = f3(s.frame_s);
@@ -370,21 +413,23 @@ DEV void complete_surface(const DScene &sc, const DShape &s, const Hit &h, F3 d,
         if (s.flip_normals) shn = -shn;
         sf.n = shn;
     } else {
-        const MTS_GLOBAL_AS float *A = as_global(sc.tri_attr) + 24 * (s.prim_offset + h.prim);
+        float A[9]; tri_attr_load<TAB, 9>(sc, s, h, tab, 0, A);
         F3 p0 = f3(A), p1 = f3(A + 3), p2 = f3(A + 6);
         float b1 = h.uv.x, b2 = h.uv.y, b0 = 1.f - b1 - b2;
         F3 dp0 = p1 - p0, dp1 = p2 - p0;
         sf.n = normalize(cross(dp0, dp1));
         coordinate_system(sf.n, dp_du, dp_dv);
         if (s.has_texcoords) {
-            float u0x = A[18], u0y = A[19], u1x = A[20], u1y = A[21], u2x = A[22], u2y = A[23];
+            float T[6]; tri_attr_load<TAB, 6>(sc, s, h, tab, 18, T);
+            float u0x = T[0], u0y = T[1], u1x = T[2], u1y = T[3], u2x = T[4], u2y = T[5];
             float d0x = u1x - u0x, d0y = u1y - u0y, d1x = u2x - u0x, d1y = u2y - u0y;
             float det = pm_fma(d0x, d1y, -(d0y * d1x)), inv_det = pm_rcp(det);
             if (det != 0.f)
                 dp_du = f3(pm_fma(d1y, dp0.x, -(d0y * dp1.x)), pm_fma(d1y, dp0.y, -(d0y * dp1.y)), pm_fma(d1y, dp0.z, -(d0y * dp1.z))) * inv_det;
         }
         if (s.has_normals) {
-            F3 n0 = f3(A + 9), n1 = f3(A + 12), n2 = f3(A + 15);
+            float N[9]; tri_attr_load<TAB, 9>(sc, s, h, tab, 9, N);
+            F3 n0 = f3(N), n1 = f3(N + 3), n2 = f3(N + 6);
             shn = normalize(n0 * b0 + n1 * b1 + n2 * b2);
         } else shn = sf.n;
     }
@@ -1106,9 +1151,10 @@ DEV Spec null_transmission(const DScene &sc, const DShape &s) { return sc.bsdfs[
 DEV float mis_weight(float pdf_a, float pdf_b) { pdf_a *= pdf_a; pdf_b *= pdf_b; return pdf_a > 0.0f ? pdf_a / (pdf_a + pdf_b) : 0.0f; }   // volpath.cpp:479-483
 
 // Geometric normal of a hit without the full shading frame (only needed for medium transitions)
+template <bool TAB = false>
 DEV F3 hit_geo_normal(const DScene &sc, const DShape &s, const Hit &h) {
     if (s.type == MTS_SHAPE_RECTANGLE || s.type == MTS_SHAPE_DISK) return f3(s.frame_n);
-    Surf sf; complete_surface(sc, s, h, f3(0.f, 0.f, 1.f), sf);
+    Surf sf; complete_surface<TAB>(sc, s, h, f3(0.f, 0.f, 1.f), sf);
     return sf.n;
 }
 DEV F3 hit_geo_normal(const DScene &sc, const Hit &h) {

@@ -10,6 +10,9 @@
 // the suffix _spectral).
 #include <hip/hip_runtime.h>
 #define PM_TABLES_IN_LDS 1            // pmath.h: LDS copies of the two hot lookup tables; every kernel below fills them first
+#if defined(MTSAMD_BLOCKSTATS) && !defined(MTS_SPEC_N) && !defined(MTS_GEOM_LDS)
+#define MTS_GEOM_LDS 1                // the diagnostic build has no lean units: its general rgb ring kernels stand in for them, table included
+#endif
 #include "integrator_dev.h"
 #include "volpath_flat.h"
 #include "volpathmis_flat.h"

@@ -8,5 +8,6 @@
 #define MTS_VARIANT_NS v_rgb_lean_a
 #define MTS_LEAN_MIS_768 1     // `volpathmis`: 164 VGPRs here (general kernel: 193) -- room for a third wave per SIMD, 768 threads on the 512 paths
 #define MTS_TRAITS MT_UNIT_A      // dscene.h
+#define MTS_GEOM_LDS 1           // integrator_dev.h: small scenes keep their triangles' attribute rows in LDS (the volpath rings)
 #include "kernels.hip"
 #endif

@@ -5,5 +5,6 @@
 #define MTS_LEAN _lean_h
 #define MTS_VARIANT_NS v_rgb_lean_h
 #define MTS_TRAITS MT_UNIT_H      // dscene.h
+#define MTS_GEOM_LDS 1           // integrator_dev.h: small scenes keep their triangles' attribute rows in LDS (the volpath rings)
 #include "kernels.hip"
 #endif

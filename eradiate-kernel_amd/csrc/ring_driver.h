@@ -154,6 +154,9 @@ DEV void ring_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt) {
     }
     if (tid < 2u * B_COUNT + 2u) q_ctl[tid] = 0;
     pm_tables_to_lds(tid);
+    // the kernel's LDS: the three arrays above, the two pmath tables (512 B) and, for a machine that has one, the geometry table
+    static_assert(sizeof(hot_lds) + sizeof(q_ids) + sizeof(q_ctl) + 512 + (M::GEOM_TABLE ? MTS_GEOM_LDS_BYTES : 0) <= 160 * 1024, "a workgroup has 160 KiB of LDS");
+    if constexpr (M::GEOM_TABLE) geom_table_to_lds(cload_k<WgArgs>(kernarg).sc, tid, (uint32_t) NT);      // read-only behind the barrier
     __syncthreads();
 #pragma unroll 1
     for (uint32_t pid0 = tid; pid0 < (uint32_t) WG; pid0 += NT) {   // ---- initialise the paths (integrator.cpp:198) and queue them

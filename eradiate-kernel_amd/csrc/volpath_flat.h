@@ -509,7 +509,7 @@ struct RingMachine {
     // ================================================================= INTERSECT, the core (volpath.cpp:109,182,241,298,339,395,425)
     DEV bool intersect(P &p) const {
         if (!wants_int(p)) return false;
-        p.si = ray_intersect(sc, p.ray);
+        p.si = ray_intersect<M::GEOM_TABLE>(sc, p.ray);      // ring kernels of the lean units a, h: hit points from the LDS table
         p.flags &= ~FL_NEEDS_INT;
         return true;
     }
@@ -554,10 +554,12 @@ struct RingMachine {
     }
 };
 
-template <bool COUNT, bool MOMENT_ = false>
-struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_>, PathState, true> {
-    typedef RingMachine<VolpathMachine<COUNT, MOMENT_>, PathState, true> Base;
+// GEOM_: the machine runs under the ring driver of a unit with the geometry table in LDS (integrator_dev.h: MTS_GEOM_LDS)
+template <bool COUNT, bool MOMENT_ = false, bool GEOM_ = false>
+struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathState, true> {
+    typedef RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathState, true> Base;
     static constexpr bool MOMENT = MOMENT_;                    // RingMachine::blk_new: the `moment` wrapper's eleven-channel tail
+    static constexpr bool GEOM_TABLE = GEOM_;
     using Base::sc; using Base::cnt; using Base::ctx; using Base::queue_intersection; using Base::wants_int;
     DEV VolpathMachine(const DScene &sc_, Counters &cnt_) : Base(sc_, cnt_) {}
     // The head of a sample (the draws up to the camera ray) stays written out here, in VolpathMisMachine::begin_sample and in render_sample
@@ -920,8 +922,8 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_>, PathState, t
                 if (!is_nee) emitter = s.emitter;
                 nt = s.bsdf_type == MTS_BSDF_NULL ? spec_s(1.f) : spec_s(0.f);                // null.cpp:70-73, bsdf.cpp:11-14
                 is_tr = s.is_medium_transition; ext = s.exterior; inte = s.interior;
-                if (emitter >= 0) complete_surface(sc, s, p.si, p.ray.d, sf);
-                else if (is_tr) sf.n = hit_geo_normal(sc, s, p.si);
+                if (emitter >= 0) complete_surface<GEOM_TABLE>(sc, s, p.si, p.ray.d, sf);
+                else if (is_tr) sf.n = hit_geo_normal<GEOM_TABLE>(sc, s, p.si);
             WATERFALL_END
         }
         if (emitter >= 0) {                                    // direct-light walk reached an emitter, volpath.cpp:430-440
@@ -956,7 +958,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_>, PathState, t
                 const DShape s = cload(sc.shapes + su);
                 emitter = s.emitter; bsdf_id = s.bsdf;
                 // the shading frame is only read by emitter evaluation and by the NEE of a smooth BSDF: a null boundary needs neither
-                if (s.emitter >= 0 || (s.bsdf_flags & F_Smooth) != 0) complete_surface(sc, s, p.si, p.ray.d, sf);
+                if (s.emitter >= 0 || (s.bsdf_flags & F_Smooth) != 0) complete_surface<GEOM_TABLE>(sc, s, p.si, p.ray.d, sf);
             WATERFALL_END
         }
         const SpecCtx cx = ctx(p); (void) cx;
@@ -993,7 +995,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_>, PathState, t
         Surf sf; int bsdf_id = 0, is_tr = 0, ext = -1, inte = -1;
         WATERFALL_BEGIN(p.si.shape, su)
             const DShape s = cload(sc.shapes + su);
-            complete_surface(sc, s, p.si, p.ray.d, sf);
+            complete_surface<GEOM_TABLE>(sc, s, p.si, p.ray.d, sf);
             bsdf_id = s.bsdf; is_tr = s.is_medium_transition; ext = s.exterior; inte = s.interior;
         WATERFALL_END
         const float s1 = p.rng.next_1d(); const F2 s2 = p.rng.next_2d();
@@ -1326,7 +1328,7 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
     uint32_t wg_base;
     const MTS_CONST_AS void *kernarg = block_uniforms(kernarg_, wg_base_, wg_base);
     const WgArgs a = cload_k<WgArgs>(kernarg);
-    VolpathMachine<COUNT, MOMENT> vm(a.sc, *cnt);
+    VolpathMachine<COUNT, MOMENT, MTS_GEOM_LDS != 0> vm(a.sc, *cnt);
     PathEnvT<ColdStoreHbm> e; wg_env<WG>(a, wg_base, pid, e);
     HotStore<WG> hs; hs.base = hot_lds + pid;
     typedef ClassFields<C> CF;
@@ -1417,7 +1419,8 @@ struct VolpathRing {
     static constexpr int WG = WG_, HOT_DWORDS = H_COUNT, PACKED = H_PACKED;
     typedef PathState State;
     typedef HotStore<WG_> Hot;
-    typedef VolpathMachine<COUNT_, MOMENT> Machine;
+    typedef VolpathMachine<COUNT_, MOMENT, MTS_GEOM_LDS != 0> Machine;
+    static constexpr bool GEOM_TABLE = Machine::GEOM_TABLE;      // the driver fills the geometry table
     template <int NT> DEV static void check_shape() { static_assert(NT <= WG_, "a thread per path at most"); }
     DEV static void init_idle(State &p) {
         p.medium = -1; p.thr = p.res = p.trans = spec_s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;

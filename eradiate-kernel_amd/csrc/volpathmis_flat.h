@@ -46,6 +46,7 @@ struct MisPathState {
 template <bool COUNT, bool SPEC, bool MOMENT_ = false>
 struct VolpathMisMachine : RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, MisPathState<SPEC>, false> {
     static constexpr bool MOMENT = MOMENT_;                    // RingMachine::blk_new: the `moment` wrapper's eleven-channel tail
+    static constexpr bool GEOM_TABLE = false;                  // RingMachine::intersect: the primitive list is walked from the scene records
     typedef MisPathState<SPEC> P;
     typedef MisWeights<SPEC> W;
     typedef RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, P, false> Base;
@@ -540,6 +541,7 @@ struct VolpathMisRing {
     typedef MisPathState<SPEC> State;
     typedef MisHotStore<WG_, SPEC> Hot;
     typedef VolpathMisMachine<COUNT_, SPEC, MOMENT> Machine;
+    static constexpr bool GEOM_TABLE = false;                  // no geometry table: the driver fills none for this machine
     template <int NT> DEV static void check_shape() { static_assert(NT <= 2 * WG_, "up to two threads per path (768 on 512: a third wave per SIMD)"); }
     DEV static void init_idle(State &p) {
         p.medium = -1; p.res = spec_s(0.f); p.lsp = f3s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;
