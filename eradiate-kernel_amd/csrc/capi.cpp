@@ -136,6 +136,29 @@ int mts_debug_scene_traits(const mts_scene_desc *desc, int32_t *traits) {
     API_CATCH
 }
 
+// Not part of the ABI either: DScene::cross_mask of a description's host scene -- the shapes whose hits the ring machines sort into the
+// class of null-boundary crossings (volpath_flat.h: B_CROSS).  Host only (tests/test_gpu_cross_class.py pins it on hand-built shape lists).
+int mts_debug_cross_mask(const mts_scene_desc *desc, uint64_t *mask) {
+    API_TRY
+    if (!mask) throw std::runtime_error("mts_debug_cross_mask: mask is NULL");
+    HostScene *hs = build_host_scene(desc);
+    *mask = hs->scene.cross_mask;
+    free_host_scene(hs);
+    API_CATCH
+}
+
+// ... and how many lane-visits the class B_CROSS served in this process's last render with loop counters (0: the kernel has no such
+// class, or met no crossing): the test that the lean units a and b do fill their ninth ring.  ONE value per process, not per scene:
+// every mts_render of any scene on any thread overwrites it, so it means something only to a caller that renders one scene at a time
+// and asks right after (tests/test_gpu_cross_class.py does).  mts_stats has no room for it without a change of the ABI.
+static std::atomic<unsigned long long> g_last_cross_visits{0};
+int mts_debug_cross_visits(uint64_t *visits) {
+    API_TRY
+    if (!visits) throw std::runtime_error("mts_debug_cross_visits: visits is NULL");
+    *visits = g_last_cross_visits.load();
+    API_CATCH
+}
+
 int mts_scene_destroy(mts_scene *scene) {
     if (scene) {
 #if defined(MTSAMD_HOST_ONLY)
@@ -407,6 +430,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
         HIP_CHECK(hipMemcpyAsync(h_counters, d_counters, sizeof(h_counters), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         throw_on_ring_stall(h_counters);
+        g_last_cross_visits.store(h_counters[3]);                    // ring_driver.h: MTS_CROSS_SLOT (zero unless the counting variant of a ring kernel ran)
         const bool cancelled = hs.stop.load() != 0;                  // render() returns !m_stop (integrator.cpp:178): a timeout alone is not a cancellation
         if (stats) {
             memset(stats, 0, sizeof(*stats));

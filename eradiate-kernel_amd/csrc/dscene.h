@@ -194,6 +194,10 @@ struct DScene {
     int32_t bin_mode, bin_count;
     const float *bin_lo, *bin_hi;
     int32_t film_channels;
+    // Bit i: shape i (i < 64) is a boundary that a main path merely crosses -- a null BSDF, which is not smooth, and no emitter on the
+    // shape: no emitter term, no emitter sample, no BSDF evaluation at such a hit.  The ring machines sort these hits into a class of
+    // their own (volpath_flat.h: B_CROSS).  Set where the shape records are built (scene_host.cpp: add_shape); a shape beyond 63 has no bit.
+    uint64_t cross_mask;
 };
 
 // bsdf.h:38-124

@@ -1,6 +1,6 @@
 // ring_driver.h -- the asynchronous-regrouping driver: a workgroup's paths wait in LDS rings, one per block class, and its waves serve them.
 //
-// Written once for every state machine that cuts its work into the block classes B_INT .. B_NEW of volpath_flat.h: `volpath`
+// Written once for every state machine that cuts its work into the block classes B_INT .. B_CROSS of volpath_flat.h: `volpath`
 // (VolpathRing, volpath_flat.h) and `volpathmis` (VolpathMisRing, volpathmis_flat.h).  A machine comes in as a policy M -- types,
 // constants and static functions, nothing stored:
 //   M::COUNT                  the counting kernel variant (loop counters, block statistics, the lost-path test hook)
@@ -11,6 +11,8 @@
 //   M::block<C>               the block function of class C (wg_block, mis_block), as a constant: block<C>(kernarg, hot_lds, wg_base,
 //                             pid, &cnt) is one visit of path `pid` and returns the class it waits for next
 //   M::check_shape<NT>()      static_assert on the threads that serve the policy's WG paths
+//   M::OPAQUE_INIT            the init loop loads the kernel arguments inside its body (see there)
+//   M::CROSS                  the machine names the class B_CROSS: nine rings; otherwise eight, and the class has neither slots nor a block
 #pragma once
 #include "volpath_flat.h"
 
@@ -48,6 +50,7 @@ inline namespace MTS_VARIANT_NS {
 #define MTS_INJECT_SLOT 14         // counters[14] != 0 (set by mts_render from MTSAMD_TEST_INJECT_LOST_PATH, counting kernel variants only):
                                    // the first wave of workgroup 0 drops one hand-over, and the idle bound is that many ticks -- the
                                    // test of the error path (tests/test_gpu_parity.py::test_lost_path_is_reported)
+#define MTS_CROSS_SLOT 3           // counters[3] (counting kernel variants): lane-visits of the class B_CROSS -- mts_debug_cross_visits, tests/test_gpu_cross_class.py
 #define MTS_DIAG_BASE 4            // counters[MTS_DIAG_BASE + 0..5]: code (1 consumer / 2 producer), ring, index, head, tail, workgroup
 enum : uint32_t { STOP_NONE = 0, STOP_CANCEL = 1, STOP_STALL = 2 };
 
@@ -138,7 +141,7 @@ DEV void wg_flush_unfinished(const MTS_CONST_AS void *kernarg, const uint32_t *h
 template <class M, int NT>
 DEV void ring_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt) {
     constexpr bool COUNT = M::COUNT;
-    constexpr int WG = M::WG, NQ = B_DONE;
+    constexpr int WG = M::WG, NQ = M::CROSS ? B_DONE : B_CROSS;      // B_CROSS is the last class: a machine without it keeps the rings before it
     static_assert((WG & (WG - 1)) == 0 && WG <= 32768, "ring indices wrap with a mask and ids are 16 bit");
     static_assert(NT % 64 == 0 && WG % 64 == 0, "whole waves");
     M::template check_shape<NT>();
@@ -160,7 +163,14 @@ DEV void ring_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt) {
     __syncthreads();
 #pragma unroll 1
     for (uint32_t pid0 = tid; pid0 < (uint32_t) WG; pid0 += NT) {   // ---- initialise the paths (integrator.cpp:198) and queue them
-        const WgArgs a = cload_k<WgArgs>(kernarg);
+        // M::OPAQUE_INIT: the loop reads the arguments through an opaque copy of their pointer, as a block does, so that the scene's scalars
+        // are loaded where begin_sample reads them and not ahead of the loop.  Register allocation only -- the flagship kernel spills 177
+        // SGPRs at its head without it and 153 with it -- but it moves whole kernels by up to a per cent either way, so the units choose
+        // (volpath_flat.h: MTS_HOT_DRCP).
+        uint32_t wg_base_u = 0;
+        const MTS_CONST_AS void *ka = kernarg;
+        if constexpr (M::OPAQUE_INIT) ka = block_uniforms(kernarg, wg_base, wg_base_u);
+        const WgArgs a = cload_k<WgArgs>(ka);
         typename M::Machine vm(a.sc, cnt);
         PathEnvT<ColdStoreHbm> e; typename M::State p;
         typename M::Hot hs; hs.base = hot_lds + pid0;
@@ -214,12 +224,13 @@ DEV void ring_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt) {
         }
         // argmax over the NQ rings in three DPP steps: lanes 0..7 hold (avail << 4 | 15 - ring), the maximum of a row's first eight
         // lanes ends up in lane 7 (ties go to the lower ring, as a first-maximum scan would have it); one readlane instead of eight
-        // and no scalar compare chain
+        // and no scalar compare chain.  Nine rings: a fourth step, and the maximum of the row's sixteen lanes is in lane 15.
         uint32_t key = lane < (uint32_t) NQ ? ((avail << 4) | (15u - lane)) : 0u;
         key = max(key, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) key, 0x111 /* row_shr:1 */, 0xf, 0xf, true));
         key = max(key, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) key, 0x112 /* row_shr:2 */, 0xf, 0xf, true));
         key = max(key, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) key, 0x114 /* row_shr:4 */, 0xf, 0xf, true));
-        const uint32_t top_key = (uint32_t) __builtin_amdgcn_readlane((int) key, 7);
+        if constexpr (NQ > 8) key = max(key, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) key, 0x118 /* row_shr:8 */, 0xf, 0xf, true));
+        const uint32_t top_key = (uint32_t) __builtin_amdgcn_readlane((int) key, NQ > 8 ? 15 : 7);
         const uint32_t best = top_key >> 4; sel = 15 - (int) (top_key & 15u);
 #if defined(MTSAMD_BLOCKSTATS)
         if (COUNT) {      // population at snapshot time: finished paths [45], paths waiting in the rings [46], snapshots [47]
@@ -290,6 +301,12 @@ DEV void ring_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt) {
                 case B_WSURF: cls = M::template block<B_WSURF>(kernarg, hot_lds, wg_base, pid, &cnt); break;
                 case B_SURF: cls = M::template block<B_SURF>(kernarg, hot_lds, wg_base, pid, &cnt); break;
                 case B_PHASE: cls = M::template block<B_PHASE>(kernarg, hot_lds, wg_base, pid, &cnt); break;
+                case B_CROSS:                                   // never claimed by a machine without the class
+                    if constexpr (M::CROSS) {
+                        cls = M::template block<B_CROSS>(kernarg, hot_lds, wg_base, pid, &cnt);
+                        if (COUNT && lane == 0) atomicAdd(cload_k<WgArgs>(kernarg).counters + MTS_CROSS_SLOT, (unsigned long long) n);     // lane-visits of the class
+                    }
+                    break;
                 default: cls = M::template block<B_NEW>(kernarg, hot_lds, wg_base, pid, &cnt); break;
             }
         }

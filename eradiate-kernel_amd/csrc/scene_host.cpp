@@ -529,6 +529,7 @@ static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaul
     ds.bsdf_type = hs.bsdfs[(size_t) ds.bsdf].type; ds.bsdf_flags = hs.bsdfs[(size_t) ds.bsdf].flags;
     ds.prim_offset = (int32_t) hs.prims.size();
     hs.shapes.push_back(ds); bbox_expand(hs.scene.bbox, sb);
+    if (i < 64 && ds.bsdf_type == MTS_BSDF_NULL && (ds.bsdf_flags & F_Smooth) == 0 && ds.emitter < 0) hs.scene.cross_mask |= 1ull << i;     // DScene::cross_mask
     const bool triangles = ds.type == MTS_SHAPE_CUBE || ds.type == MTS_SHAPE_MESH;
     for (int k = 0; k < prim_count; ++k) {
         DPrim p; p.shape = i; p.index = k; hs.prims.push_back(p);

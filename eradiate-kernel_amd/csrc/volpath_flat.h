@@ -454,7 +454,30 @@ struct PathEnvT {
 };
 // Scheduling classes: the block a path is waiting for
 enum { B_INT = 0, B_MED /* free-flight step of the main path */, B_SCATTER, B_WSURF, B_SURF, B_PHASE, B_NEW,
-       B_MEDW /* free-flight step of an NEE / direct-light walk */, B_DONE, B_COUNT };
+       B_MEDW /* free-flight step of an NEE / direct-light walk */,
+       B_CROSS /* the main path crosses a null-BSDF boundary that emits nothing: B_SURF's work for such a hit and no more (wg_block) */,
+       B_DONE, B_COUNT };
+// Which ring machines sort their crossings into B_CROSS (wg_block: cross_class): `volpath`, rgb / mono, scalar streams, on the lean units
+// a and b -- the units of the benchmark scenes, where the class was measured -- and on the diagnostic build's general
+// unit, which stands in for them.  Everywhere else the class exists and stays empty: B_SURF is the general block and serves every hit.
+#if MTS_SPEC_N == 3 && (MTS_TRAITS == MT_UNIT_A || MTS_TRAITS == MT_UNIT_B || (defined(MTSAMD_BLOCKSTATS) && MTS_TRAITS == 0))
+#define MTS_CROSS_CLASS 1
+#else
+#define MTS_CROSS_CLASS 0
+#endif
+// MTS_HOT_DRCP: the hot state holds 1 / d (HotFront).  0: the unit's ring kernels form it from d, and their init loop loads the kernel
+// arguments inside its body (ring_driver.h: M::OPAQUE_INIT) -- two changes of the same kind (registers and LDS against instructions)
+// that were measured together, unit by unit, and are kept per unit by what they measured:
+//   a, b           the ninth ring needs the 12 KiB; with the loads ahead of the loop the flagship kernel spills 177 SGPRs (test_abi holds 160);
+//                  their volpathmis kernels lose 0.8 % (C3M) with the short front but the old loop, and nothing with both
+//   h              C2 +0.2 % with both, -1.3 % with neither (under this driver's ten control pairs)
+//   general rgb    with 1 / d loaded its ring kernel spills 19 VGPRs (test_abi holds 16), without 10
+//   spectral, c    keep 1 / d and the old loop: the spectral unit lost 0.7 % (C5S) with both changes and nothing with neither
+#if MTS_CROSS_CLASS || (MTS_SPEC_N == 3 && (MTS_TRAITS == 0 || MTS_TRAITS == MT_UNIT_H))
+#define MTS_HOT_DRCP 0
+#else
+#define MTS_HOT_DRCP 1
+#endif
 
 // What a MEDIUM block reads of MedStep::info.  constexpr accessors: a lean unit's promises (MTS_TRAITS) are constants the front end folds,
 // as in the #if ladders this replaces (three plain bools: 1086 differing assembly lines in lean unit a).
@@ -947,13 +970,15 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
         else end_direct(p, e, spec_s(0.f), 0.f);
     }
     // ================================================================= SURFACE interaction of the main path (volpath.cpp:184-212)
-    template <class E> DEV void blk_surf(PathState &p, const E &e) const {
+    // CROSSING (class B_CROSS, wg_block): every lane has a valid hit on a shape with a null BSDF, which is not smooth, and without an
+    // emitter (DScene::cross_mask) -- the same statements with those facts as constants: no shape record, no emitter term, no NEE.
+    template <bool CROSSING = false, class E> DEV void blk_surf(PathState &p, const E &e) const {
         if (p.st != S_SURF || p.mode != M_MAIN || (p.flags & FL_NEEDS_INT)) return;
         const uint32_t max_depth = (uint32_t) sc.integrator.max_depth;
-        const bool hit = hit_valid(p.si);
+        const bool hit = CROSSING ? true : hit_valid(p.si);
         Surf sf; sf.wi = -p.ray.d; sf.n = f3s(0.f); sf.sh.s = sf.sh.t = sf.sh.n = f3s(0.f);
-        int emitter = sc.environment, bsdf_id = 0;
-        if (hit) {
+        int emitter = CROSSING ? -1 : sc.environment, bsdf_id = 0;
+        if (!CROSSING && hit) {
             WATERFALL_BEGIN(p.si.shape, su)
                 const DShape s = cload(sc.shapes + su);
                 emitter = s.emitter; bsdf_id = s.bsdf;
@@ -966,9 +991,11 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
         if (!hit) { p.flags &= ~FL_ALIVE; p.st = S_TOP; return; }
         p.st = S_BSDF;
         bool active_e = false;
-        WATERFALL_BEGIN(bsdf_id, bu)
-            active_e = (cload(sc.bsdfs + bu).flags & F_Smooth) != 0 && (p.depth + 1 < max_depth);
-        WATERFALL_END
+        if constexpr (!CROSSING) {
+            WATERFALL_BEGIN(bsdf_id, bu)
+                active_e = (cload(sc.bsdfs + bu).flags & F_Smooth) != 0 && (p.depth + 1 < max_depth);
+            WATERFALL_END
+        }
         if (!active_e) return;
         Spec emitter_val;                                      // volpath.cpp:200-212 -> sample_emitter :261-281
         DirSample ds = sample_emitter_direction(sc, p.si.p, p.rng.next_2d(), false, emitter_val MTS_CX);
@@ -989,7 +1016,8 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
         p.mode = M_NEE; p.st = S_TOP;
     }
     // ================================================================= BSDF sampling (volpath.cpp:214-252)
-    template <class E> DEV void blk_bsdf(PathState &p, const E &e) const {
+    // CROSSING: the BSDF is the null one (blk_surf) -- bsdf_sample on a record that says so, instead of the shape's own
+    template <bool CROSSING = false, class E> DEV void blk_bsdf(PathState &p, const E &e) const {
         if (p.st != S_BSDF) return;
         const uint32_t max_depth = (uint32_t) sc.integrator.max_depth;
         Surf sf; int bsdf_id = 0, is_tr = 0, ext = -1, inte = -1;
@@ -1001,10 +1029,15 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
         const float s1 = p.rng.next_1d(); const F2 s2 = p.rng.next_2d();
         BSDFSample bs; Spec bsdf_val;
         const SpecCtx cx = ctx(p); (void) cx;
-        WATERFALL_BEGIN(bsdf_id, bu)
-            const DBsdf bsdf = cload(sc.bsdfs + bu);
-            bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs MTS_CXI(bu));
-        WATERFALL_END
+        if constexpr (CROSSING) {
+            DBsdf bsdf = {}; bsdf.type = MTS_BSDF_NULL;            // null.cpp:41-58 reads nothing else of it
+            bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs MTS_CXI(bsdf_id));
+        } else {
+            WATERFALL_BEGIN(bsdf_id, bu)
+                const DBsdf bsdf = cload(sc.bsdfs + bu);
+                bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs MTS_CXI(bu));
+            WATERFALL_END
+        }
         p.thr = p.thr * bsdf_val;
         p.eta *= bs.eta;
         p.ray = spawn_ray(p.si.p, to_world(sf.sh, bs.wo));
@@ -1049,6 +1082,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
             case B_SCATTER: blk_scatter(p, e); break;
             case B_WSURF: blk_wsurf(p, e); break;
             case B_SURF: blk_surf(p, e); blk_bsdf(p, e); break;     // no NEE at this surface: the BSDF is sampled in the same visit
+            case B_CROSS: blk_surf<true>(p, e); blk_bsdf<true>(p, e); break;
             case B_PHASE: blk_phase(p, e); break;
             default: break;
         }
@@ -1081,7 +1115,7 @@ DEV void volpath_pixel_flat(const DScene &sc, Pcg32 &rng, const DBlock &blk, uin
         int cls = vm.classify(p);
         if (cls == B_MEDW) cls = B_MED;                        // this driver runs the generic MEDIUM block for both
         int sel = B_MED, best = -1;
-        for (int b = 0; b < B_DONE; ++b) { int v = __popcll(__ballot(cls == b)); if (v > best) { best = v; sel = b; } }
+        for (int b = 0; b < B_CROSS; ++b) { int v = __popcll(__ballot(cls == b)); if (v > best) { best = v; sel = b; } }     // classify() never says B_CROSS
         if (best == 0) continue;
 #if defined(MTSAMD_BLOCKSTATS)
         if (COUNT) {
@@ -1108,18 +1142,26 @@ DEV void volpath_pixel_flat(const DScene &sc, Pcg32 &rng, const DBlock &blk, uin
 // Every block class loads / stores only the fields it can touch (ClassFields), which keeps the blocks' register budget small.
 // depth shares a dword with the packed small fields (15 bits: a path of more than 32767 scattering events would need to
 // survive Russian roulette with probability < 0.95^32000).
-// The sixteen dwords every tracking step touches come first: an LDS instruction reaches 64 KB (16 fields of 1024 paths) from its
-// address register, later fields cost an address computation each.
-enum { H_RNG = 0, H_O = 2, H_D = 5, H_DRCP = 8, H_MINT = 11, H_MAXT = 12, H_SIT = 13, H_MEDIUM = 14,
-       H_PACKED = 15 /* st, mode, channel, flags, class, depth */, H_THR = 16, H_TRANS = H_THR + MTS_SPEC_DW, H_WA = H_TRANS + MTS_SPEC_DW,
+// The dwords every tracking step touches come first: an LDS instruction reaches 64 KB (16 fields of 1024 paths) from its address
+// register, later fields cost an address computation each.
+// MTS_HOT_DRCP: whether 1 / d is part of the state.  It is vrcp(d) wherever a ray is made (make_ray, resume_main) and pm_rcp is a
+// function of its argument's bits alone (tests/micro/rcp_exhaustive.hip), so a block that loads d can form it again -- 12 vector
+// instructions in place of three LDS reads, three LDS writes less wherever d is stored, 12 KiB of LDS at 1024 paths.  The units with
+// the ninth ring (MTS_CROSS_CLASS: lean a and b, all their ring kernels) do, which is where that ring's 2 KiB come from, and so do unit h
+// and the general rgb / mono unit (MTS_HOT_DRCP above); then the front
+// is thirteen dwords and the main path's throughput sits inside the 64 KB reach as well.  The other units keep the three dwords.
+enum { H_RNG = 0, H_O = 2, H_D = 5, H_DRCP = 8 /* MTS_HOT_DRCP: three dwords, else none */, H_MINT = 8 + 3 * MTS_HOT_DRCP, H_MAXT = H_MINT + 1,
+       H_SIT = H_MAXT + 1, H_MEDIUM = H_SIT + 1, H_PACKED = H_MEDIUM + 1 /* st, mode, channel, flags, class, depth */,
+       H_FRONT = H_PACKED + 1 /* 16 or 13: the dwords of HotFront; a machine's own fields follow */,
+       H_THR = H_FRONT, H_TRANS = H_THR + MTS_SPEC_DW, H_WA = H_TRANS + MTS_SPEC_DW,
        H_WB = H_WA + 1, H_ETA = H_WB + 1, H_RES = H_ETA + 1, H_SIX = H_RES + MTS_SPEC_DW /* si.p, si.uv, si.shape, si.prim */,
 #if MTS_SPEC_N == 3
-       H_COUNT = H_SIX + 7 };                                   // 35
+       H_COUNT = H_SIX + 7 };                                   // 35, or 32 without 1 / d
 #else
        H_WL = H_SIX + 7 /* the sample's four wavelengths */, H_COUNT = H_WL + 4 };      // 42
 #endif
 
-enum : uint32_t { G_RNG = 1, G_O = 2, G_D = 4 /* d and 1/d */, G_MINT = 8, G_MAXT = 16, G_SIT = 32 /* si.t */, G_SIX = 64 /* rest of si */,
+enum : uint32_t { G_RNG = 1, G_O = 2, G_D = 4 /* d and 1/d (stored, or formed on load: MTS_HOT_DRCP) */, G_MINT = 8, G_MAXT = 16, G_SIT = 32 /* si.t */, G_SIX = 64 /* rest of si */,
                   G_MED = 128, G_THR = 256, G_RES = 512, G_ETA = 1024, G_TRANS = 2048, G_WA = 4096, G_WB = 8192,
 #if MTS_SPEC_N == 3
                   G_WL = 0, G_ALL = 16383 };
@@ -1152,13 +1194,17 @@ template <> struct ClassFields<B_SCATTER> {
     static constexpr uint32_t load = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_MED | G_THR | G_TRANS | G_WA | G_WB | G_WL,
                               store = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_TRANS | G_WA | G_WB | (MTS_FUSE_INT ? G_SIX : 0u);
     static constexpr bool defer = true; };
+template <> struct ClassFields<B_CROSS> {        // no emitter sample, no walk, no cold record: the smallest set that samples the null BSDF and spawns the ray
+    static constexpr uint32_t load = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_SIX | G_MED | G_THR | G_ETA | G_WL,
+                              store = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_MED | G_THR | G_ETA;
+    static constexpr bool defer = false; };
 template <> struct ClassFields<B_PHASE> {
     static constexpr uint32_t load = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_MED | G_THR | G_ETA | G_WL,
                               store = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_THR | (MTS_FUSE_INT ? G_SIX : 0u);
     static constexpr bool defer = true; };
 
 // The front of a ring machine's hot store, shared by HotStore below and MisHotStore (volpathmis_flat.h): the LDS accessors, the packed
-// dword, and the eight field groups G_RNG .. G_MED over the sixteen-dword layout H_RNG .. H_PACKED.  SIX: where the machine keeps the
+// dword, and the eight field groups G_RNG .. G_MED over the layout H_RNG .. H_PACKED (sixteen dwords, thirteen without 1 / d).  SIX: where the machine keeps the
 // rest of the hit (behind its own fields).  The packed dword is stored / unpacked by the derived store, where its own order has it.
 template <int WG, int SIX>
 struct HotFront {
@@ -1186,7 +1232,7 @@ struct HotFront {
     template <uint32_t M, class P> DEV void store_front(const P &p) const {
         if (M & G_RNG) { u(H_RNG) = (uint32_t) p.rng.state; u(H_RNG + 1) = (uint32_t) (p.rng.state >> 32); }
         if (M & G_O) put3(H_O, p.ray.o);
-        if (M & G_D) { put3(H_D, p.ray.d); put3(H_DRCP, p.ray.d_rcp); }
+        if (M & G_D) { put3(H_D, p.ray.d); if (MTS_HOT_DRCP) put3(H_DRCP, p.ray.d_rcp); }
         if (M & G_MINT) putf(H_MINT, p.ray.mint);
         if (M & G_MAXT) putf(H_MAXT, p.ray.maxt);
         if (M & G_SIT) putf(H_SIT, p.si.t);
@@ -1199,7 +1245,7 @@ struct HotFront {
         p.rng.state = 0; p.rng.inc = (PCG32_DEFAULT_STREAM << 1u) | 1u;
         if (M & G_RNG) p.rng.state = (uint64_t) u(H_RNG) | ((uint64_t) u(H_RNG + 1) << 32);
         p.ray.o = (M & G_O) ? get3(H_O) : f3s(0.f);
-        p.ray.d = (M & G_D) ? get3(H_D) : f3s(0.f); p.ray.d_rcp = (M & G_D) ? get3(H_DRCP) : f3s(0.f);
+        p.ray.d = (M & G_D) ? get3(H_D) : f3s(0.f); p.ray.d_rcp = (M & G_D) ? (MTS_HOT_DRCP ? get3(H_DRCP) : vrcp(p.ray.d)) : f3s(0.f);
         p.ray.mint = (M & G_MINT) ? f(H_MINT) : 0.f; p.ray.maxt = (M & G_MAXT) ? f(H_MAXT) : 0.f;
         p.si.t = (M & G_SIT) ? f(H_SIT) : pm_inf();
         p.si.p = f3s(0.f); p.si.uv.x = p.si.uv.y = 0.f; p.si.shape = -1; p.si.prim = 0;
@@ -1239,7 +1285,7 @@ struct HotStore : HotFront<WG, H_SIX> {
     template <uint32_t M> DEV void load_add(PathState &p) const {
         if (M & G_RNG) p.rng.state = (uint64_t) u(H_RNG) | ((uint64_t) u(H_RNG + 1) << 32);
         if (M & G_O) p.ray.o = get3(H_O);
-        if (M & G_D) { p.ray.d = get3(H_D); p.ray.d_rcp = get3(H_DRCP); }
+        if (M & G_D) { p.ray.d = get3(H_D); p.ray.d_rcp = MTS_HOT_DRCP ? get3(H_DRCP) : vrcp(p.ray.d); }
         if (M & G_MINT) p.ray.mint = f(H_MINT);
         if (M & G_MAXT) p.ray.maxt = f(H_MAXT);
         if (M & G_SIT) p.si.t = f(H_SIT);
@@ -1315,6 +1361,22 @@ DEV const MTS_CONST_AS void *block_uniforms(const MTS_CONST_AS void *kernarg_, u
     return kernarg;
 }
 
+// The class of a main-path lane that classify() sends to B_SURF: B_CROSS when it arrives there from S_SURF with a valid hit on a shape
+// of DScene::cross_mask (null BSDF, not smooth, no emitter; shapes 0 .. 63), else B_SURF -- which is always right, being the general block,
+// so every doubtful case (no hit, S_BSDF, a shape beyond the mask) stays there.  HAVE_SHAPE: the block holds si.shape in registers; a
+// tracking block does not, and its leaving lanes read that one dword.
+// The mask is fetched where it is needed (two dwords of the kernel arguments, a scalar load), not kept from the head of the block.
+struct MaskWords { uint32_t lo, hi; };
+template <bool HAVE_SHAPE, int WG>
+DEV int cross_class(int cls, const PathState &p, const HotStore<WG> &hs, const MTS_CONST_AS void *kernarg) {
+    if (cls == B_SURF && p.st == S_SURF && hit_valid(p.si)) {
+        const uint32_t shape = HAVE_SHAPE ? (uint32_t) p.si.shape : hs.u(H_SIX + 5);
+        const MaskWords m = cload_k<MaskWords>((const MTS_CONST_AS char *) kernarg + offsetof(WgArgs, sc) + offsetof(DScene, cross_mask));
+        if (shape < 64u && (((shape < 32u ? m.lo : m.hi) >> (shape & 31u)) & 1u) != 0u) cls = B_CROSS;
+    }
+    return cls;
+}
+
 // One block of class C for the path `pid`: load, run (repeat while the path stays in class C and enough lanes do), store.
 // WF: wavefront (gpu_*) streams -- one PCG32 per (pixel, sample), seeded with TEA (sampler.cpp:89-92).  The hot state holds only the
 // generator's 64-bit state; its increment, which for the scalar variants' streams is the default stream's constant, is recomputed here
@@ -1332,11 +1394,24 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
     PathEnvT<ColdStoreHbm> e; wg_env<WG>(a, wg_base, pid, e);
     HotStore<WG> hs; hs.base = hot_lds + pid;
     typedef ClassFields<C> CF;
+    // VolpathRing::CROSS, in the blocks a main path can leave towards a surface WITH a hit: the intersection itself, a tracking step
+    // that ends at the cached hit, and the end of a direct-light walk, which hands the parked hit back.  Every other block spawns a ray
+    // (si.t = inf) or starts a walk; the rare deferred tail could (end_direct) and leaves its crossings to B_SURF.
+    constexpr bool CROSS = MTS_CROSS_CLASS && !WF && !MOMENT && (C == B_INT || C == B_MED || C == B_WSURF);
+    constexpr bool HAVE_SHAPE = ((CF::load | CF::store) & G_SIX) != 0;
     PathState p;
     if (COUNT && C == B_MED) MTS_SEG_BEGIN(*cnt);
     hs.template load_m<CF::load>(p);
     if (WF && C != B_INT) p.rng.inc = wavefront_increment(a.sc.sensor, e.blk, e.lx, e.ly, __float_as_uint(e.cold.f(C_SAMPLE)));
     if (COUNT && C == B_MED) MTS_SEG(*cnt, 0);
+#if defined(MTSAMD_BLOCKSTATS)
+    if (COUNT && C == B_SURF) {                               // [9]: the lane-visits of this class that are null-boundary crossings (tools/cross_class_stats.py)
+        bool cross = p.st == S_SURF && hit_valid(p.si);
+        if (cross) { const DShape &s = a.sc.shapes[p.si.shape]; cross = s.bsdf_type == MTS_BSDF_NULL && (s.bsdf_flags & F_Smooth) == 0 && s.emitter < 0; }     // DScene::cross_mask's condition
+        const unsigned long long m = __ballot(cross);
+        if (__builtin_amdgcn_readfirstlane((int) (threadIdx.x & 63)) == (int) (threadIdx.x & 63)) atomicAdd(&g_blockstats[9], (unsigned long long) __popcll(m));
+    }
+#endif
     int cls;
     // A tracking step is most often followed by another one (null collisions): while at least half of the wave's lanes stay in this
     // class the block runs again on the registers it holds -- no LDS round trip, no ring push, no claim for those paths; lanes that
@@ -1390,6 +1465,7 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
         vm.top(p, e);
         cls = vm.classify(p);
     }
+    if constexpr (CROSS) cls = cross_class<HAVE_SHAPE>(cls, p, hs, kernarg);
     if ((MTS_CHAIN & 8) && C == B_MED && cls == B_SCATTER) {   // a real collision: emitter sample and the start of its walk (volpath.cpp:162-167)
         vm.blk_scatter(p, e);
         vm.template top<true>(p, e);
@@ -1421,6 +1497,8 @@ struct VolpathRing {
     typedef HotStore<WG_> Hot;
     typedef VolpathMachine<COUNT_, MOMENT, MTS_GEOM_LDS != 0> Machine;
     static constexpr bool GEOM_TABLE = Machine::GEOM_TABLE;      // the driver fills the geometry table
+    static constexpr bool CROSS = MTS_CROSS_CLASS && !WF && !MOMENT;      // the machine fills the ring of B_CROSS (wg_block); else the driver keeps eight rings
+    static constexpr bool OPAQUE_INIT = !MTS_HOT_DRCP;                    // see MTS_HOT_DRCP
     template <int NT> DEV static void check_shape() { static_assert(NT <= WG_, "a thread per path at most"); }
     DEV static void init_idle(State &p) {
         p.medium = -1; p.thr = p.res = p.trans = spec_s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;

@@ -449,10 +449,10 @@ template <> struct MisClassFields<B_PHASE> {
                               store = K_RNG | K_O | K_D | K_MINT | K_MAXT | K_SIT | K_PF | K_PN;
     static constexpr bool defer = true; };
 
-// MisHotStore's own dwords, behind HotFront's sixteen (H_RNG .. H_PACKED)
-enum { MH_WA = 16, MH_WB = 17, MH_ETA = 18, MH_RES = 19, MH_LSP = MH_RES + MTS_SPEC_DW, MH_SIX = MH_LSP + 3,
+// MisHotStore's own dwords, behind HotFront's (H_RNG .. H_PACKED: H_FRONT = 16 dwords, 13 in the units that do not store 1 / d)
+enum { MH_WA = H_FRONT, MH_WB = MH_WA + 1, MH_ETA = MH_WB + 1, MH_RES = MH_ETA + 1, MH_LSP = MH_RES + MTS_SPEC_DW, MH_SIX = MH_LSP + 3,
 #if MTS_SPEC_N == 3
-       MH_W = 32 };
+       MH_W = MH_SIX + 7 };                                         // 32 (29)
 #else
        MH_WL = MH_SIX + 7, MH_W = MH_WL + 4 };                      // 37
 #endif
@@ -542,6 +542,8 @@ struct VolpathMisRing {
     typedef MisHotStore<WG_, SPEC> Hot;
     typedef VolpathMisMachine<COUNT_, SPEC, MOMENT> Machine;
     static constexpr bool GEOM_TABLE = false;                  // no geometry table: the driver fills none for this machine
+    static constexpr bool OPAQUE_INIT = !MTS_HOT_DRCP;          // volpath_flat.h: MTS_HOT_DRCP
+    static constexpr bool CROSS = false;                       // ... and no ring of B_CROSS: the machine never names the class
     template <int NT> DEV static void check_shape() { static_assert(NT <= 2 * WG_, "up to two threads per path (768 on 512: a third wave per SIMD)"); }
     DEV static void init_idle(State &p) {
         p.medium = -1; p.res = spec_s(0.f); p.lsp = f3s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;
