@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["kernels.hip", "kernels_spectral.hip", "kernels_lean_a.hip", "kernels_lean_b.hip", "kernels_lean_c.hip", "kernels_lean_s.hip", "kernels_lean_h.hip", "kernels_lean_p.hip", "kernels_lean_ps.hip", "scene_host.cpp", "capi.cpp"]
-HEADERS = ["pmath.h", "dmath.h", "dscene.h", "integrator_dev.h", "volpath_flat.h", "volpathmis_flat.h", "ring_driver.h", "launch.h", "kernel_names.h", "scene_host.h", "render_plan.h", "render_plan.cpp", "cie_tables.h"]
+HEADERS = ["pmath.h", "dmath.h", "dscene.h", "unit_config.h", "integrator_dev.h", "volpath_flat.h", "volpathmis_flat.h", "ring_driver.h", "launch.h", "kernel_names.h", "scene_host.h", "render_plan.h", "render_plan.cpp", "cie_tables.h"]
 MARKER = b"MTSAMD_BUILD_ID="
 # hipcc flags of the product build (build.py).  Flags that matter for parity with the CPU restatement: see build.py's docstring.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",

@@ -7,7 +7,7 @@
 // Citations are relative to /root/reference.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "dscene.h"
+#include "unit_config.h"
 #include "dmath.h"
 #include "../../include/mtsamd.h"
 
@@ -18,17 +18,8 @@
 // with MTS_TRAITS != 0 (kernels_lean_*.hip) PROMISES the properties below; the host checks them per scene (scene_host.cpp:
 // scene_traits) and mts_render picks the leanest kernel whose promises the scene keeps.  Same source, same arithmetic: the promised-away
 // branches are simply never compiled (C3 562 -> 629, C4 397 -> 469 Msamples/s on the 256-spp probes, profiles/r04_ab_experiments.log).
-// (the MT_* bits themselves live in dscene.h: the host computes them per scene)
-#ifndef MTS_TRAITS
-#define MTS_TRAITS 0
-#endif
-#if MTS_SPEC_N == 3
-#if !defined(MTS_VARIANT_NS)
-#define MTS_VARIANT_NS v_rgb
-#endif
-#elif !defined(MTS_VARIANT_NS)
-#define MTS_VARIANT_NS v_spectral
-#endif
+// (the MT_* bits themselves live in dscene.h: the host computes them per scene; which unit promises what, and every other switch that
+// differs between the units, is unit_config.h)
 namespace mtsamd {
 inline namespace MTS_VARIANT_NS {
 
@@ -328,11 +319,8 @@ DEV Hit ray_intersect_preliminary(const DScene &sc, DRay ray) {
 // lane, indexed by s.prim_offset + h.prim, instead of through per-lane global loads behind the scalar load of the shape record
 // (profiles/geom_table_ab.txt).  The rows are MTS_GEOM_ATTR_STRIDE = 25 dwords apart: an odd stride puts the rows of the sixteen
 // primitives on distinct banks (24 would map primitives k and k + 8 to the same ones), lanes on one primitive broadcast.  A unit
-// asks for the table with MTS_GEOM_LDS (kernels_lean_{a,h}.hip); only functions instantiated with TAB = true reference it, so no
+// asks for the table with MTS_GEOM_LDS (unit_config.h); only functions instantiated with TAB = true reference it, so no
 // other kernel's LDS changes.  The primitive list itself stays on scalar loads: walked from LDS records it measured slower.
-#ifndef MTS_GEOM_LDS
-#define MTS_GEOM_LDS 0
-#endif
 #define MTS_GEOM_LDS_PRIMS 16
 #define MTS_GEOM_ATTR_STRIDE 25
 #define MTS_GEOM_LDS_BYTES (MTS_GEOM_LDS_PRIMS * MTS_GEOM_ATTR_STRIDE * 4)

@@ -7,26 +7,18 @@
 // gathers and one film update per pixel.  Citations are relative to /root/reference.
 // Compiled twice into libmtsamd.so: as it is (MTS_SPEC_N = 3: the rgb / mono variants, all kernels) and through kernels_spectral.hip
 // (MTS_SPEC_N = 4: the spectral variant: `volpath` on the regrouping machine with 256-path workgroups, `path` per lane; launchers carry
-// the suffix _spectral).
+// the suffix _spectral), and once per lean unit through kernels_lean_*.hip (MTS_UNIT).  What a unit is -- its namespace, its launchers'
+// suffix, its traits and the switches of its ring kernels -- is one row of unit_config.h (through integrator_dev.h).
 #include <hip/hip_runtime.h>
 #define PM_TABLES_IN_LDS 1            // pmath.h: LDS copies of the two hot lookup tables; every kernel below fills them first
-#if defined(MTSAMD_BLOCKSTATS) && !defined(MTS_SPEC_N) && !defined(MTS_GEOM_LDS)
-#define MTS_GEOM_LDS 1                // the diagnostic build has no lean units: its general rgb ring kernels stand in for them, table included
-#endif
 #include "integrator_dev.h"
 #include "volpath_flat.h"
 #include "volpathmis_flat.h"
 #include "ring_driver.h"
-#if defined(MTS_LEAN)               // kernels_lean_*.hip: the regrouping kernels once more, for scenes that keep the promises of MTS_TRAITS
-#define MTS_LAUNCHER_CAT2(a, b) a##b
-#define MTS_LAUNCHER_CAT(a, b) MTS_LAUNCHER_CAT2(a, b)
-#define MTS_LAUNCHER(name) MTS_LAUNCHER_CAT(name, MTS_LEAN)
-#elif MTS_SPEC_N == 3
-#define MTS_LAUNCHER(name) name
-#else
-#define MTS_LAUNCHER(name) name##_spectral
-#endif
 #include "launch.h"
+static_assert(MTS_UNIT_ID_GENERAL == mtsamd::UNIT_GENERAL && MTS_UNIT_ID_A == mtsamd::UNIT_A && MTS_UNIT_ID_B == mtsamd::UNIT_B && MTS_UNIT_ID_S == mtsamd::UNIT_S &&
+              MTS_UNIT_ID_P == mtsamd::UNIT_P && MTS_UNIT_ID_PS == mtsamd::UNIT_PS && MTS_UNIT_ID_H == mtsamd::UNIT_H && MTS_UNIT_ID_C == mtsamd::UNIT_C &&
+              mtsamd::UNIT_COUNT == 8, "unit_config.h numbers the units as kernel_names.h does");
 
 namespace mtsamd {
 inline namespace MTS_VARIANT_NS {
@@ -220,13 +212,10 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
 // FLAT = true: volpath as the flat state machine of volpath_flat.h (the production kernel of the metric);
 // FLAT = false: the nested formulation of integrator_dev.h (path and volpathmis; volpath cross-check, MTSAMD_KERNEL=nested),
 // one instantiation per integrator (INTEG = NI_*).
-#ifndef MTS_NESTED_WAVES
 #define MTS_NESTED_WAVES 1
-#endif
-#if !defined(MTS_PATH_WAVES) && MTS_SPEC_N != 3
+#if MTS_SPEC_N != 3
 #define MTS_PATH_WAVES 3      // four-wide spectra: the register budget of four waves per SIMD is not met
-#endif
-#ifndef MTS_PATH_WAVES
+#else
 #define MTS_PATH_WAVES 4      // measured on the cornell box: 1 -> 1631, 3 -> 1717, 4 -> 2355, 5 -> 1870, 6 -> 1241 Msamples/s
 #endif
 template <bool COUNT, bool FLAT, int INTEG>
@@ -554,14 +543,11 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
 #if MTS_SPEC_N != 3           // the spectral variant's machines: 256-path workgroups
     // register budget of three waves per SIMD (three 256-path workgroups per CU): with the spectral grid lookups inline the allocator needs the bound
     if (a.variant == kv::ring(256) && volpath) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 3));
-    if (a.variant == kv::ring(256) && mis && spec_mis) return launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256));
+    if (a.variant == kv::ring(256) && mis && spec_mis) return launch_wg(a, threads, 256, MTS_MIS_THREADS, MTS_BY_COUNT(render_kernel_wga_mis, true, 256, MTS_MIS_THREADS));
 #else
     if (a.variant == kv::ring(1024) && volpath) return launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4));
-#if defined(MTS_LEAN_MIS_768)   // the 512 paths served by 768 threads: three waves per SIMD want <= 168 VGPRs, which this unit's kernel meets (C3M 375 -> 393)
-    if (a.variant == kv::ring(512) && mis && spec_mis) return launch_wg(a, threads, 512, 768, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 768));
-#else
-    if (a.variant == kv::ring(512) && mis && spec_mis) return launch_wg(a, threads, 512, 512, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 512));
-#endif
+    // the 512 paths are served by as many threads as the unit's kernel has registers for (unit_config.h: 768 in unit a)
+    if (a.variant == kv::ring(512) && mis && spec_mis) return launch_wg(a, threads, 512, MTS_MIS_THREADS, MTS_BY_COUNT(render_kernel_wga_mis, true, 512, MTS_MIS_THREADS));
 #endif
     return hipErrorInvalidConfiguration;
 #else                         // the general kernels
@@ -582,7 +568,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     }
     if (kv::is_ring(a.variant) && mis) {                          // the same machinery, 512 or 256 paths per workgroup
         if (a.variant == kv::ring(512))
-            return launch_wg(a, threads, 512, 512, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 512, 512) : MTS_BY_COUNT(render_kernel_wga_mis, false, 512, 512));
+            return launch_wg(a, threads, 512, MTS_MIS_THREADS, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 512, MTS_MIS_THREADS) : MTS_BY_COUNT(render_kernel_wga_mis, false, 512, MTS_MIS_THREADS));
         if (a.variant == kv::ring(256))
             return launch_wg(a, threads, 256, 256, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256) : MTS_BY_COUNT(render_kernel_wga_mis, false, 256, 256));
         return hipErrorInvalidConfiguration;
@@ -595,7 +581,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     if (kv::is_ring(a.variant) && volpath)
         return a.variant == kv::ring(256) ? launch_wg(a, threads, 256, 256, MTS_BY_COUNT(render_kernel_wga, 256, 256, 2)) : hipErrorInvalidConfiguration;
     if (kv::is_ring(a.variant) && mis)
-        return a.variant == kv::ring(256) ? launch_wg(a, threads, 256, 256, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 256, 256) : MTS_BY_COUNT(render_kernel_wga_mis, false, 256, 256))
+        return a.variant == kv::ring(256) ? launch_wg(a, threads, 256, MTS_MIS_THREADS, spec_mis ? MTS_BY_COUNT(render_kernel_wga_mis, true, 256, MTS_MIS_THREADS) : MTS_BY_COUNT(render_kernel_wga_mis, false, 256, MTS_MIS_THREADS))
                                   : hipErrorInvalidConfiguration;
 #endif
     if (integ == MTS_INTEGRATOR_PATH)                         // flat: one loop over path segments with regeneration (path_pixel_flat)

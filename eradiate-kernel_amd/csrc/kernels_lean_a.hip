@@ -4,10 +4,6 @@
 // (122 VGPRs, no spilled VGPR dword, 28 B of scratch against 384).  Same source as kernels.hip, same arithmetic: the promised-away branches
 // are not compiled.  mts_render selects it from HostScene::traits (render_plan.cpp: choose_kernel); MTSAMD_LEAN=0 keeps every scene on the general kernels.
 #if !defined(MTSAMD_BLOCKSTATS)
-#define MTS_LEAN _lean_a
-#define MTS_VARIANT_NS v_rgb_lean_a
-#define MTS_LEAN_MIS_768 1     // `volpathmis`: 164 VGPRs here (general kernel: 193) -- room for a third wave per SIMD, 768 threads on the 512 paths
-#define MTS_TRAITS MT_UNIT_A      // dscene.h
-#define MTS_GEOM_LDS 1           // integrator_dev.h: small scenes keep their triangles' attribute rows in LDS (the volpath rings)
+#define MTS_UNIT MTS_UNIT_ID_A     // unit_config.h: this unit's row of the table
 #include "kernels.hip"
 #endif

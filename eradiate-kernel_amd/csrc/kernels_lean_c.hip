@@ -2,8 +2,6 @@
 // heterogeneous grey media on pair grids: no spheres, no area emitters, no nested blendphase; rpv, blend-weight grids and the BVH allowed.
 // The traversal stays the one real function of the kernel (bvh_intersect: its loop keeps its registers out of the blocks that call it).
 #if !defined(MTSAMD_BLOCKSTATS)
-#define MTS_LEAN _lean_c
-#define MTS_VARIANT_NS v_rgb_lean_c
-#define MTS_TRAITS MT_UNIT_C      // dscene.h
+#define MTS_UNIT MTS_UNIT_ID_C     // unit_config.h: this unit's row of the table
 #include "kernels.hip"
 #endif

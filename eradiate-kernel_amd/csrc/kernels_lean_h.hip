@@ -2,9 +2,6 @@
 // primitive list without spheres, no area emitters, no nested blendphase; rpv allowed.  A homogeneous atmosphere over a surface (C2) is one:
 // the tracking step keeps neither the slab test nor a grid lookup.
 #if !defined(MTSAMD_BLOCKSTATS)
-#define MTS_LEAN _lean_h
-#define MTS_VARIANT_NS v_rgb_lean_h
-#define MTS_TRAITS MT_UNIT_H      // dscene.h
-#define MTS_GEOM_LDS 1           // integrator_dev.h: small scenes keep their triangles' attribute rows in LDS (the volpath rings)
+#define MTS_UNIT MTS_UNIT_ID_H     // unit_config.h: this unit's row of the table
 #include "kernels.hip"
 #endif

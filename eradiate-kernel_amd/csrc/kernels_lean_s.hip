@@ -3,9 +3,6 @@
 // walked primitive list without spheres, no area emitters and no nested blendphase (rpv and blend-weight grids allowed): the layered
 // atmosphere as Eradiate renders it (C5S, C5SB under nbins, C5SM under volpathmis).
 #if !defined(MTSAMD_BLOCKSTATS)
-#define MTS_SPEC_N 4
-#define MTS_LEAN _lean_s
-#define MTS_VARIANT_NS v_spectral_lean
-#define MTS_TRAITS MT_UNIT_B      // dscene.h
+#define MTS_UNIT MTS_UNIT_ID_S     // unit_config.h: this unit's row of the table
 #include "kernels.hip"
 #endif

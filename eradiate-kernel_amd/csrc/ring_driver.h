@@ -166,7 +166,7 @@ DEV void ring_workgroup_async(const MTS_CONST_AS void *kernarg, Counters &cnt) {
         // M::OPAQUE_INIT: the loop reads the arguments through an opaque copy of their pointer, as a block does, so that the scene's scalars
         // are loaded where begin_sample reads them and not ahead of the loop.  Register allocation only -- the flagship kernel spills 177
         // SGPRs at its head without it and 153 with it -- but it moves whole kernels by up to a per cent either way, so the units choose
-        // (volpath_flat.h: MTS_HOT_DRCP).
+        // (unit_config.h: MTS_OPAQUE_INIT, with MTS_HOT_DRCP).
         uint32_t wg_base_u = 0;
         const MTS_CONST_AS void *ka = kernarg;
         if constexpr (M::OPAQUE_INIT) ka = block_uniforms(kernarg, wg_base, wg_base_u);

@@ -42,22 +42,13 @@ inline namespace MTS_VARIANT_NS {
 #else
 #define MTS_FILM_STRIDE(sc) ((size_t) (sc).film_channels)          // X, Y, Z, A, W (+ two AOV channels per spectral bin: nbins / bins)
 #endif
-// Blocks that run a path's NEXT block in the same visit (bit mask; wg_block).  A visit costs a ring push, a claim and an LDS round trip
-// of the state, but what runs in place runs on the lanes that want it only.  Measured one by one (round 3, profiles/r03_ab_experiments.log;
-// C3 512 x 512 x 256 / C4 1024 x 1024 x 64, Msamples/s against 547 / 267 without; all bit-identical):
-//   1  walk SURFACE twice: a walk that leaves through a boundary face with nothing behind it (queue_intersection: the new ray
-//      misses the scene's box, no INTERSECT visit) comes straight back to this class, only to end.  569 / 268: ON.
-//   2  ... and then the PHASE sample of the main path the ended walk hands back to: 567 / 258 together with 1.
-//   4  the walk's MEDIUM block runs the SURFACE step(s) of the lanes whose walk left the medium: 540 / 229 together with 1 and 2.
-//   8  the main path's MEDIUM block runs SCATTER (emitter sample, start of the walk) for its real collisions: 564 / 250 with 1.
-//  16  main-path SURFACE twice (a ray that leaves through a boundary face into nothing ends the sample): 564 / 267 with 1.
-// Only the first pays: its second round is a handful of instructions, every other candidate runs real work on a thinned wave.
-#ifndef MTS_CHAIN
-#define MTS_CHAIN 1
-#endif
-#ifndef MTS_REPEAT_MIN_W
+// A block that runs a path's NEXT block in the same visit (wg_block, mis_block) saves a ring push, a claim and an LDS round trip of the
+// state, but what runs in place runs on the lanes that want it only.  One such continuation is built in: walk SURFACE twice -- a walk
+// that leaves through a boundary face with nothing behind it (queue_intersection: the new ray misses the scene's box, no INTERSECT
+// visit) comes straight back to this class, only to end; its second round is a handful of instructions (C3 547 -> 569 Msamples/s).
+// Four others (the PHASE sample after the ended walk, the walk's SURFACE steps and SCATTER inside the MEDIUM blocks, main-path SURFACE
+// twice) ran real work on a thinned wave and measured slower; they were removed with their switch.
 #define MTS_REPEAT_MIN_W 32        // MTS_REPEAT_MIN for the walks' class: 16 and 48 measured 539 / 265 and 536 / 265
-#endif
 #define MTS_REPEAT_MIN 32          // lanes that must stay in a MEDIUM class for the block to run again in place (wg_block)
 
 enum : uint32_t { S_TOP = 0, S_MED = 1, S_SURF = 2, S_PHASE = 3, S_BSDF = 4, S_DIRB = 5, S_NEW = 6, S_DONE = 7, S_SCATTER = 8,
@@ -65,16 +56,10 @@ enum : uint32_t { S_TOP = 0, S_MED = 1, S_SURF = 2, S_PHASE = 3, S_BSDF = 4, S_D
 enum : uint32_t { M_MAIN = 0, M_NEE = 1, M_DIR = 2 };
 enum : uint32_t { FL_ALIVE = 1, FL_VALID_RAY = 2, FL_SPEC_CHAIN = 4, FL_NEEDS_INT = 8, FL_FROM_MEDIUM = 16 };
 
-// The tracking step of the ring driver as straight-line code (VolpathMachine::step_fast): the units whose media are all of one kind
-// (MT_MEDIA in the rgb / mono build: lean units a, b, c).  Every other unit keeps blk_med + top + classify in wg_block: the spectral
-// units' step evaluates two four-channel spectral grids and divides per channel, the homogeneous unit (h) has no lookup to make
-// unconditional, and the general units choose the medium's kind per step -- a select-committed form of those was not built.
-// -DMTS_STEP_GENERAL: the general step everywhere (A/B measurements).
-#if (MTS_TRAITS & MT_MEDIA) && MTS_SPEC_N == 3 && !defined(MTSAMD_BLOCKSTATS) && !defined(MTS_STEP_GENERAL)
-#define MTS_STEP_FAST 1
-#else
-#define MTS_STEP_FAST 0
-#endif
+// MTS_STEP_FAST (unit_config.h: lean units a, b, c): the tracking step of the ring driver as straight-line code
+// (VolpathMachine::step_fast).  It relies on media that are all heterogeneous, grey and on a pair grid:
+static_assert(!MTS_STEP_FAST || ((MTS_TRAITS & MT_MEDIA) && MTS_SPEC_N == 3), "step_fast is written for MT_MEDIA in the rgb / mono build");
+// Every other unit keeps blk_med + top + classify in wg_block.
 
 // Result of one free-flight sample (librender/medium.cpp:34-75); sigma_n is derived by the caller
 // (heterogeneous.cpp:46: combined - sigma_t, homogeneous.cpp:44: 0).
@@ -457,27 +442,12 @@ enum { B_INT = 0, B_MED /* free-flight step of the main path */, B_SCATTER, B_WS
        B_MEDW /* free-flight step of an NEE / direct-light walk */,
        B_CROSS /* the main path crosses a null-BSDF boundary that emits nothing: B_SURF's work for such a hit and no more (wg_block) */,
        B_DONE, B_COUNT };
-// Which ring machines sort their crossings into B_CROSS (wg_block: cross_class): `volpath`, rgb / mono, scalar streams, on the lean units
-// a and b -- the units of the benchmark scenes, where the class was measured -- and on the diagnostic build's general
-// unit, which stands in for them.  Everywhere else the class exists and stays empty: B_SURF is the general block and serves every hit.
-#if MTS_SPEC_N == 3 && (MTS_TRAITS == MT_UNIT_A || MTS_TRAITS == MT_UNIT_B || (defined(MTSAMD_BLOCKSTATS) && MTS_TRAITS == 0))
-#define MTS_CROSS_CLASS 1
-#else
-#define MTS_CROSS_CLASS 0
-#endif
-// MTS_HOT_DRCP: the hot state holds 1 / d (HotFront).  0: the unit's ring kernels form it from d, and their init loop loads the kernel
-// arguments inside its body (ring_driver.h: M::OPAQUE_INIT) -- two changes of the same kind (registers and LDS against instructions)
-// that were measured together, unit by unit, and are kept per unit by what they measured:
-//   a, b           the ninth ring needs the 12 KiB; with the loads ahead of the loop the flagship kernel spills 177 SGPRs (test_abi holds 160);
-//                  their volpathmis kernels lose 0.8 % (C3M) with the short front but the old loop, and nothing with both
-//   h              C2 +0.2 % with both, -1.3 % with neither (under this driver's ten control pairs)
-//   general rgb    with 1 / d loaded its ring kernel spills 19 VGPRs (test_abi holds 16), without 10
-//   spectral, c    keep 1 / d and the old loop: the spectral unit lost 0.7 % (C5S) with both changes and nothing with neither
-#if MTS_CROSS_CLASS || (MTS_SPEC_N == 3 && (MTS_TRAITS == 0 || MTS_TRAITS == MT_UNIT_H))
-#define MTS_HOT_DRCP 0
-#else
-#define MTS_HOT_DRCP 1
-#endif
+// MTS_CROSS_CLASS (unit_config.h): the `volpath` ring machines of the unit, scalar streams, sort their crossings into B_CROSS (wg_block:
+// cross_class).  Everywhere else the class exists and stays empty: B_SURF is the general block and serves every hit.
+// MTS_HOT_DRCP (unit_config.h): the hot state holds 1 / d (HotFront).  0: the unit's ring kernels form it from d, and their init loop
+// loads the kernel arguments inside its body (ring_driver.h: M::OPAQUE_INIT = MTS_OPAQUE_INIT) -- two changes of the same kind
+// (registers and LDS against instructions) that were measured together, unit by unit.  The ninth ring takes its LDS from the 12 KiB:
+static_assert(!MTS_CROSS_CLASS || (!MTS_HOT_DRCP && MTS_SPEC_N == 3), "B_CROSS: rgb / mono, and the ring's 2 KiB come out of H_DRCP's 12");
 
 // What a MEDIUM block reads of MedStep::info.  constexpr accessors: a lean unit's promises (MTS_TRAITS) are constants the front end folds,
 // as in the #if ladders this replaces (three plain bools: 1086 differing assembly lines in lean unit a).
@@ -1146,9 +1116,8 @@ DEV void volpath_pixel_flat(const DScene &sc, Pcg32 &rng, const DBlock &blk, uin
 // register, later fields cost an address computation each.
 // MTS_HOT_DRCP: whether 1 / d is part of the state.  It is vrcp(d) wherever a ray is made (make_ray, resume_main) and pm_rcp is a
 // function of its argument's bits alone (tests/micro/rcp_exhaustive.hip), so a block that loads d can form it again -- 12 vector
-// instructions in place of three LDS reads, three LDS writes less wherever d is stored, 12 KiB of LDS at 1024 paths.  The units with
-// the ninth ring (MTS_CROSS_CLASS: lean a and b, all their ring kernels) do, which is where that ring's 2 KiB come from, and so do unit h
-// and the general rgb / mono unit (MTS_HOT_DRCP above); then the front
+// instructions in place of three LDS reads, three LDS writes less wherever d is stored, 12 KiB of LDS at 1024 paths.  Which units do
+// is unit_config.h: those with the ninth ring (MTS_CROSS_CLASS), which is where that ring's 2 KiB come from, and two more; then the front
 // is thirteen dwords and the main path's throughput sits inside the 64 KB reach as well.  The other units keep the three dwords.
 enum { H_RNG = 0, H_O = 2, H_D = 5, H_DRCP = 8 /* MTS_HOT_DRCP: three dwords, else none */, H_MINT = 8 + 3 * MTS_HOT_DRCP, H_MAXT = H_MINT + 1,
        H_SIT = H_MAXT + 1, H_MEDIUM = H_SIT + 1, H_PACKED = H_MEDIUM + 1 /* st, mode, channel, flags, class, depth */,
@@ -1168,14 +1137,6 @@ enum : uint32_t { G_RNG = 1, G_O = 2, G_D = 4 /* d and 1/d (stored, or formed on
 #else
                   G_WL = 16384 /* read by every block that evaluates a spectrum, written by NEW */, G_ALL = 32767 };
 #endif
-// Measurement build (-DMTS_FUSE_INT=1, round 3): scenes without a BVH run the intersection of a freshly spawned ray at the end of
-// the block that spawned it (PHASE, SCATTER, walk SURFACE, SURFACE + BSDF, NEW) instead of queueing the path for an INTERSECT visit,
-// which saves 14 of 64 visits per sample on the metric scene (claim, state load / store, push).  Bit-identical; measured 546 -> 537
-// Msamples/s on C3 (512 x 512 x 256): the twelve triangle tests then run at the 45 - 50 lanes of the host blocks instead of the 54
-// of a class of their own, which costs what the saved visits gain.  Off by default.
-#ifndef MTS_FUSE_INT
-#define MTS_FUSE_INT 0
-#endif
 // What block class C (followed by top()) may read (`load`, a superset of `store`) and write (`store`).  end_nee / end_direct touch
 // almost everything; the classes with partial sets run them deferred (VolpathMachine::finish on the full state).
 template <int C> struct ClassFields { static constexpr uint32_t load = G_ALL, store = G_ALL; static constexpr bool defer = false; };
@@ -1192,7 +1153,7 @@ template <> struct ClassFields<B_INT> {          // every lane of the class want
     static constexpr bool defer = true; };
 template <> struct ClassFields<B_SCATTER> {
     static constexpr uint32_t load = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_MED | G_THR | G_TRANS | G_WA | G_WB | G_WL,
-                              store = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_TRANS | G_WA | G_WB | (MTS_FUSE_INT ? G_SIX : 0u);
+                              store = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_TRANS | G_WA | G_WB;
     static constexpr bool defer = true; };
 template <> struct ClassFields<B_CROSS> {        // no emitter sample, no walk, no cold record: the smallest set that samples the null BSDF and spawns the ray
     static constexpr uint32_t load = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_SIX | G_MED | G_THR | G_ETA | G_WL,
@@ -1200,7 +1161,7 @@ template <> struct ClassFields<B_CROSS> {        // no emitter sample, no walk, 
     static constexpr bool defer = false; };
 template <> struct ClassFields<B_PHASE> {
     static constexpr uint32_t load = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_MED | G_THR | G_ETA | G_WL,
-                              store = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_THR | (MTS_FUSE_INT ? G_SIX : 0u);
+                              store = G_RNG | G_O | G_D | G_MINT | G_MAXT | G_SIT | G_THR;
     static constexpr bool defer = true; };
 
 // The front of a ring machine's hot store, shared by HotStore below and MisHotStore (volpathmis_flat.h): the LDS accessors, the packed
@@ -1239,8 +1200,9 @@ struct HotFront {
         if (M & G_SIX) { put3(SIX, p.si.p); putf(SIX + 3, p.si.uv.x); putf(SIX + 4, p.si.uv.y); u(SIX + 5) = (uint32_t) p.si.shape; u(SIX + 6) = (uint32_t) p.si.prim; }
         if (M & G_MED) u(H_MEDIUM) = (uint32_t) p.medium;
     }
-    // ... and loads them; a block that does not load a group finds idle values in its place.  (As conditional loads over idle values,
-    // the form of load_add: lean unit a's volpath kernels 122 -> 121 and 128 -> 127 VGPRs, 23000 differing assembly lines.)
+    // ... and loads them; a block that does not load a group finds idle values in its place.  (Written as `if (M & G_X) field = load`
+    // over idle values set first, instead of the selects below: lean unit a's volpath kernels 122 -> 121 and 128 -> 127 VGPRs, 23000
+    // differing assembly lines.)
     template <uint32_t M, class P> DEV void load_front(P &p) const {
         p.rng.state = 0; p.rng.inc = (PCG32_DEFAULT_STREAM << 1u) | 1u;
         if (M & G_RNG) p.rng.state = (uint64_t) u(H_RNG) | ((uint64_t) u(H_RNG + 1) << 32);
@@ -1280,26 +1242,6 @@ struct HotStore : HotFront<WG, H_SIX> {
         p.wl = (M & G_WL) ? get_spec(H_WL) : spec_s(0.f);
 #endif
         Front::unpack(u(H_PACKED), p);
-    }
-    // the fields of M on top of a state that already holds the others (st / mode / flags / depth stay as the registers have them)
-    template <uint32_t M> DEV void load_add(PathState &p) const {
-        if (M & G_RNG) p.rng.state = (uint64_t) u(H_RNG) | ((uint64_t) u(H_RNG + 1) << 32);
-        if (M & G_O) p.ray.o = get3(H_O);
-        if (M & G_D) { p.ray.d = get3(H_D); p.ray.d_rcp = MTS_HOT_DRCP ? get3(H_DRCP) : vrcp(p.ray.d); }
-        if (M & G_MINT) p.ray.mint = f(H_MINT);
-        if (M & G_MAXT) p.ray.maxt = f(H_MAXT);
-        if (M & G_SIT) p.si.t = f(H_SIT);
-        if (M & G_SIX) { p.si.p = get3(H_SIX); p.si.uv.x = f(H_SIX + 3); p.si.uv.y = f(H_SIX + 4); p.si.shape = (int) u(H_SIX + 5); p.si.prim = (int) u(H_SIX + 6); }
-        if (M & G_MED) p.medium = (int) u(H_MEDIUM);
-        if (M & G_THR) p.thr = get_spec(H_THR);
-        if (M & G_RES) p.res = get_spec(H_RES);
-        if (M & G_ETA) p.eta = f(H_ETA);
-        if (M & G_TRANS) p.trans = get_spec(H_TRANS);
-        if (M & G_WA) p.wa = f(H_WA);
-        if (M & G_WB) p.wb = f(H_WB);
-#if MTS_SPEC_N != 3
-        if (M & G_WL) p.wl = get_spec(H_WL);
-#endif
     }
     DEV void store(const PathState &p, int cls) const { store_m<G_ALL>(p, cls); }
     DEV void load(PathState &p) const { load_m<G_ALL>(p); }
@@ -1382,11 +1324,9 @@ DEV int cross_class(int cls, const PathState &p, const HotStore<WG> &hs, const M
 // generator's 64-bit state; its increment, which for the scalar variants' streams is the default stream's constant, is recomputed here
 // from (pixel, sample index) on every load: a 64-bit TEA of four rounds, ~60 instructions, and one dword of the cold record -- in an
 // instantiation of its own, so that the kernels of the scalar streams do not change by an instruction.
+// __forceinline__: a real call costs 48 callee-saved VGPR spills + reloads per block visit (measured: 5 TB of scratch writes per render)
 template <bool COUNT, int WG, int C, bool WF = false, bool MOMENT = false>
-#ifndef WG_BLOCK_ATTR
-#define WG_BLOCK_ATTR __forceinline__   // a real call costs 48 callee-saved VGPR spills + reloads per block visit (measured: 5 TB of scratch writes per render)
-#endif
-static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, uint32_t *hot_lds, uint32_t wg_base_, uint32_t pid, Counters *cnt) {
+static __device__ __forceinline__ int wg_block(const MTS_CONST_AS void *kernarg_, uint32_t *hot_lds, uint32_t wg_base_, uint32_t pid, Counters *cnt) {
     uint32_t wg_base;
     const MTS_CONST_AS void *kernarg = block_uniforms(kernarg_, wg_base_, wg_base);
     const WgArgs a = cload_k<WgArgs>(kernarg);
@@ -1427,18 +1367,10 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
             vm.template run<CF::defer, true>(p, e, C);
             if (COUNT && C == B_MED) MTS_SEG(*cnt, 3);
             vm.template top<CF::defer>(p, e);
-            if (MTS_FUSE_INT && (C == B_PHASE || C == B_SCATTER || C == B_WSURF || C == B_SURF || C == B_NEW) && a.sc.bvh_node_count == 0) {
-                vm.blk_int(p, e);                            // acts on the lanes whose new ray can reach the scene (wants_int)
-                vm.template top<CF::defer>(p, e);            // start_direct() leaves a direct-light walk at its loop head
-            }
             if (COUNT && C == B_MED) MTS_SEG(*cnt, 4);
             cls = vm.classify(p);
         }
-        if ((MTS_CHAIN & 16) && C == B_SURF) {                 // the same for the main path (its second visit finds no hit: the sample ends)
-            if (cls != C || rounds >= 1) break;
-            continue;
-        }
-        if ((MTS_CHAIN & 1) && C == B_WSURF) {                 // a walk that left through a boundary face with nothing behind it (queue_intersection:
+        if (C == B_WSURF) {                                     // a walk that left through a boundary face with nothing behind it (queue_intersection:
             if (cls != C || rounds >= 1) break;                 // the ray misses the scene's box) comes straight back to this class to end
             continue;
         }
@@ -1448,32 +1380,8 @@ static __device__ WG_BLOCK_ATTR int wg_block(const MTS_CONST_AS void *kernarg_, 
         // remaining distance (`(1.f - MTS_SHADOW_EPSILON) - `) in top() and step_fast: reword those lines and its anchors together.
         if (__popcll(__ballot(true)) < (C == B_MEDW ? MTS_REPEAT_MIN_W : MTS_REPEAT_MIN)) break;
     }
-    bool chained = false;
-    if ((MTS_CHAIN & 4) && C == B_MEDW && cls == B_WSURF) {    // the walk left the medium: its surface step(s) run here, on the lanes that have one
-        hs.template load_add<G_ALL & ~CF::load>(p);
-#pragma nounroll
-        for (int r = 0; r < 2; ++r) {
-            vm.blk_wsurf(p, e);
-            vm.top(p, e);
-            cls = vm.classify(p);
-            if (cls != B_WSURF) break;
-        }
-        chained = true;
-    }
-    if ((MTS_CHAIN & 2) && (C == B_WSURF || chained) && cls == B_PHASE) {      // the walk has ended: the main path's phase sample (volpath.cpp:169-175)
-        vm.blk_phase(p, e);
-        vm.top(p, e);
-        cls = vm.classify(p);
-    }
     if constexpr (CROSS) cls = cross_class<HAVE_SHAPE>(cls, p, hs, kernarg);
-    if ((MTS_CHAIN & 8) && C == B_MED && cls == B_SCATTER) {   // a real collision: emitter sample and the start of its walk (volpath.cpp:162-167)
-        vm.blk_scatter(p, e);
-        vm.template top<true>(p, e);
-        cls = vm.classify(p);
-        hs.template store_m<CF::store | ClassFields<B_SCATTER>::store>(p, cls);
-    } else
-    if (chained) hs.template store_m<G_ALL>(p, cls);
-    else hs.template store_m<CF::store>(p, cls);
+    hs.template store_m<CF::store>(p, cls);
     if (COUNT && C == B_MED) MTS_SEG(*cnt, 5);
     if (CF::defer && (p.st == S_ENDNEE || p.st == S_ENDDIR0)) {     // rare tail on the full state
         PathState q;
@@ -1498,7 +1406,7 @@ struct VolpathRing {
     typedef VolpathMachine<COUNT_, MOMENT, MTS_GEOM_LDS != 0> Machine;
     static constexpr bool GEOM_TABLE = Machine::GEOM_TABLE;      // the driver fills the geometry table
     static constexpr bool CROSS = MTS_CROSS_CLASS && !WF && !MOMENT;      // the machine fills the ring of B_CROSS (wg_block); else the driver keeps eight rings
-    static constexpr bool OPAQUE_INIT = !MTS_HOT_DRCP;                    // see MTS_HOT_DRCP
+    static constexpr bool OPAQUE_INIT = MTS_OPAQUE_INIT;                  // unit_config.h: travels with MTS_HOT_DRCP
     template <int NT> DEV static void check_shape() { static_assert(NT <= WG_, "a thread per path at most"); }
     DEV static void init_idle(State &p) {
         p.medium = -1; p.thr = p.res = p.trans = spec_s(0.f); p.eta = 1.f; p.depth = 0; p.channel = 0; p.mode = M_MAIN; p.flags = 0; p.wa = p.wb = 0.f;

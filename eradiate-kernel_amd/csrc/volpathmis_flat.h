@@ -514,7 +514,7 @@ static __device__ __forceinline__ int mis_block(const MTS_CONST_AS void *kernarg
         vm.template run<CF::defer>(p, e, C);
         vm.template top<CF::defer>(p, e);
         cls = vm.classify(p);
-        if ((MTS_CHAIN & 1) && C == B_WSURF) {                 // a walk that left the scene's box ends in the same visit (volpath_flat.h, MTS_CHAIN)
+        if (C == B_WSURF) {                                     // a walk that left the scene's box ends in the same visit (volpath_flat.h, wg_block)
             if (cls != C || rounds >= 1) break;
             continue;
         }
@@ -542,7 +542,7 @@ struct VolpathMisRing {
     typedef MisHotStore<WG_, SPEC> Hot;
     typedef VolpathMisMachine<COUNT_, SPEC, MOMENT> Machine;
     static constexpr bool GEOM_TABLE = false;                  // no geometry table: the driver fills none for this machine
-    static constexpr bool OPAQUE_INIT = !MTS_HOT_DRCP;          // volpath_flat.h: MTS_HOT_DRCP
+    static constexpr bool OPAQUE_INIT = MTS_OPAQUE_INIT;        // unit_config.h: travels with MTS_HOT_DRCP
     static constexpr bool CROSS = false;                       // ... and no ring of B_CROSS: the machine never names the class
     template <int NT> DEV static void check_shape() { static_assert(NT <= 2 * WG_, "up to two threads per path (768 on 512: a third wave per SIMD)"); }
     DEV static void init_idle(State &p) {
