@@ -244,7 +244,7 @@ class Integrator:
                 A.check(A.lib().mts_render(scene._handle, C.byref(opts), out.ctypes.data_as(C.c_void_p), C.byref(stats)))
         finally:
             # stats first: a KeyboardInterrupt re-raised by the handler surfaces at the next bytecode
-            self.last_stats = {k: getattr(stats, k) for k, _ in A.Stats._fields_ if k != "reserved_"}
+            self.last_stats = {k: getattr(stats, k) for k, _ in A.Stats._fields_ if not k.startswith("reserved")}
             if scoped:
                 A.lib().mts_sigint_scope_exit()
         return not bool(stats.cancelled)

@@ -12,12 +12,14 @@ from . import _buildid
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTSAMD_LIB") or os.path.join(HERE, "libmtsamd.so")
 
-MTS_ABI_VERSION = 11
+MTS_ABI_VERSION = 12
 
 # enums (include/mtsamd.h)
 VOLUME_CONST, VOLUME_GRID, VOLUME_GRID_SPECTRAL = 0, 1, 2
 SPECTRUM_UNIFORM, SPECTRUM_REGULAR, SPECTRUM_IRREGULAR, SPECTRUM_DISCRETE = 0, 1, 2, 3
 FILTER_NEAREST, FILTER_TRILINEAR = 0, 1
+FILTER_BILINEAR = 1
+TEXTURE_BITMAP, TEXTURE_CHECKERBOARD = 0, 1
 WRAP_REPEAT, WRAP_MIRROR, WRAP_CLAMP = 0, 1, 2
 PHASE_ISOTROPIC, PHASE_HG, PHASE_RAYLEIGH, PHASE_BLEND, PHASE_TABULATED = 0, 1, 2, 3, 4
 MEDIUM_HOMOGENEOUS, MEDIUM_HETEROGENEOUS = 0, 1
@@ -28,7 +30,7 @@ SENSOR_PERSPECTIVE, SENSOR_DISTANT, SENSOR_MRADIANCEMETER, SENSOR_MDISTANT, SENS
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
 DISTANT_TARGET_NONE, DISTANT_TARGET_POINT, DISTANT_TARGET_SHAPE = 0, 1, 2
 INTEGRATOR_PATH, INTEGRATOR_VOLPATH, INTEGRATOR_VOLPATHMIS = 0, 1, 2
-OBJ_SPECTRUM, OBJ_VOLUME, OBJ_PHASE, OBJ_MEDIUM, OBJ_BSDF, OBJ_EMITTER = 0, 1, 2, 3, 4, 5
+OBJ_SPECTRUM, OBJ_VOLUME, OBJ_PHASE, OBJ_MEDIUM, OBJ_BSDF, OBJ_EMITTER, OBJ_TEXTURE = 0, 1, 2, 3, 4, 5, 6
 
 f32 = C.c_float
 i32 = C.c_int32
@@ -66,6 +68,11 @@ class Medium(C.Structure):
 class Bsdf(C.Structure):
     _fields_ = [("type", i32), ("reflectance", f32 * 3), ("rho_0", f32 * 3), ("k", f32 * 3),
                 ("g", f32 * 3), ("rho_c", f32 * 3), ("transmittance", f32 * 3), ("spectrum", i32 * 6)]
+
+
+class Texture(C.Structure):
+    _fields_ = [("type", i32), ("to_uv", f32 * 9), ("data", fp), ("width", i32), ("height", i32), ("channels", i32),
+                ("filter_type", i32), ("wrap_mode", i32), ("color0", f32 * 3), ("color1", f32 * 3)]
 
 
 class Shape(C.Structure):
@@ -107,14 +114,16 @@ class SceneDesc(C.Structure):
                 ("shapes", C.POINTER(Shape)), ("shape_count", i32),
                 ("emitters", C.POINTER(Emitter)), ("emitter_count", i32),
                 ("sensor", Sensor), ("integrator", Integrator),
-                ("spectra", C.POINTER(Spectrum)), ("spectrum_count", i32)]
+                ("spectra", C.POINTER(Spectrum)), ("spectrum_count", i32),
+                ("textures", C.POINTER(Texture)), ("texture_count", i32), ("bsdf_textures", C.POINTER(i32))]
 
 
 class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("n_iter", C.c_uint64), ("n_lookup", C.c_uint64),
                 ("n_nee_step", C.c_uint64), ("kernel_ms", C.c_double), ("wall_ms", C.c_double),
                 ("kernel_launches", i32), ("cancelled", i32), ("timed_out", i32), ("kernel_variant", i32),
-                ("calibration_launches", i32), ("reserved_", i32), ("calibration_ms", C.c_double)]
+                ("calibration_launches", i32), ("reserved_", i32), ("calibration_ms", C.c_double),
+                ("textured", i32), ("reserved2_", i32)]
 
 
 class RenderOpts(C.Structure):
@@ -129,7 +138,7 @@ class Dirty(C.Structure):
 ABI_STRUCTS = {"mts_spectrum": Spectrum, "mts_transform": Transform, "mts_volume": Volume, "mts_phase": Phase, "mts_medium": Medium,
                "mts_bsdf": Bsdf, "mts_shape": Shape, "mts_emitter": Emitter, "mts_sensor": Sensor,
                "mts_integrator": Integrator, "mts_scene_desc": SceneDesc, "mts_stats": Stats,
-               "mts_render_opts": RenderOpts, "mts_dirty": Dirty}
+               "mts_render_opts": RenderOpts, "mts_dirty": Dirty, "mts_texture": Texture}
 
 # every symbol include/mtsamd.h declares
 ABI_SYMBOLS = ["mts_abi_version", "mts_build_id", "mts_last_error", "mts_device_count", "mts_scene_create", "mts_scene_destroy",

@@ -86,7 +86,7 @@ const char *mts_last_error(void) { return g_error.c_str(); }
 int mts_abi_sizeof(const char *name) {
 #define SZ(T) if (!strcmp(name, #T)) return (int) sizeof(T);
     SZ(mts_spectrum) SZ(mts_transform) SZ(mts_volume) SZ(mts_phase) SZ(mts_medium) SZ(mts_bsdf) SZ(mts_shape) SZ(mts_emitter)
-    SZ(mts_sensor) SZ(mts_integrator) SZ(mts_scene_desc) SZ(mts_stats) SZ(mts_render_opts) SZ(mts_dirty)
+    SZ(mts_sensor) SZ(mts_integrator) SZ(mts_scene_desc) SZ(mts_stats) SZ(mts_render_opts) SZ(mts_dirty) SZ(mts_texture)
 #undef SZ
     return -1;
 }
@@ -319,7 +319,9 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
                                  " (crop_width x crop_height x " + std::to_string(hs.scene.film_channels) + " channels: " +
                                  (hs.integrator.moment ? "X, Y, Z, A, W + the moment integrator's m1.X, m1.Y, m1.Z, m2.X, m2.Y, m2.Z)" : "X, Y, Z, A, W + two per spectral bin)"));
     const KernelChoice kc = kernel_of(hs, block_size, sw, opts.collect_counters != 0);
-    const int variant = kc.variant;
+    // a textured scene: the TEX instantiation that renders the table's row (kernel_names.h); mts_stats.kernel_variant keeps naming the row
+    const bool textured = !hs.textures.empty();
+    const int variant = textured ? kv::textured_variant(kc.variant, hs.integrator.type, hs.scene.sensor.wavefront != 0, opts.collect_counters != 0) : kc.variant;
 #if defined(MTSAMD_HOST_ONLY)
     (void) stream; (void) t0; (void) stats; (void) variant;
     HOST_ONLY_STOP("mts_render");
@@ -357,7 +359,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
                                      ", workgroup " + std::to_string(c[9]) + ")");
     };
     try {
-        last_variant = kv::stat(variant, kc.unit);
+        last_variant = kv::stat(kc.variant, kc.unit);
         const RenderLauncher launcher = kc.unit == UNIT_GENERAL && hs.integrator.spectral ? launch_render_spectral : RENDER_LAUNCHERS[kc.unit];
 
         // one launch over `blocks` with `spp` samples per pixel, watched for cancel() / the timeout (which reach the kernel through the stop word).
@@ -377,7 +379,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
             const size_t ws_records = hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS ? 2 : 1;
             float *d_ws = (float *) rc.get(BUF_WORKSPACE, render_workspace_floats(paths, variant) * ws_records * sizeof(float));
             const RenderArgs args = { &hs.scene, d_blocks, (uint32_t) blocks.size(), block_size, spp, d_target, d_counters, opts.collect_counters != 0, variant,
-                                      d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream, hs.integrator.moment != 0 };
+                                      d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream, hs.integrator.moment != 0, textured };
             HIP_CHECK(launcher(args));
             HIP_CHECK(hipEventRecord(rc.ev1, stream));
             for (;;) {
@@ -436,7 +438,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
             memset(stats, 0, sizeof(*stats));
             stats->samples = plan.samples; stats->n_iter = h_counters[0]; stats->n_lookup = h_counters[1]; stats->n_nee_step = h_counters[2];
             stats->kernel_ms = kernel_ms; stats->kernel_launches = launches; stats->cancelled = cancelled ? 1 : 0; stats->timed_out = timed_out ? 1 : 0; stats->kernel_variant = last_variant;
-            stats->calibration_ms = calibration_ms; stats->calibration_launches = calibration_launches;
+            stats->calibration_ms = calibration_ms; stats->calibration_launches = calibration_launches; stats->textured = textured ? 1 : 0;
             stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
     } catch (...) { (void) hipStreamSynchronize(stream); throw; }     // nothing of this render may still be using the cached buffers

@@ -66,6 +66,11 @@ struct DMedium {
 
 struct DBsdf { int32_t type; float reflectance[3], rho_0[3], k[3], g[3], rho_c[3]; uint32_t flags; float transmittance[3]; };
 
+// Textures behind a BSDF's colour parameters (textures/bitmap.cpp, textures/checkerboard.cpp; rgb / mono variants).  to_uv: row-major
+// 3x3 (Transform4f::extract, transform.h:327-348).  data: device pointer to height * width texels, texel (x, y) at x + y * width;
+// a single-channel texel is one float, a three-channel texel four (r, g, b, 0): one 16-byte load.
+struct DTexture { int32_t type; float to_uv[9]; const float *data; int32_t width, height, channels, filter, wrap; float color0[3], color1[3]; };
+
 // Shapes (shapes/rectangle.cpp, shapes/cube.cpp + librender/mesh.cpp, shapes/sphere.cpp)
 struct DShape {
     int32_t type;
@@ -198,6 +203,13 @@ struct DScene {
     // shape: no emitter term, no emitter sample, no BSDF evaluation at such a hit.  The ring machines sort these hits into a class of
     // their own (volpath_flat.h: B_CROSS).  Set where the shape records are built (scene_host.cpp: add_shape); a shape beyond 63 has no bit.
     uint64_t cross_mask;
+    // Textured scenes only (rgb / mono; NULL / 0 otherwise), at the END of the record: everything above keeps its offset, so the plain
+    // kernels read what they always read.  bsdf_tex: per BSDF (the two default ones included) MTS_BSDF_SP_COUNT indices into
+    // textures, in the order reflectance, rho_0, k, g, rho_c, transmittance; -1 = the constant in DBsdf.  Only the TEX
+    // instantiations (integrator_dev.h: HitBsdf) read them.
+    const DTexture *textures;
+    const int32_t *bsdf_tex;
+    int32_t texture_count, pad_;
 };
 
 // bsdf.h:38-124

@@ -1138,6 +1138,94 @@ DEV int target_medium(const DShape &s, F3 n, F3 d) { return dot(d, n) > 0 ? s.ex
 DEV Spec null_transmission(const DScene &sc, const DShape &s) { return sc.bsdfs[s.bsdf].type == MTS_BSDF_NULL ? spec_s(1.f) : spec_s(0.f); }   // null.cpp:70-73, bsdf.cpp:11-14
 DEV float mis_weight(float pdf_a, float pdf_b) { pdf_a *= pdf_a; pdf_b *= pdf_b; return pdf_a > 0.0f ? pdf_a / (pdf_a + pdf_b) : 0.0f; }   // volpath.cpp:479-483
 
+// ---------------------------------------------------------------- textures (the TEX instantiations of the general rgb / mono unit)
+// The reference evaluates every BSDF parameter through Texture::eval(si) (diffuse.cpp, rpv.cpp, bilambertian.cpp).  The plain kernels
+// read constants from DBsdf; an instantiation with TEX = true makes a local copy of the record at each hit and overwrites the textured
+// fields (HitBsdf), so bsdf_eval / pdf / sample stay what they are and every use at one hit sees one value.
+// si.uv of the reference from what a Hit keeps of the primitive's own parameter
+DEV F2 surface_uv(const DScene &sc, const DShape &s, const Hit &h) {
+    F2 uv;
+    if (s.type == MTS_SHAPE_RECTANGLE) {                                                      // rectangle.cpp:205
+        uv.x = pm_fma(h.uv.x, .5f, .5f); uv.y = pm_fma(h.uv.y, .5f, .5f);
+    } else if (s.type == MTS_SHAPE_DISK) {                                                    // disk.cpp:206-211
+        float v = atan2f(h.uv.y, h.uv.x) * MTS_INV_TWO_PI;
+        if (v < 0.f) v += 1.f;
+        uv.x = pm_sqrt(pm_fma(h.uv.y, h.uv.y, h.uv.x * h.uv.x)); uv.y = v;
+    } else if (s.type == MTS_SHAPE_SPHERE) {                                                  // sphere.cpp:362-370; h.p is the re-projected point
+        const F3 local = mat_point_affine(s.to_object.m, h.p);
+        const float temp = asinf(.5f * norm(f3(local.x, local.y, local.z - pm_mulsign(1.f, local.z)))) * 2.f;      // unit_angle_z (core/vector.h)
+        const float theta = local.z >= 0.f ? temp : MTS_PI - temp;
+        float phi = atan2f(local.y, local.x);
+        if (phi < 0.f) phi += 2.f * MTS_PI;
+        uv.x = phi * MTS_INV_TWO_PI; uv.y = theta * MTS_INV_PI;
+    } else {                                                                                  // mesh.cpp:490-497 (cube: a mesh with texcoords)
+        const float b1 = h.uv.x, b2 = h.uv.y, b0 = 1.f - b1 - b2;
+        uv.x = b1; uv.y = b2;
+        if (s.has_texcoords) {
+            float T[6]; tri_attr_load<false, 6>(sc, s, h, false, 18, T);
+            uv.x = T[0] * b0 + T[2] * b1 + T[4] * b2; uv.y = T[1] * b0 + T[3] * b1 + T[5] * b2;
+        }
+    }
+    return uv;
+}
+DEV F3 texture_texel(const DTexture &t, int index) {
+    if (t.channels == 1) return f3s(as_global(t.data)[index]);
+    typedef float mts_float4 __attribute__((ext_vector_type(4)));
+    const mts_float4 v = *(const MTS_GLOBAL_AS mts_float4 *) (as_global(t.data) + 4 * (size_t) index);             // (r, g, b, 0)
+    return f3(v.x, v.y, v.z);
+}
+// Texture::eval: checkerboard.cpp:46-65; bitmap.cpp:403-474 (interpolate) with its wrap() (:386-401, the rule of wrap_coord)
+DEV F3 texture_eval(const DTexture &t, F2 st) {
+    // Transform3f::transform_affine (transform.h:91-98): the third column, then one fmadd per input coordinate; no divide
+    float u = pm_fma(t.to_uv[1], st.y, pm_fma(t.to_uv[0], st.x, t.to_uv[2])), v = pm_fma(t.to_uv[4], st.y, pm_fma(t.to_uv[3], st.x, t.to_uv[5]));
+    if (t.type == MTS_TEXTURE_CHECKERBOARD) {
+        const bool mx = u - pm_floor(u) > .5f, my = v - pm_floor(v) > .5f;
+        return mx == my ? f3(t.color0) : f3(t.color1);
+    }
+    const int W = t.width, H = t.height;
+    if (t.filter == MTS_FILTER_NEAREST) {                                                     // bitmap.cpp:459-472
+        u *= (float) W; v *= (float) H;
+        const int x = wrap_coord(t.wrap, (int) pm_floor(u), W), y = wrap_coord(t.wrap, (int) pm_floor(v), H);
+        return texture_texel(t, x + y * W);
+    }
+    u = pm_fma(u, (float) W, -.5f); v = pm_fma(v, (float) H, -.5f);                           // :417-456
+    const int ix = (int) pm_floor(u), iy = (int) pm_floor(v);
+    const float w1x = u - (float) ix, w1y = v - (float) iy, w0x = 1.f - w1x, w0y = 1.f - w1y;
+    const int x0 = wrap_coord(t.wrap, ix, W), x1 = wrap_coord(t.wrap, ix + 1, W), y0 = wrap_coord(t.wrap, iy, H), y1 = wrap_coord(t.wrap, iy + 1, H);
+    const F3 v00 = texture_texel(t, x0 + y0 * W), v10 = texture_texel(t, x1 + y0 * W), v01 = texture_texel(t, x0 + y1 * W), v11 = texture_texel(t, x1 + y1 * W);
+    const F3 v0 = fmadd(v00, w0x, v10 * w1x), v1 = fmadd(v01, w0x, v11 * w1x);
+    return fmadd(v0, w0y, v1 * w1y);
+}
+// The BSDF record of a hit.  Plain instantiations: the scene's record itself (an empty object: nothing of it is left in their code).
+// TEX: `local`, a copy whose textured colour parameters hold Texture::eval at the hit; a BSDF without a texture costs the test of its
+// six indices.
+// `b`, a copy of the record of BSDF bsdf_id: its textured colour parameters replaced by Texture::eval at uv_of()
+template <class UV>
+DEV void bsdf_apply_textures(const DScene &sc, int bsdf_id, DBsdf &b, UV uv_of) {
+    const MTS_GLOBAL_AS int32_t *tab = as_global(sc.bsdf_tex) + MTS_BSDF_SP_COUNT * bsdf_id;
+    const int t0 = tab[0], t1 = tab[1], t2 = tab[2], t3 = tab[3], t4 = tab[4], t5 = tab[5];
+    if ((t0 & t1 & t2 & t3 & t4 & t5) == -1) return;                     // -1 everywhere: constants only
+    const F2 uv = uv_of();
+    auto put = [&](int ti, float *field) {
+        if (ti < 0) return;
+        const F3 c = texture_eval(sc.textures[ti], uv);
+        field[0] = c.x; field[1] = c.y; field[2] = c.z;
+    };
+    put(t0, b.reflectance); put(t1, b.rho_0); put(t2, b.k); put(t3, b.g); put(t4, b.rho_c); put(t5, b.transmittance);
+}
+template <bool TEX> struct HitBsdf;
+template <> struct HitBsdf<false> {
+    DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &, const Hit &) { return sc.bsdfs[bsdf_id]; }
+};
+template <> struct HitBsdf<true> {
+    DBsdf local;
+    DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &shape, const Hit &si) {
+        local = sc.bsdfs[bsdf_id];
+        bsdf_apply_textures(sc, bsdf_id, local, [&]() { return surface_uv(sc, shape, si); });
+        return local;
+    }
+};
+
 // Geometric normal of a hit without the full shading frame (only needed for medium transitions)
 template <bool TAB = false>
 DEV F3 hit_geo_normal(const DScene &sc, const DShape &s, const Hit &h) {
@@ -1286,7 +1374,7 @@ DEV Spec volpath_evaluate_direct_light(const DScene &sc, F3 ref_p, Pcg32 &rng, i
 }
 
 // integrators/volpath.cpp:38-257
-template <bool COUNT>
+template <bool COUNT, bool TEX = false>
 DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool &valid_out, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     const uint32_t max_depth = (uint32_t) sc.integrator.max_depth, rr_depth = (uint32_t) sc.integrator.rr_depth;
     const bool hide_emitters = sc.integrator.hide_emitters != 0;
@@ -1373,7 +1461,8 @@ DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool
         active_surface = active_surface && hit_valid(si);
         if (active_surface) {
             const DShape &shape = sc.shapes[si.shape];
-            const DBsdf &bsdf = sc.bsdfs[shape.bsdf];
+            HitBsdf<TEX> hit_bsdf;
+            const DBsdf &bsdf = hit_bsdf.at(sc, shape.bsdf, shape, si);
             bool active_e = (bsdf.flags & F_Smooth) != 0 && (depth + 1 < max_depth);
             if (active_e) {
                 DirSample ds;
@@ -1579,7 +1668,7 @@ DEV Spec volpathmis_sample_emitter(const DScene &sc, F3 ref_p, bool is_medium_in
 }
 
 // volpathmis.cpp:86-328
-template <bool COUNT, bool SPEC>
+template <bool COUNT, bool SPEC, bool TEX = false>
 DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool &valid_out, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     const uint32_t max_depth = (uint32_t) sc.integrator.max_depth, rr_depth = (uint32_t) sc.integrator.rr_depth;
     const bool hide_emitters = sc.integrator.hide_emitters != 0;
@@ -1704,7 +1793,8 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
         active_surface = active_surface && hit_valid(si);
         if (active_surface) {
             const DShape &shape = sc.shapes[si.shape];
-            const DBsdf &bsdf = sc.bsdfs[shape.bsdf];
+            HitBsdf<TEX> hit_bsdf;
+            const DBsdf &bsdf = hit_bsdf.at(sc, shape.bsdf, shape, si);
             bool active_e = (bsdf.flags & F_Smooth) != 0 && (depth + 1 < max_depth);
             if (active_e) {
                 MisWeights<SPEC> nee_end, uni_end; DirSample ds;
@@ -1742,7 +1832,7 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
 
 // ---------------------------------------------------------------- path
 // integrators/path.cpp:100-211
-template <bool COUNT>
+template <bool COUNT, bool TEX = false>
 DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     const int max_depth = sc.integrator.max_depth, rr_depth = sc.integrator.rr_depth;
     float eta = 1.f, emission_weight = 1.f;
@@ -1764,7 +1854,8 @@ DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Co
         }
         if ((uint32_t) depth >= (uint32_t) max_depth || !active) break;
         const int bsdf_id = sc.shapes[si.shape].bsdf;
-        const DBsdf &bsdf = sc.bsdfs[bsdf_id];
+        HitBsdf<TEX> hit_bsdf;
+        const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[si.shape], si);
         bool active_e = (bsdf.flags & F_Smooth) != 0;
         if (active_e) {
             Spec emitter_val;
@@ -1807,17 +1898,18 @@ DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Co
 // INTEG: -1 = decided at run time from the scene record (the probe kernel), otherwise the integrator is fixed at compile time
 // (NI_*: one render-kernel instantiation each, so that `path` does not carry the registers of the volumetric integrators)
 enum { NI_ANY = -1, NI_PATH = 0, NI_VOLPATH = 1, NI_VOLPATHMIS = 2, NI_VOLPATHMIS_NOSPEC = 3 };
-template <bool COUNT, int INTEG = NI_ANY>
+// TEX: the BSDF parameters of a hit go through their textures (HitBsdf)
+template <bool COUNT, int INTEG = NI_ANY, bool TEX = false>
 DEV Spec integrator_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool &valid, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
-    if (INTEG == NI_PATH) return path_sample<COUNT>(sc, rng, ray, valid, cnt, cx);
-    if (INTEG == NI_VOLPATH) return volpath_sample<COUNT>(sc, rng, ray, medium, valid, cnt, cx);
-    if (INTEG == NI_VOLPATHMIS) return volpathmis_sample<COUNT, true>(sc, rng, ray, medium, valid, cnt, cx);
-    if (INTEG == NI_VOLPATHMIS_NOSPEC) return volpathmis_sample<COUNT, false>(sc, rng, ray, medium, valid, cnt, cx);
-    if (sc.integrator.type == MTS_INTEGRATOR_VOLPATH) return volpath_sample<COUNT>(sc, rng, ray, medium, valid, cnt, cx);
+    if (INTEG == NI_PATH) return path_sample<COUNT, TEX>(sc, rng, ray, valid, cnt, cx);
+    if (INTEG == NI_VOLPATH) return volpath_sample<COUNT, TEX>(sc, rng, ray, medium, valid, cnt, cx);
+    if (INTEG == NI_VOLPATHMIS) return volpathmis_sample<COUNT, true, TEX>(sc, rng, ray, medium, valid, cnt, cx);
+    if (INTEG == NI_VOLPATHMIS_NOSPEC) return volpathmis_sample<COUNT, false, TEX>(sc, rng, ray, medium, valid, cnt, cx);
+    if (sc.integrator.type == MTS_INTEGRATOR_VOLPATH) return volpath_sample<COUNT, TEX>(sc, rng, ray, medium, valid, cnt, cx);
     if (sc.integrator.type == MTS_INTEGRATOR_VOLPATHMIS)
-        return sc.integrator.use_spectral_mis ? volpathmis_sample<COUNT, true>(sc, rng, ray, medium, valid, cnt, cx)
-                                              : volpathmis_sample<COUNT, false>(sc, rng, ray, medium, valid, cnt, cx);
-    return path_sample<COUNT>(sc, rng, ray, valid, cnt, cx);
+        return sc.integrator.use_spectral_mis ? volpathmis_sample<COUNT, true, TEX>(sc, rng, ray, medium, valid, cnt, cx)
+                                              : volpathmis_sample<COUNT, false, TEX>(sc, rng, ray, medium, valid, cnt, cx);
+    return path_sample<COUNT, TEX>(sc, rng, ray, valid, cnt, cx);
 }
 
 // ---------------------------------------------------------------- film

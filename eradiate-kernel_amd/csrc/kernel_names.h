@@ -26,6 +26,14 @@ constexpr int moment_variant(int variant, int integrator, bool wavefront, bool c
          : variant == ring(512) && integrator == 2 ? variant
          : variant == FLAT && integrator == 0 ? variant : NESTED;
 }
+// A textured scene (mts_scene_desc.textures) renders on the general rgb / mono unit as well, in TEX instantiations: `volpath` on
+// 1024-path rings in its ring TEX kernel (scalar streams, no counters), `path` on the flat row in the flat TEX loop, every other row
+// -- `volpathmis`, wavefront streams, counters, 256-path rings -- in the nested TEX kernel (same functions, same streams: the same film).
+// mts_stats.kernel_variant keeps naming the table's row; mts_stats.textured says that this mapping applied.
+constexpr int textured_variant(int variant, int integrator, bool wavefront, bool counters) {
+    return variant == ring(1024) && integrator == 1 && !wavefront && !counters ? variant
+         : variant == FLAT && integrator == 0 ? FLAT : NESTED;
+}
 } // namespace kv
 enum KernelUnit : int { UNIT_GENERAL = 0, UNIT_A = 1, UNIT_B = 2, UNIT_S = 3, UNIT_P = 4, UNIT_PS = 5, UNIT_H = 6, UNIT_C = 7, UNIT_COUNT = 8 };
 

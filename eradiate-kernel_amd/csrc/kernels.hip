@@ -36,7 +36,8 @@ DEV void flush_counters(unsigned long long *counters, const Counters &cnt) {
 // in registers in sample order (bit-identical to the reference's block accumulation); the rare
 // sample that falls on the left/top pixel edge (u == 0) goes to the neighbour through an atomic.
 // MOMENT (rgb / mono general unit): the `moment` wrapper's tail, eleven accumulators (splat_moment_t, volpath_flat.h)
-template <bool COUNT, int INTEG, bool MOMENT = false>
+// TEX (rgb / mono general unit): BSDF parameters through their textures (integrator_dev.h: HitBsdf)
+template <bool COUNT, int INTEG, bool MOMENT = false, bool TEX = false>
 __device__ __forceinline__ void render_sample(const DScene &sc, Pcg32 &rng, const DBlock &blk, uint32_t lx, uint32_t ly,
                                               float *__restrict__ film, float acc[5], Counters &cnt) {
     const DSensor &se = sc.sensor;
@@ -64,7 +65,7 @@ __device__ __forceinline__ void render_sample(const DScene &sc, Pcg32 &rng, cons
     DRay ray = sensor_sample_ray(sc, adjusted, aperture_sample, ray_weight);
     bool valid;
 #if MTS_SPEC_N == 3
-    F3 L = integrator_sample<COUNT, INTEG>(sc, rng, ray, se.medium, valid, cnt);
+    F3 L = integrator_sample<COUNT, INTEG, TEX>(sc, rng, ray, se.medium, valid, cnt);
 #if !defined(MTS_LEAN)
     if constexpr (MOMENT) { splat_moment_t<true>(sc, blk, lx, ly, position_sample, L, ray_weight.x, valid, as_global(film), acc); return; }
 #endif
@@ -89,7 +90,7 @@ __device__ __forceinline__ void render_sample(const DScene &sc, Pcg32 &rng, cons
 // same order, and sums its samples in the same order: bit-identical to the nested formulation and to the CPU restatement.
 // Written over the variant's spectrum type: in the spectral build a sample also draws its four wavelengths (from the sensor's response
 // function when there is one), carries the bins' AOV values and reaches the film through spectrum_to_xyz, as render_sample above.
-template <bool COUNT, bool MOMENT = false>
+template <bool COUNT, bool MOMENT = false, bool TEX = false>
 __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, const DBlock &blk, uint32_t lx, uint32_t ly, uint32_t sample_count,
                                                 float *__restrict__ film, float acc[5], Counters &cnt, const uint32_t *stop_flag) {
     const DSensor &se = sc.sensor;
@@ -163,7 +164,8 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
         bool ended = (uint32_t) depth >= (uint32_t) max_depth || !active;
         if (!ended) {
             const int bsdf_id = sc.shapes[si.shape].bsdf;
-            const DBsdf &bsdf = sc.bsdfs[bsdf_id];
+            HitBsdf<TEX> hit_bsdf;
+            const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[si.shape], si);
             bool active_e = (bsdf.flags & F_Smooth) != 0;
             if (active_e) {
                 Spec emitter_val;
@@ -352,7 +354,59 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis_m
     ring_workgroup_async<VolpathMisRing<false, SPEC, WG, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
 }
 
-// SamplingIntegrator::sample for caller-supplied rays (librender/python/integrator_v.cpp:62-78)
+// ---- textured scenes (mts_scene_desc.textures): the per-lane kernels above with TEX = true -- every BSDF parameter of a hit goes
+// through its texture (integrator_dev.h: HitBsdf) -- under a name of their own: the plain instantiations stay what they are.
+// launch_render maps a row of the kernel table to one of these or to render_kernel_wga_tex below (kernel_names.h: kv::textured_variant).  FLAT: `path` as the flat
+// loop with regeneration; otherwise the nested formulation of whichever integrator the scene has, decided at run time.
+template <bool COUNT, bool FLAT>
+__global__ void __launch_bounds__(256, FLAT ? MTS_PATH_WAVES : MTS_NESTED_WAVES) render_kernel_tex(DScene sc, const DBlock *__restrict__ blocks, uint32_t n_blocks, uint32_t block_size,
+                                                     uint32_t sample_count, float *__restrict__ film_base, unsigned long long *__restrict__ counters,
+                                                     const uint32_t *__restrict__ stop_flag) {
+    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];             // as render_kernel
+    {
+        const int staged = min(sc.bvh_node_count, MTS_BVH_LDS_NODES);
+        for (int k = (int) threadIdx.x; k < staged * 8; k += (int) blockDim.x) bvh_top[k] = sc.bvh_nodes[k];
+        pm_tables_to_lds(threadIdx.x);
+        __syncthreads();
+        sc.bvh_lds = bvh_top; sc.bvh_lds_count = staged;
+    }
+    const uint32_t ppb = block_size * block_size;
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t b = gid / ppb, i = gid - b * ppb;
+    if (b >= n_blocks) return;
+    const DBlock blk = blocks[b];
+    float *__restrict__ film = film_base + (((size_t) blk.film_off_hi << 32) | blk.film_off_lo);
+    const uint32_t lx = compact_bits(i), ly = compact_bits(i >> 1);
+    if (lx >= (uint32_t) blk.sx || ly >= (uint32_t) blk.sy) return;
+    Pcg32 rng;
+    rng.seed(sc.sensor.seed + (uint64_t) blk.id * ppb + i, PCG32_DEFAULT_STREAM);
+    Counters cnt = {};
+    float acc[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };
+    if (FLAT) path_pixel_flat<COUNT, false, true>(sc, rng, blk, lx, ly, sample_count, film, acc, cnt, stop_flag);
+    else
+    for (uint32_t j = 0; j < sample_count; ++j) {
+        if ((j & 63u) == 63u && stop_requested(stop_flag)) break;
+        if (sc.sensor.wavefront) seed_wavefront_sample(rng, sc.sensor, blk, lx, ly, j);
+        render_sample<COUNT, NI_ANY, false, true>(sc, rng, blk, lx, ly, film, acc, cnt);
+    }
+    float *dst = film_entry(sc, blk, lx, ly, as_global(film));
+    for (int k = 0; k < 5; ++k) atomicAdd(dst + k, acc[k]);
+    if (COUNT) flush_counters(counters, cnt);
+}
+
+// `volpath` of a textured scene on the 1024-path rings (render_kernel_wga): the machine's SURFACE and BSDF blocks take the hit's BSDF
+// record through its textures; scalar streams, no counters.
+template <int WG, int NT, int WPE>
+__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_tex(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
+                                                               uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
+                                                               unsigned long long *counters, const uint32_t *stop_flag,
+                                                               const uint32_t *tiles, uint32_t n_tiles) {
+    Counters cnt = {};
+    ring_workgroup_async<VolpathRing<false, WG, false, false, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+}
+
+// SamplingIntegrator::sample for caller-supplied rays (librender/python/integrator_v.cpp:62-78); TEX: of a textured scene
+template <bool TEX>
 __global__ void __launch_bounds__(256) sample_kernel(DScene sc, int32_t n, uint64_t seed_offset, const float *__restrict__ rays /* 6 SoA rows */,
                                                      float *__restrict__ out_rgb, uint8_t *__restrict__ out_valid) {
     pm_tables_to_lds(threadIdx.x);
@@ -362,7 +416,7 @@ __global__ void __launch_bounds__(256) sample_kernel(DScene sc, int32_t n, uint6
     Pcg32 rng; rng.seed(sc.sensor.seed + seed_offset + (uint64_t) i, PCG32_DEFAULT_STREAM);
     DRay ray = make_ray(f3(rays[i], rays[n + i], rays[2 * n + i]), f3(rays[3 * n + i], rays[4 * n + i], rays[5 * n + i]), MTS_RAY_EPSILON, pm_inf());
     bool valid; Counters cnt;
-    F3 L = integrator_sample<false>(sc, rng, ray, sc.sensor.medium, valid, cnt);
+    F3 L = integrator_sample<false, NI_ANY, TEX>(sc, rng, ray, sc.sensor.medium, valid, cnt);
     out_rgb[3 * i] = L.x; out_rgb[3 * i + 1] = L.y; out_rgb[3 * i + 2] = L.z; out_valid[i] = valid ? 1 : 0;
 }
 
@@ -532,7 +586,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     const int integ = a.sc->integrator.type;
     const bool volpath = integ == MTS_INTEGRATOR_VOLPATH, mis = integ == MTS_INTEGRATOR_VOLPATHMIS, spec_mis = a.sc->integrator.use_spectral_mis != 0;
 #if defined(MTS_LEAN)
-    if (a.moment) return hipErrorInvalidConfiguration;         // a moment scene presents no traits: the general unit renders it
+    if (a.moment || a.textured) return hipErrorInvalidConfiguration;      // a moment or textured scene presents no traits: the general unit renders it
 #endif
 #if defined(MTS_LEAN_PATH)    // kernels_lean_p.hip / _ps.hip: `path` as the flat loop with regeneration, nothing else
     (void) volpath; (void) mis; (void) spec_mis;
@@ -559,6 +613,12 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
         if (a.variant == kv::FLAT) return launch_lane(a, threads, render_kernel_moment<false, true>);
         return launch_lane(a, threads, a.count ? render_kernel_moment<true, false> : render_kernel_moment<false, false>);
     }
+    if (a.textured) {                                          // a textured scene: a.variant is kv::textured_variant() of the table's row (capi.cpp)
+        if (a.variant != kv::textured_variant(a.variant, integ, a.sc->sensor.wavefront != 0, a.count)) return hipErrorInvalidConfiguration;
+        if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, render_kernel_wga_tex<1024, 1024, 4>);
+        if (a.variant == kv::FLAT) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel_tex, true));
+        return launch_lane(a, threads, MTS_BY_COUNT(render_kernel_tex, false));
+    }
     if (kv::is_ring(a.variant) && volpath) {                      // asynchronous regrouping
         if (a.sc->sensor.wavefront)                           // gpu_* streams: the instantiation that recomputes the generator's increment (wg_block, WF)
             return a.variant == kv::ring(1024) ? launch_wg(a, threads, 1024, 1024, MTS_BY_COUNT(render_kernel_wga, 1024, 1024, 4, true)) : hipErrorInvalidConfiguration;
@@ -575,7 +635,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     }
     if (a.variant != kv::NESTED && volpath) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_VOLPATH));     // the flat state machine per lane
 #else
-    if (a.moment) return hipErrorInvalidConfiguration;         // rgb / mono only (scene_host.cpp refuses the description)
+    if (a.moment || a.textured) return hipErrorInvalidConfiguration;      // rgb / mono only (scene_host.cpp refuses the description)
     // four-wide state: `volpath` 42 hot dwords per path; `volpathmis` 69 with spectral MIS (round 4: the path's matrices are parked during
     // walks), 53 without -- 256 paths per workgroup, two or three workgroups per CU
     if (kv::is_ring(a.variant) && volpath)
@@ -596,7 +656,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
 
 hipError_t launch_sample(const DScene &sc, int32_t n, uint64_t seed_offset, const float *d_rays, float *d_rgb, uint8_t *d_valid, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sample_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
+    hipLaunchKernelGGL(sc.texture_count > 0 ? sample_kernel<true> : sample_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 // /root/reference) with the same float arithmetic (explicit fma where the reference uses fmadd), so the
 // constants the kernels read are the ones a scalar_rgb build would hold.
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <algorithm>
 #include <map>
@@ -192,6 +193,7 @@ static DXf xf_perspective(float fov, float near_, float far_) {
 // Which promises of integrator_dev.h's scene traits (MT_*: what the lean translation units were compiled without) this scene keeps.
 // mts_render launches the leanest kernel whose promises are all kept; a scene that keeps none runs on the general kernels.
 static int scene_traits(const HostScene &hs, bool spectral) {
+    if (!hs.textures.empty()) return 0;                                 // a textured scene promises nothing: the general rgb / mono unit holds the TEX kernels
     int tr = 0;
     bool media = !hs.media.empty();
     for (size_t i = 0; i < hs.media.size(); ++i) {
@@ -440,6 +442,41 @@ static DBsdf build_bsdf(const mts_bsdf &b) {
 // which of the six colour parameters each BSDF plugin reads (spectral variant: the spectra it needs)
 static const bool BSDF_SP_USED[4][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */ };
 
+// A texture's record and (bitmap) its texels as the device holds them: validated as BitmapTexture's / Checkerboard's constructors
+// validate (bitmap.cpp:92-206, checkerboard.cpp:40-44).  `with_data` = false: the record alone (an update checks the frozen fields first).
+static DTexture build_texture(const mts_texture &t, int i, bool mono, bool with_data, std::vector<float> &texels) {
+    const std::string name = "texture " + std::to_string(i) + ": ";
+    DTexture dt; memset(&dt, 0, sizeof(dt));
+    if (t.type != MTS_TEXTURE_BITMAP && t.type != MTS_TEXTURE_CHECKERBOARD) throw std::runtime_error(name + "unknown texture type");
+    dt.type = t.type;
+    for (int k = 0; k < 9; ++k) { if (!std::isfinite(t.to_uv[k])) throw std::runtime_error(name + "\"to_uv\" is not finite"); dt.to_uv[k] = t.to_uv[k]; }
+    if (t.type == MTS_TEXTURE_CHECKERBOARD) {
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(t.color0[k]) || !std::isfinite(t.color1[k])) throw std::runtime_error(name + "checkerboard: \"color0\" / \"color1\" must be finite");
+            dt.color0[k] = t.color0[k]; dt.color1[k] = t.color1[k];
+        }
+        return dt;
+    }
+    if (t.channels != 1 && t.channels != 3) throw std::runtime_error(name + "Unsupported channel count: " + std::to_string(t.channels) + " (expected 1 or 3)");       // bitmap.cpp:196
+    if (mono && t.channels != 1) throw std::runtime_error(name + "a monochromatic scene takes single-channel bitmaps (the caller reduces rgb texels to their luminance)");
+    // bitmap.cpp:155-161 up-samples smaller images with a tent filter, which this backend has not got
+    if (t.width < 2 || t.height < 2) throw std::runtime_error(name + "Image must be at least 2x2 pixels in size (got " + std::to_string(t.width) + "x" + std::to_string(t.height) + "; this backend does not up-sample)");
+    if ((int64_t) t.width * t.height > ((int64_t) 1 << 28)) throw std::runtime_error(name + "bitmap too large (more than 2^28 texels)");
+    if (t.filter_type != MTS_FILTER_NEAREST && t.filter_type != MTS_FILTER_BILINEAR) throw std::runtime_error(name + "Invalid filter type, must be one of: \"nearest\", or \"bilinear\"!");
+    if (t.wrap_mode != MTS_WRAP_REPEAT && t.wrap_mode != MTS_WRAP_MIRROR && t.wrap_mode != MTS_WRAP_CLAMP) throw std::runtime_error(name + "Invalid wrap mode, must be one of: \"repeat\", \"mirror\", or \"clamp\"!");
+    if (!t.data) throw std::runtime_error(name + "bitmap without data");
+    dt.width = t.width; dt.height = t.height; dt.channels = t.channels; dt.filter = t.filter_type; dt.wrap = t.wrap_mode;
+    if (!with_data) return dt;
+    const size_t n = (size_t) t.width * t.height;
+    for (size_t k = 0; k < n * (size_t) t.channels; ++k) if (std::isnan(t.data[k])) throw std::runtime_error(name + "bitmap data contains NaN");
+    if (t.channels == 1) texels.assign(t.data, t.data + n);
+    else {
+        texels.assign(4 * n, 0.f);
+        for (size_t k = 0; k < n; ++k) { texels[4 * k] = t.data[3 * k]; texels[4 * k + 1] = t.data[3 * k + 1]; texels[4 * k + 2] = t.data[3 * k + 2]; }
+    }
+    return dt;
+}
+
 // an emitter's record; the scene's bounding sphere comes from set_scene (scene.cpp:95-97)
 static DEmitter build_emitter(const mts_emitter &e, const float center[3], float bsphere_radius) {
     DEmitter de; memset(&de, 0, sizeof(de));
@@ -517,6 +554,33 @@ static DefaultBsdfs build_bsdfs(const mts_scene_desc &d, bool spectral, HostScen
         for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(zero);
     }
     return ids;
+}
+// the six texture indices of BSDF i as the scene keeps them: range-checked, -1 for a parameter the plugin does not read
+static void bsdf_texture_indices(const mts_scene_desc &d, int i, int32_t out[MTS_BSDF_SP_COUNT]) {
+    for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) {
+        const int32_t t = d.bsdf_textures ? d.bsdf_textures[(size_t) i * MTS_BSDF_SP_COUNT + k] : -1;
+        if (t < -1 || t >= d.texture_count) throw std::runtime_error("index out of range: bsdf " + std::to_string(i) + " texture");
+        out[k] = BSDF_SP_USED[d.bsdfs[i].type][k] ? t : -1;
+    }
+}
+// Textures (after the BSDFs: the table has a row for each of them, the two default ones included).  A scene without a texture
+// record keeps all three arrays empty, whatever its index table says.
+static void build_textures(const mts_scene_desc &d, bool spectral, HostScene &hs) {
+    if (d.texture_count < 0 || (d.texture_count > 0 && !d.textures)) throw std::runtime_error("textures: a negative count, or records missing");
+    if (d.texture_count == 0) {
+        for (int i = 0; i < d.bsdf_count; ++i) { int32_t t[MTS_BSDF_SP_COUNT]; bsdf_texture_indices(d, i, t); }        // nothing but -1 is in range
+        return;
+    }
+    // rgb texels need the sRGB upsampling model (bitmap.cpp:169-178), whose data this backend has not got -- as for three-channel grids
+    if (spectral) throw std::runtime_error("textures are not supported in the spectral variant");
+    if (d.integrator.moment != 0) throw std::runtime_error("textures are not supported inside a moment integrator's scene");
+    for (int i = 0; i < d.texture_count; ++i) {
+        hs.texels.emplace_back();
+        hs.textures.push_back(build_texture(d.textures[i], i, d.integrator.monochrome != 0, true, hs.texels.back()));
+    }
+    hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1);
+    for (int i = 0; i < d.bsdf_count; ++i) bsdf_texture_indices(d, i, &hs.bsdf_tex[(size_t) i * MTS_BSDF_SP_COUNT]);
+    hs.scene.texture_count = d.texture_count;
 }
 // one shape of the description: its record, its primitives and their rows in the per-primitive tables; the scene's bounding box grows (scene.cpp:31-40)
 static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaults, HostScene &hs) {
@@ -719,6 +783,7 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     build_phases(*d, hs);
     build_media(*d, spectral, hs);
     const DefaultBsdfs defaults = build_bsdfs(*d, spectral, hs);
+    build_textures(*d, spectral, hs);
     bbox_reset(sc.bbox);
     for (int i = 0; i < d->shape_count; ++i) add_shape(*d, i, defaults, hs);
     build_bvh(hs);
@@ -877,6 +942,12 @@ void upload_host_scene(HostScene &hs, int device) {
     if (sc.bvh_node_count > 0) { sc.bvh_nodes = upload(hs, hs.bvh_nodes); sc.bvh_prims = upload(hs, hs.bvh_prims); }
     sc.sensor.rfilter.values = upload(hs, hs.rfilter_values);
     sc.sensor.multi = upload(hs, hs.multi_transforms);
+    sc.textures = nullptr; sc.bsdf_tex = nullptr;
+    if (!hs.textures.empty()) {
+        for (size_t i = 0; i < hs.textures.size(); ++i)
+            if (hs.textures[i].type == MTS_TEXTURE_BITMAP) hs.textures[i].data = upload(hs, hs.texels[i]);
+        sc.textures = upload(hs, hs.textures); sc.bsdf_tex = upload(hs, hs.bsdf_tex);
+    }
     sc.spectra = nullptr; sc.bsdf_sp = nullptr; sc.emitter_sp = nullptr; sc.volume_sp = nullptr; sc.cie = nullptr;
     if (hs.integrator.spectral) {
         for (size_t i = 0; i < hs.spectra.size(); ++i)
@@ -932,22 +1003,24 @@ void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *
     const bool spectral = hs.integrator.spectral != 0;
     // the description's own counts (build_host_scene appends two default BSDFs and, in the spectral variant, their two spectra)
     const int32_t n_volumes = (int32_t) hs.volumes.size(), n_phases = (int32_t) hs.phases.size(), n_media = (int32_t) hs.media.size(),
-                  n_bsdfs = (int32_t) hs.bsdfs.size() - 2, n_emitters = (int32_t) hs.emitters.size(), n_spectra = spectral ? (int32_t) hs.spectra.size() - 2 : 0;
+                  n_bsdfs = (int32_t) hs.bsdfs.size() - 2, n_emitters = (int32_t) hs.emitters.size(), n_spectra = spectral ? (int32_t) hs.spectra.size() - 2 : 0,
+                  n_textures = (int32_t) hs.textures.size();
     if ((d->integrator.spectral != 0) != spectral || (d->integrator.monochrome != 0) != (hs.scene.integrator.monochrome != 0))
         throw std::runtime_error("mts_scene_update: the description is of another variant than the scene");
     if (d->volume_count != n_volumes || d->phase_count != n_phases || d->medium_count != n_media || d->bsdf_count != n_bsdfs ||
-        d->emitter_count != n_emitters || (spectral && d->spectrum_count != n_spectra))
+        d->emitter_count != n_emitters || (spectral && d->spectrum_count != n_spectra) || d->texture_count != n_textures)
         throw std::runtime_error("mts_scene_update: the description's record counts differ from what the scene was created with");
 
     // ---- 1. validate and stage: nothing of the scene is written before every dirty record has passed
     std::map<int, StagedSpectrum> spectra; std::map<int, StagedPhase> phases; std::map<int, DBsdf> bsdfs; std::map<int, DEmitter> emitters;
+    std::map<int, std::pair<DTexture, std::vector<float>>> textures;
     std::map<int, const float *> volumes;                  // dirty volume -> mts_dirty::device_data
     std::set<int> media;
     for (int32_t k = 0; k < n; ++k) {
         const int i = dirty[k].index;
-        static const char *NAMES[] = { "spectrum", "volume", "phase", "medium", "bsdf", "emitter" };
-        const int32_t counts[] = { n_spectra, n_volumes, n_phases, n_media, n_bsdfs, n_emitters };
-        if (dirty[k].object < MTS_OBJ_SPECTRUM || dirty[k].object > MTS_OBJ_EMITTER) throw std::runtime_error("mts_scene_update: dirty[" + std::to_string(k) + "]: unknown object kind");
+        static const char *NAMES[] = { "spectrum", "volume", "phase", "medium", "bsdf", "emitter", "texture" };
+        const int32_t counts[] = { n_spectra, n_volumes, n_phases, n_media, n_bsdfs, n_emitters, n_textures };
+        if (dirty[k].object < MTS_OBJ_SPECTRUM || dirty[k].object > MTS_OBJ_TEXTURE) throw std::runtime_error("mts_scene_update: dirty[" + std::to_string(k) + "]: unknown object kind");
         const char *name = NAMES[dirty[k].object];
         if (i < 0 || i >= counts[dirty[k].object]) refuse(name, i, "index out of range");
         if (dirty[k].device_data && !(dirty[k].object == MTS_OBJ_VOLUME && hs.volumes[(size_t) i].type == MTS_VOLUME_GRID))
@@ -1005,7 +1078,27 @@ void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *
             if (spectral)
                 for (int s = 0; s < MTS_BSDF_SP_COUNT; ++s)
                     if (BSDF_SP_USED[b.type][s] && b.spectrum[s] != hs.bsdf_sp[(size_t) i * MTS_BSDF_SP_COUNT + s]) frozen(name, i, "spectrum");
+            if (n_textures > 0) {
+                int32_t t[MTS_BSDF_SP_COUNT]; bsdf_texture_indices(*d, i, t);
+                if (memcmp(t, &hs.bsdf_tex[(size_t) i * MTS_BSDF_SP_COUNT], sizeof(t)) != 0) frozen(name, i, "bsdf_textures");
+            }
             bsdfs[i] = build_bsdf(b);
+            break; }
+        case MTS_OBJ_TEXTURE: {                                // new texels / checkerboard colours (bitmap.cpp:562-564, checkerboard.cpp:92-96)
+            if (!d->textures) refuse(name, i, "the description holds no texture records");
+            const mts_texture &t = d->textures[i]; const DTexture &old = hs.textures[(size_t) i];
+            if (t.type != old.type) frozen(name, i, "type");
+            if (t.type == MTS_TEXTURE_BITMAP) {
+                if (t.width != old.width) frozen(name, i, "width");
+                if (t.height != old.height) frozen(name, i, "height");
+                if (t.channels != old.channels) frozen(name, i, "channels");
+                if (t.filter_type != old.filter) frozen(name, i, "filter_type");
+                if (t.wrap_mode != old.wrap) frozen(name, i, "wrap_mode");
+            }
+            if (memcmp(t.to_uv, old.to_uv, sizeof(old.to_uv)) != 0) frozen(name, i, "to_uv");
+            std::pair<DTexture, std::vector<float>> &st = textures[i]; st.second.clear();
+            try { st.first = build_texture(t, i, hs.scene.integrator.monochrome != 0, true, st.second); }
+            catch (const std::runtime_error &e) { refuse(name, i, e.what()); }
             break; }
         default: {
             const mts_emitter &e = d->emitters[i]; const DEmitter &old = hs.emitters[(size_t) i];
@@ -1100,6 +1193,11 @@ void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *
         if (pair && !hs.uploaded) build_pair_grid(hs.volumes[(size_t) dm.sigma_t], hs.grid_data[(size_t) dm.sigma_t], hs.grid_data[(size_t) dm.albedo], hs.pair_data[(size_t) i]);
     }
     for (const auto &kv : bsdfs) hs.bsdfs[(size_t) kv.first] = kv.second;
+    for (auto &kv : textures) {
+        const size_t i = (size_t) kv.first;
+        kv.second.first.data = hs.textures[i].data;
+        hs.textures[i] = kv.second.first; hs.texels[i].swap(kv.second.second);
+    }
     for (const auto &kv : emitters) hs.emitters[(size_t) kv.first] = kv.second;
     for (auto &kv : spectra) {
         const size_t i = (size_t) kv.first;
@@ -1119,6 +1217,8 @@ void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *
         if (!media.empty()) reupload(sc.media, hs.media, stream);
         if (!bsdfs.empty()) reupload(sc.bsdfs, hs.bsdfs, stream);
         if (!emitters.empty()) reupload(sc.emitters, hs.emitters, stream);
+        for (const auto &kv : textures) if (hs.textures[(size_t) kv.first].type == MTS_TEXTURE_BITMAP) reupload(hs.textures[(size_t) kv.first].data, hs.texels[(size_t) kv.first], stream);
+        if (!textures.empty()) reupload(sc.textures, hs.textures, stream);
         for (const auto &kv : phases) {
             const size_t i = (size_t) kv.first;
             if (hs.phases[i].type == MTS_PHASE_TABULATED) { reupload(hs.phases[i].pdf, hs.tab_pdf[i], stream); reupload(hs.phases[i].cdf, hs.tab_cdf[i], stream); }
@@ -1194,6 +1294,15 @@ void digest_host_scene(HostScene &hs, bool device, uint64_t out[8]) {
     }
     rec.add(volumes); rec.add(phases); rec.add(media);
     rec.add(from(sc.bsdfs, hs.bsdfs)); rec.add(from(sc.emitters, hs.emitters)); rec.add(from(sc.shapes, hs.shapes));
+    {                                                      // textures: empty arrays add nothing, so a scene without them hashes as it always did
+        std::vector<DTexture> textures = from(sc.textures, hs.textures);
+        for (size_t i = 0; i < textures.size(); ++i) {
+            if (textures[i].data != hs.textures[i].data) throw std::runtime_error("mts_debug_scene_digest: a texture record points elsewhere than the host's copy");
+            tab.add(from(textures[i].data, hs.texels[i]));
+            textures[i].data = nullptr;
+        }
+        rec.add(textures); rec.add(from(sc.bsdf_tex, hs.bsdf_tex));
+    }
     if (hs.integrator.spectral) {
         std::vector<DSpectrum> spectra = from(sc.spectra, hs.spectra);
         for (size_t i = 0; i < spectra.size(); ++i) {
@@ -1210,7 +1319,8 @@ void digest_host_scene(HostScene &hs, bool device, uint64_t out[8]) {
     h.positions = h.normals = h.texcoords = nullptr; h.faces = nullptr; h.tri = h.tri_attr = h.area_pmf = h.area_cdf = nullptr;
     h.bvh_nodes = nullptr; h.bvh_prims = nullptr; h.bvh_lds = nullptr; h.sensor.rfilter.values = nullptr; h.sensor.multi = nullptr;
     h.spectra = nullptr; h.bsdf_sp = nullptr; h.emitter_sp = nullptr; h.volume_sp = nullptr; h.cie = nullptr; h.bin_lo = h.bin_hi = nullptr;
-    head.add(&h, sizeof(h));
+    head.add(&h, offsetof(DScene, textures));              // the header up to the textured tail, which the record slot holds (texture_count: its array)
+
     const int32_t tail[2] = { hs.traits, hs.srf_lookup_by_wavelength ? 1 : 0 };
     head.add(tail, sizeof(tail));
     geom.add(from(sc.prims, hs.prims)); geom.add(from(sc.walk, hs.walk));

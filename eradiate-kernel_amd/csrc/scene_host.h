@@ -39,6 +39,9 @@ struct HostScene {
     std::vector<float> bin_lo, bin_hi;
     bool srf_lookup_by_wavelength = true;            // the response function's weights can be recovered from the sampled wavelengths (regrouping kernel)
     std::vector<int32_t> bsdf_sp, emitter_sp; std::vector<DVolumeSp> volume_sp;
+    // textured scenes (DScene::textures ...): the records, each bitmap's texels as the device holds them (three-channel texels padded
+    // to four floats), and the per-BSDF index table; all three empty in a scene without textures
+    std::vector<DTexture> textures; std::vector<std::vector<float>> texels; std::vector<int32_t> bsdf_tex;
     std::vector<void *> device_allocs;
     // mts_scene_update: two words per volume the grid pass reduces into (launch.h: GridUpdateJob::stats), allocated by the first update
     // that rewrites a grid.  After an update of an uploaded scene, grid_data / pair_data above keep their sizes, not the device's contents.
@@ -57,7 +60,8 @@ void free_host_scene(HostScene *hs);
 // scene_traits.  Validates everything before it writes (throws std::runtime_error with the scene untouched).  An uploaded scene is
 // rewritten in place on `stream` (grid statistics and pair grids by grid_update_kernel); a host-only scene through the host functions.
 void update_host_scene(HostScene &hs, const mts_scene_desc *desc, const mts_dirty *dirty, int32_t n, hipStream_t stream);
-// FNV-1a over the scene's contents, pointer fields zeroed: [0] record arrays, [1] grid data, [2] pair grids, [3] phase tables,
+// FNV-1a over the scene's contents, pointer fields zeroed: [0] record arrays (texture records and the BSDFs' texture indices behind
+// them), [1] grid data, [2] pair grids, [3] phase tables (bitmap texels behind them),
 // [4] spectra, [5] traits and the scalar header of DScene, [6] geometry (prims, walk, vertex and triangle tables, area tables, BVH),
 // [7] the sensor's and the bins' arrays (filter table, sub-sensor matrices, bin bounds).  One walk, two sources: `device` reads the
 // uploaded copy back (throws for a scene that is not in device memory), otherwise the walk reads HostScene's own vectors -- no

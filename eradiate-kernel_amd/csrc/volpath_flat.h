@@ -548,10 +548,12 @@ struct RingMachine {
 };
 
 // GEOM_: the machine runs under the ring driver of a unit with the geometry table in LDS (integrator_dev.h: MTS_GEOM_LDS)
-template <bool COUNT, bool MOMENT_ = false, bool GEOM_ = false>
-struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathState, true> {
-    typedef RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathState, true> Base;
+// TEX_: the BSDF record of a hit goes through its textures (integrator_dev.h: bsdf_apply_textures; general rgb / mono unit only)
+template <bool COUNT, bool MOMENT_ = false, bool GEOM_ = false, bool TEX_ = false>
+struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>, PathState, true> {
+    typedef RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>, PathState, true> Base;
     static constexpr bool MOMENT = MOMENT_;                    // RingMachine::blk_new: the `moment` wrapper's eleven-channel tail
+    static constexpr bool TEX = TEX_;
     static constexpr bool GEOM_TABLE = GEOM_;
     using Base::sc; using Base::cnt; using Base::ctx; using Base::queue_intersection; using Base::wants_int;
     DEV VolpathMachine(const DScene &sc_, Counters &cnt_) : Base(sc_, cnt_) {}
@@ -948,10 +950,12 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
         const bool hit = CROSSING ? true : hit_valid(p.si);
         Surf sf; sf.wi = -p.ray.d; sf.n = f3s(0.f); sf.sh.s = sf.sh.t = sf.sh.n = f3s(0.f);
         int emitter = CROSSING ? -1 : sc.environment, bsdf_id = 0;
+        F2 tex_uv; tex_uv.x = tex_uv.y = 0.f;                  // TEX: si.uv of the hit
         if (!CROSSING && hit) {
             WATERFALL_BEGIN(p.si.shape, su)
                 const DShape s = cload(sc.shapes + su);
                 emitter = s.emitter; bsdf_id = s.bsdf;
+                if constexpr (TEX) tex_uv = surface_uv(sc, s, p.si);
                 // the shading frame is only read by emitter evaluation and by the NEE of a smooth BSDF: a null boundary needs neither
                 if (s.emitter >= 0 || (s.bsdf_flags & F_Smooth) != 0) complete_surface<GEOM_TABLE>(sc, s, p.si, p.ray.d, sf);
             WATERFALL_END
@@ -973,7 +977,8 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
         F3 wo = to_local(sf.sh, ds.d);
         Spec bsdf_val; float bpdf;
         WATERFALL_BEGIN(bsdf_id, bu)
-            const DBsdf bsdf = cload(sc.bsdfs + bu);
+            DBsdf bsdf = cload(sc.bsdfs + bu);
+            if constexpr (TEX) bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; });
             bsdf_val = bsdf_eval(bsdf, sf.wi, wo MTS_CXI(bu));
             bpdf = bsdf_pdf(bsdf, sf.wi, wo MTS_CXI(bu));
         WATERFALL_END
@@ -991,9 +996,11 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
         if (p.st != S_BSDF) return;
         const uint32_t max_depth = (uint32_t) sc.integrator.max_depth;
         Surf sf; int bsdf_id = 0, is_tr = 0, ext = -1, inte = -1;
+        F2 tex_uv; tex_uv.x = tex_uv.y = 0.f;                  // TEX: si.uv of the hit
         WATERFALL_BEGIN(p.si.shape, su)
             const DShape s = cload(sc.shapes + su);
             complete_surface<GEOM_TABLE>(sc, s, p.si, p.ray.d, sf);
+            if constexpr (TEX) tex_uv = surface_uv(sc, s, p.si);
             bsdf_id = s.bsdf; is_tr = s.is_medium_transition; ext = s.exterior; inte = s.interior;
         WATERFALL_END
         const float s1 = p.rng.next_1d(); const F2 s2 = p.rng.next_2d();
@@ -1004,7 +1011,8 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_>, PathS
             bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs MTS_CXI(bsdf_id));
         } else {
             WATERFALL_BEGIN(bsdf_id, bu)
-                const DBsdf bsdf = cload(sc.bsdfs + bu);
+                DBsdf bsdf = cload(sc.bsdfs + bu);
+                if constexpr (TEX) bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; });
                 bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs MTS_CXI(bu));
             WATERFALL_END
         }
@@ -1325,12 +1333,12 @@ DEV int cross_class(int cls, const PathState &p, const HotStore<WG> &hs, const M
 // from (pixel, sample index) on every load: a 64-bit TEA of four rounds, ~60 instructions, and one dword of the cold record -- in an
 // instantiation of its own, so that the kernels of the scalar streams do not change by an instruction.
 // __forceinline__: a real call costs 48 callee-saved VGPR spills + reloads per block visit (measured: 5 TB of scratch writes per render)
-template <bool COUNT, int WG, int C, bool WF = false, bool MOMENT = false>
+template <bool COUNT, int WG, int C, bool WF = false, bool MOMENT = false, bool TEX = false>
 static __device__ __forceinline__ int wg_block(const MTS_CONST_AS void *kernarg_, uint32_t *hot_lds, uint32_t wg_base_, uint32_t pid, Counters *cnt) {
     uint32_t wg_base;
     const MTS_CONST_AS void *kernarg = block_uniforms(kernarg_, wg_base_, wg_base);
     const WgArgs a = cload_k<WgArgs>(kernarg);
-    VolpathMachine<COUNT, MOMENT, MTS_GEOM_LDS != 0> vm(a.sc, *cnt);
+    VolpathMachine<COUNT, MOMENT, MTS_GEOM_LDS != 0, TEX> vm(a.sc, *cnt);
     PathEnvT<ColdStoreHbm> e; wg_env<WG>(a, wg_base, pid, e);
     HotStore<WG> hs; hs.base = hot_lds + pid;
     typedef ClassFields<C> CF;
@@ -1397,13 +1405,13 @@ static __device__ __forceinline__ int wg_block(const MTS_CONST_AS void *kernarg_
 
 // Driver 2, the asynchronous regrouping of a workgroup's paths through LDS rings, is ring_driver.h; this is what it needs to know of
 // `volpath`.  WF: wavefront streams (wg_block).
-template <bool COUNT_, int WG_, bool WF, bool MOMENT = false>
+template <bool COUNT_, int WG_, bool WF, bool MOMENT = false, bool TEX = false>
 struct VolpathRing {
     static constexpr bool COUNT = COUNT_;
     static constexpr int WG = WG_, HOT_DWORDS = H_COUNT, PACKED = H_PACKED;
     typedef PathState State;
     typedef HotStore<WG_> Hot;
-    typedef VolpathMachine<COUNT_, MOMENT, MTS_GEOM_LDS != 0> Machine;
+    typedef VolpathMachine<COUNT_, MOMENT, MTS_GEOM_LDS != 0, TEX> Machine;
     static constexpr bool GEOM_TABLE = Machine::GEOM_TABLE;      // the driver fills the geometry table
     static constexpr bool CROSS = MTS_CROSS_CLASS && !WF && !MOMENT;      // the machine fills the ring of B_CROSS (wg_block); else the driver keeps eight rings
     static constexpr bool OPAQUE_INIT = MTS_OPAQUE_INIT;                  // unit_config.h: travels with MTS_HOT_DRCP
@@ -1415,7 +1423,7 @@ struct VolpathRing {
 #endif
     }
     // the block function itself, not a forwarding function: one more layer of inlining changed the code of the flagship kernel
-    template <int C> static constexpr auto block = &wg_block<COUNT_, WG_, C, WF, MOMENT>;
+    template <int C> static constexpr auto block = &wg_block<COUNT_, WG_, C, WF, MOMENT, TEX>;
 };
 
 } // inline namespace

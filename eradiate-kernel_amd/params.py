@@ -26,8 +26,8 @@ import numpy as np
 from . import _capi as A
 from . import scene_dict as SD
 
-_OBJ = {"spectrum": A.OBJ_SPECTRUM, "volume": A.OBJ_VOLUME, "phase": A.OBJ_PHASE, "medium": A.OBJ_MEDIUM, "bsdf": A.OBJ_BSDF, "emitter": A.OBJ_EMITTER}
-_ARRAYS = {"spectrum": "spectra", "volume": "volumes", "phase": "phases", "medium": "media", "bsdf": "bsdfs", "emitter": "emitters", "shape": "shapes"}
+_OBJ = {"spectrum": A.OBJ_SPECTRUM, "volume": A.OBJ_VOLUME, "phase": A.OBJ_PHASE, "medium": A.OBJ_MEDIUM, "bsdf": A.OBJ_BSDF, "emitter": A.OBJ_EMITTER, "texture": A.OBJ_TEXTURE}
+_ARRAYS = {"spectrum": "spectra", "volume": "volumes", "phase": "phases", "medium": "media", "bsdf": "bsdfs", "emitter": "emitters", "shape": "shapes", "texture": "textures"}
 _ABSENT = object()
 _GEOMETRY = "geometry updates are not supported yet (shapes are uploaded once: no BVH refit)"
 
@@ -46,7 +46,7 @@ class _Param:
     def readonly(self):
         if self.what == "geometry":
             return _GEOMETRY
-        if self.what in ("size", "lambda"):
+        if self.what in ("size", "lambda", "resolution", "to_uv"):
             return "the parameter is read-only"
         return None
 
@@ -143,6 +143,12 @@ class ParameterMap:
             return (rec.nx, rec.ny, rec.nz)
         if p.what == "tab":
             return self._keep.tabs[p.index]
+        if p.what == "texels":                                  # bitmap.cpp:562: the (height, width, channels) array
+            return self._keep.bitmaps[p.index]
+        if p.what == "resolution":
+            return (rec.width, rec.height)
+        if p.what == "to_uv":
+            return np.array(list(rec.to_uv), np.float32).reshape(3, 3)
         if p.what == "rgb":
             return np.array(list(getattr(rec, p.field.split("+")[0])), np.float32)
         if p.what == "range":
@@ -208,6 +214,12 @@ class ParameterMap:
                 raise RuntimeError("\"%s\": 'size' / 'channels' cannot change: the grid is (nz, ny, nx, channels) = %s, got %s"
                                    % (key, (rec.nz, rec.ny, rec.nx, rec.channels), data.shape))
             return (data, mono_max), None
+        if p.what == "texels":
+            data = SD._bitmap_data(value)
+            if data.shape != (rec.height, rec.width, rec.channels):
+                raise RuntimeError("\"%s\": 'resolution' / 'channels' differ from what the scene was created with (the topology of a scene is frozen): "
+                                   "the bitmap is (height, width, channels) = %s, got %s" % (key, (rec.height, rec.width, rec.channels), data.shape))
+            return data, None
         if p.what == "tab":
             arr = SD._tab_values(value) if isinstance(value, str) else np.ascontiguousarray(np.asarray(value, np.float32).reshape(-1))
             if arr.size != rec.tab_count:
@@ -282,6 +294,10 @@ class ParameterMap:
                     put(rec, "data", data.ctypes.data_as(A.fp))
                     if mono_max is not None and keep.grid_mono_max.get(p.index):
                         put(rec, "max_value", mono_max)
+            elif p.what == "texels":
+                remember(keep.bitmaps, p.index)
+                keep.bitmaps[p.index] = value
+                put(rec, "data", value.ctypes.data_as(A.fp))
             elif p.what == "tab":
                 remember(keep.tabs, p.index)
                 keep.tabs[p.index] = value

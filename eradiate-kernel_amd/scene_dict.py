@@ -18,6 +18,7 @@ from . import _capi as A
 from .transform import ScalarTransform4f, coordinate_system, normalize32
 from .volume_io import read_volume
 from .mesh_io import load_mesh
+from .texture_io import read_pfm
 from .fresolver import file_resolver
 
 
@@ -332,6 +333,10 @@ def _color_rgb(v, where, default=None, emitter=False):
         if t in ("srgb", "srgb_d65"):
             c = np.asarray(v.get("color"), dtype=np.float32).reshape(-1)
             return tuple(float(x) for x in c[:3])
+        if t in TEXTURE_PLUGINS:                                # textures are taken where a BSDF's colour parameter is (SceneBuilder.add_bsdf)
+            if emitter:
+                raise RuntimeError("Textures on emitters are not supported by this backend (\"%s\" in %s): give a constant" % (t, where))
+            raise RuntimeError("A \"%s\" texture is not accepted in %s: textures are supported for the colour parameters of BSDFs only" % (t, where))
         raise RuntimeError("Unsupported texture / spectrum plugin \"%s\" in %s (rgb constants only)" % (t, where))
     c = np.asarray(v, dtype=np.float32).reshape(-1)
     if c.size == 1:
@@ -394,6 +399,43 @@ def _grid_data(data):
     return data, mono_max
 
 
+TEXTURE_PLUGINS = ("bitmap", "checkerboard")
+
+
+def _to_uv(t):
+    """props.transform("to_uv").extract() (bitmap.cpp:93, checkerboard.cpp:43; transform.h:327-348) as nine floats, row-major.
+    enoki's coeff(i, j) is column i, row j: the loop copies the upper-left 2x2 and, as `coeff(2, i) = coeff(3, i)`, the first two
+    entries of the 4x4's last COLUMN -- the x and y of a translation survive, its z is dropped; the 3x3's last row keeps the identity's
+    zeros and takes the 4x4's corner.  transform_affine (transform.h:91-98) then never reads that row."""
+    if t is None:
+        t = ScalarTransform4f()
+    if not isinstance(t, ScalarTransform4f):
+        t = ScalarTransform4f(np.asarray(t, dtype=np.float32))
+    m = np.asarray(t.matrix, np.float32).reshape(4, 4)
+    return [float(x) for x in (m[0, 0], m[0, 1], m[0, 3], m[1, 0], m[1, 1], m[1, 3], 0.0, 0.0, m[3, 3])]
+
+
+def _bitmap_data(data):
+    """A bitmap's texels as the description holds them: float32, C order, (height, width, channels), channels 1 or 3.  Under the
+    *_mono variants rgb texels become their luminance (bitmap.cpp:278-279; luminance is linear, so it commutes with the filter)."""
+    data = np.asarray(data, dtype=np.float32)
+    if data.ndim == 2:
+        data = data[..., None]
+    if data.ndim != 3:
+        raise RuntimeError("bitmap: data must have shape (height, width) or (height, width, channels)")
+    if data.shape[2] not in (1, 3):
+        raise RuntimeError("Unsupported channel count: %d (expected 1 or 3)" % data.shape[2])                  # bitmap.cpp:196
+    if data.shape[0] < 2 or data.shape[1] < 2:
+        # bitmap.cpp:155-161 up-samples such an image with a tent filter, which this backend has not got
+        raise RuntimeError("bitmap: Image must be at least 2x2 pixels in size (got %dx%d; this backend does not up-sample)" % (data.shape[1], data.shape[0]))
+    if np.isnan(data).any():
+        raise RuntimeError("bitmap: data contains NaN")
+    if _MONO and data.shape[2] == 3:
+        f = np.float32
+        data = ((data[..., 0] * f(0.212671) + data[..., 1] * f(0.715160)) + data[..., 2] * f(0.072169))[..., None]      # spectrum.h:246-248
+    return np.ascontiguousarray(data, dtype=np.float32)
+
+
 def _tab_values(vals):
     """tabphase "values": a string of numbers (tabphase.cpp:33-40) -> float32 array."""
     if not isinstance(vals, str):
@@ -425,6 +467,9 @@ class SceneBuilder:
         self.children = []       # the scene's own children: (key, node)
         self.grids, self.grid_mono_max, self.tabs = {}, {}, {}
         self.spectrum_arrays = {}    # (spectrum, field) -> the array an update put there (one live array per record; load's own are in `keep`)
+        # textures behind BSDF colour parameters (rgb / mono): the records, six indices per BSDF (-1: the constant), each bitmap's
+        # live (height, width, channels) array
+        self.textures, self.bsdf_textures, self.bitmaps = [], [], {}
 
     def _colour_node(self, kind, index, field, where, spectrum=-1, emitter=False):
         return ("spectrum", spectrum) if _SPECTRAL is not None else ("colour", kind, index, field, where, emitter)
@@ -626,6 +671,68 @@ class SceneBuilder:
         self._register(d, "medium", len(self.media) - 1)
         return len(self.media) - 1
 
+    # ------------------------------------------------------------ textures
+    def _is_texture(self, v):
+        if not isinstance(v, dict):
+            return False
+        if v.get("type") == "ref":
+            return self.instances.get(v.get("id"), (None,))[0] == "texture"
+        return v.get("type") in TEXTURE_PLUGINS
+
+    def add_texture(self, d, where):
+        """src/textures/bitmap.cpp:92-206, src/textures/checkerboard.cpp:40-44 -> index of the mts_texture record"""
+        r = self._resolve_ref(d, "texture")
+        if r is not None:
+            return r
+        if _SPECTRAL is not None:
+            raise RuntimeError("Textures are not supported in the spectral variant (\"%s\" in %s): rgb texels need the sRGB upsampling "
+                               "model, whose data this backend has not got" % (d.get("type"), where))
+        p = Props(d, where)
+        rec = A.Texture()
+        index = len(self.textures)
+        rec.to_uv[:] = _to_uv(p.get("to_uv"))
+        if p.type == "checkerboard":
+            rec.type = A.TEXTURE_CHECKERBOARD
+            node = [("param", "transform", "to_uv", "to_uv")]                # checkerboard.cpp:92-96
+            for key, default in (("color0", 0.4), ("color1", 0.2)):
+                v = p.get(key, default)
+                if isinstance(v, dict) and v.get("type") in TEXTURE_PLUGINS + ("ref",):
+                    raise RuntimeError("checkerboard: \"%s\" must be a constant (a float or rgb) in this backend, not a nested texture: %s" % (key, where))
+                getattr(rec, key)[:] = _color(v, where + "." + key)
+                node.append(("object", key, ("colour", "texture", index, key, where + "." + key, False)))
+        else:
+            rec.type = A.TEXTURE_BITMAP
+            if p.has("filename") == p.has("data"):
+                raise RuntimeError("bitmap: give either \"filename\" (a .pfm file) or \"data\" (an array): %s" % where)
+            if p.has("filename"):
+                name = str(p.get("filename"))
+                if not name.lower().endswith(".pfm"):
+                    raise RuntimeError("bitmap: cannot read \"%s\": this backend reads PFM files (.pfm) only; pass other images as "
+                                       "\"data\" (a linear float32 array of shape (height, width) or (height, width, 3))" % name)
+                data = read_pfm(file_resolver().resolve(name))
+            else:
+                data = p.get("data")
+            ft = str(p.get("filter_type", "bilinear"))
+            if ft not in ("nearest", "bilinear"):
+                raise RuntimeError("Invalid filter type \"%s\", must be one of: \"nearest\", or \"bilinear\"!" % ft)      # bitmap.cpp:100-107
+            wm = str(p.get("wrap_mode", "repeat"))
+            if wm not in ("repeat", "mirror", "clamp"):
+                raise RuntimeError("Invalid wrap mode \"%s\", must be one of: \"repeat\", \"mirror\", or \"clamp\"!" % wm)   # bitmap.cpp:109-118
+            p.get("raw", False)                                          # linear float data either way: nothing to undo
+            data = _bitmap_data(data)
+            self.keep.append(data)
+            self.bitmaps[index] = data
+            rec.data = data.ctypes.data_as(A.fp)
+            rec.height, rec.width, rec.channels = data.shape
+            rec.filter_type = A.FILTER_NEAREST if ft == "nearest" else A.FILTER_BILINEAR
+            rec.wrap_mode = {"repeat": A.WRAP_REPEAT, "mirror": A.WRAP_MIRROR, "clamp": A.WRAP_CLAMP}[wm]
+            node = [("param", "data", "texels", "data"), ("param", "resolution", "resolution", None), ("param", "transform", "to_uv", "to_uv")]      # bitmap.cpp:561-565
+        p.finish()
+        self.nodes[("texture", index)] = node
+        self.textures.append(rec)
+        self._register(d, "texture", index)
+        return index
+
     # ------------------------------------------------------------ BSDFs
     def add_bsdf(self, d, where):
         r = self._resolve_ref(d, "bsdf")
@@ -636,7 +743,13 @@ class SceneBuilder:
         rec.spectrum[:] = [-1] * 6
         spectral = _SPECTRAL is not None
         node = []
+        textures = [-1] * 6                                              # per colour parameter: its texture record, -1 = the constant
         def colour(field, slot, key, default):                           # rgb triple, or (spectral variant) the index of the spectrum
+            if self._is_texture(p.d.get(key)):                           # a bitmap / checkerboard; the record's own constant (what a reader that
+                textures[slot] = self.add_texture(p.get(key), where + "." + key)      # knows no textures sees) is the parameter's default
+                getattr(rec, field)[:] = _color(default, where) if default is not None else tuple(rec.rho_0)
+                node.append(("object", key, ("texture", textures[slot])))
+                return
             if spectral:
                 rec.spectrum[slot] = _spectrum(p.get(key), where + "." + key, default=default)
             else:
@@ -662,11 +775,14 @@ class SceneBuilder:
                 rec.spectrum[4] = rec.spectrum[1]                        # rpv.cpp:75-79: rho_c defaults to rho_0
             else:
                 rec.rho_c[:] = tuple(rec.rho_0)                          # (one texture under two names: traverse() lists it once, an update of rho_0 reaches both)
-                node[0] = ("object", "rho_0", ("colour", "bsdf", len(self.bsdfs), "rho_0+rho_c", where, False))
+                textures[4] = textures[1]
+                if textures[1] < 0:
+                    node[0] = ("object", "rho_0", ("colour", "bsdf", len(self.bsdfs), "rho_0+rho_c", where, False))
         else:
             raise RuntimeError("Unknown / unsupported BSDF plugin \"%s\"" % p.type)
         p.finish()
         self.nodes[("bsdf", len(self.bsdfs))] = node
+        self.bsdf_textures.append(textures)
         self.bsdfs.append(rec)
         self._register(d, "bsdf", len(self.bsdfs) - 1)
         return len(self.bsdfs) - 1
@@ -1189,12 +1305,16 @@ class SceneBuilder:
                 self.children.append((name, ("phase", self.add_phase(v, k))))
             elif t in ("gridvolume", "constvolume"):
                 self.children.append((name, ("volume", self.add_volume(v, k))))
+            elif t in TEXTURE_PLUGINS:                                   # declared at the scene level, referenced by id from BSDFs
+                self.children.append((name, ("texture", self.add_texture(v, k))))
             else:
                 raise RuntimeError("Unknown / unsupported plugin \"%s\" (key \"%s\")" % (t, k))
         if self.sensor is None:
             raise RuntimeError("No sensors found! (this backend does not instantiate a default camera)")
         if self.integrator is None:
             self.set_integrator({"type": "path"}, "integrator")          # scene.cpp:88-92
+        if self.textures and self.integrator.moment:
+            raise RuntimeError("Textures inside a moment integrator's scene are not supported by this backend")
         return self.finish()
 
     def finish(self):
@@ -1214,6 +1334,9 @@ class SceneBuilder:
         desc.sensor = self.sensor
         desc.integrator = self.integrator
         desc.spectra, desc.spectrum_count = arr(A.Spectrum, self.spectra), len(self.spectra)
+        if self.textures:                                                # a scene without textures keeps the zeroed tail
+            desc.textures, desc.texture_count = arr(A.Texture, self.textures), len(self.textures)
+            desc.bsdf_textures = arr(A.i32, [t for row in self.bsdf_textures for t in row])
         self.keep.append(desc)
         return desc
 

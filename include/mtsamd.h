@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MTS_ABI_VERSION 11
+#define MTS_ABI_VERSION 12
 
 /* Transform4f: row-major 4x4 matrix and its inverse transpose (transform.h:36-50). */
 typedef struct mts_transform {
@@ -118,6 +118,28 @@ typedef struct mts_bsdf {
     int32_t spectrum[6];      /* spectral variant: indices into mts_scene_desc.spectra of reflectance, rho_0, k, g, rho_c,
                                  transmittance, in this order (-1 in rgb / mono scenes)                                   */
 } mts_bsdf;
+
+/* ---- Textures behind a BSDF's colour parameters (rgb / mono variants): src/textures/bitmap.cpp, src/textures/checkerboard.cpp.
+ *      A BSDF parameter is either the constant in mts_bsdf or one of these records (mts_scene_desc.bsdf_textures); the reference
+ *      evaluates every BSDF parameter through Texture::eval(si) (diffuse.cpp, rpv.cpp, bilambertian.cpp), si.uv being the shape's
+ *      parameterisation: rectangle.cpp:205, disk.cpp:206-211, sphere.cpp:362-370, mesh.cpp:490-497.
+ *      to_uv: row-major 3x3 -- props.transform("to_uv").extract() (bitmap.cpp:93, checkerboard.cpp:43; transform.h:327-348): the upper
+ *      left 2x2 of the 4x4, its translation's x and y in the third column, its last row's x, y and w in the third row.  It is applied
+ *      as transform_affine (transform.h:91-98): uv' = column 2 + column 0 * u + column 1 * v, no divide; the third row is not read. ---- */
+enum { MTS_TEXTURE_BITMAP = 0, MTS_TEXTURE_CHECKERBOARD = 1 };
+enum { MTS_FILTER_BILINEAR = 1 };          /* bitmap "filter_type": MTS_FILTER_NEAREST or this (bitmap.cpp:100-107) */
+typedef struct mts_texture {
+    int32_t type;
+    float to_uv[9];
+    /* bitmap: linear float texels, row y first, texel (x, y) at index x + y * width, y growing with v (bitmap.cpp:430,466) */
+    const float *data;        /* height * width * channels floats                                 */
+    int32_t width, height;    /* both >= 2 (the reference up-samples smaller images with a tent filter, bitmap.cpp:155-161; refused here) */
+    int32_t channels;         /* 1 or 3 (bitmap.cpp:196); 1 in *_mono scenes: the caller reduces rgb texels to their luminance */
+    int32_t filter_type;      /* "filter_type", default bilinear (bitmap.cpp:100-107, 410-473)    */
+    int32_t wrap_mode;        /* "wrap_mode" MTS_WRAP_*, default repeat (bitmap.cpp:109-118, 386-401) */
+    /* checkerboard "color0" / "color1", constants; defaults 0.4 / 0.2; color0 where (frac(u) > .5) == (frac(v) > .5) (checkerboard.cpp:40-65) */
+    float color0[3], color1[3];
+} mts_texture;
 
 /* ---- Shapes (src/shapes/{rectangle,cube,sphere,disk}.cpp, src/librender/mesh.cpp) ---- */
 enum { MTS_SHAPE_RECTANGLE = 0, MTS_SHAPE_CUBE = 1, MTS_SHAPE_SPHERE = 2, MTS_SHAPE_MESH = 3, MTS_SHAPE_DISK = 4 /* src/shapes/disk.cpp */ };
@@ -254,6 +276,11 @@ typedef struct mts_scene_desc {
     mts_sensor sensor;
     mts_integrator integrator;
     const mts_spectrum *spectra; int32_t spectrum_count;  /* spectral variant only */
+    /* Textures (rgb / mono variants; not with mts_integrator.moment).  bsdf_textures: NULL = no texture anywhere, else six indices
+       into `textures` per BSDF, in the order of mts_bsdf.spectrum[] (reflectance, rho_0, k, g, rho_c, transmittance); -1 = the
+       constant in mts_bsdf.  A zeroed tail means "no textures". */
+    const mts_texture *textures; int32_t texture_count;
+    const int32_t *bsdf_textures;                         /* 6 * bsdf_count, or NULL */
 } mts_scene_desc;
 
 typedef struct mts_scene mts_scene;   /* opaque */
@@ -279,6 +306,9 @@ typedef struct mts_stats {
                                      (expensive blocks first; its samples are discarded)          */
     int32_t reserved_;
     double calibration_ms;    /* device time of that launch                                      */
+    int32_t textured;         /* 1 when a textured instantiation rendered (a scene with mts_scene_desc.textures): kernel_variant still names
+                                 the row of the kernel table the scene gets; kernel_names.h: kv::textured_variant maps it to the kernel that ran */
+    int32_t reserved2_;
 } mts_stats;
 
 typedef struct mts_render_opts {
@@ -310,7 +340,7 @@ int  mts_scene_destroy(mts_scene *scene);
  * plugin's traverse() lists its parameters, parameters_changed() re-runs what its constructor derived from them).  `desc` is the
  * description the scene was created from with new VALUES in the records `dirty` lists; records that are not listed are not looked at.
  * The topology is frozen: in a dirty record the `type`, every index into another array, a grid's dimensions / channels / filter /
- * wrap mode / transform and every table or spectrum `count` must be what the scene was created with -- anything else is an error
+ * wrap mode / transform, a BSDF's texture indices and every table or spectrum `count` must be what the scene was created with -- anything else is an error
  * that names the record and the field.  Shapes, the sensor, the film and the integrator have no MTS_OBJ_* (no geometry updates).
  *
  * For each dirty record the library re-runs the constructor-time work of mts_scene_create for it and for every record derived from
@@ -320,7 +350,8 @@ int  mts_scene_destroy(mts_scene *scene);
  * the call returns once they are in place, so the caller's arrays may go away.  Everything is validated before anything is written:
  * a refused update (also: n < 0, a NULL desc, an ABI mismatch, an index out of range, a device_data on anything but a grid, a render
  * of this scene in flight) leaves the scene as it was. */
-enum { MTS_OBJ_SPECTRUM = 0, MTS_OBJ_VOLUME = 1, MTS_OBJ_PHASE = 2, MTS_OBJ_MEDIUM = 3, MTS_OBJ_BSDF = 4, MTS_OBJ_EMITTER = 5 };
+enum { MTS_OBJ_SPECTRUM = 0, MTS_OBJ_VOLUME = 1, MTS_OBJ_PHASE = 2, MTS_OBJ_MEDIUM = 3, MTS_OBJ_BSDF = 4, MTS_OBJ_EMITTER = 5,
+       MTS_OBJ_TEXTURE = 6 /* new texels / checkerboard colours; type, size, channels, filter, wrap mode and to_uv are frozen (bitmap.cpp:562-564, checkerboard.cpp:92-96) */ };
 typedef struct mts_dirty {
     int32_t object, index;       /* which record of the description changed: MTS_OBJ_*, index into its array               */
     const float *device_data;    /* MTS_OBJ_VOLUME, grids only: non-NULL = the new nz*ny*nx*channels floats are read from this
