@@ -64,6 +64,9 @@ struct DMedium {
     int32_t pair_nx, pair_ny, pair_nz, pair_affine;      // pair_affine: bit 0 = affine, bit 1 = both grids have equal columns (DVolume::columns_equal)
 };
 
+// A blendbsdf (MTS_BSDF_BLEND; TEX instantiations only) keeps in the same record: reflectance[0] = its constant weight, the bits of
+// rho_0[0] / rho_0[1] = the indices of bsdf_0 / bsdf_1, flags = the union of its children's (blendbsdf.cpp:80); slot 0 of its bsdf_tex
+// row = the weight's texture.
 struct DBsdf { int32_t type; float reflectance[3], rho_0[3], k[3], g[3], rho_c[3]; uint32_t flags; float transmittance[3]; };
 
 // Textures behind a BSDF's colour parameters (textures/bitmap.cpp, textures/checkerboard.cpp; rgb / mono variants).  to_uv: row-major
@@ -203,7 +206,7 @@ struct DScene {
     // shape: no emitter term, no emitter sample, no BSDF evaluation at such a hit.  The ring machines sort these hits into a class of
     // their own (volpath_flat.h: B_CROSS).  Set where the shape records are built (scene_host.cpp: add_shape); a shape beyond 63 has no bit.
     uint64_t cross_mask;
-    // Textured scenes only (rgb / mono; NULL / 0 otherwise), at the END of the record: everything above keeps its offset, so the plain
+    // Scenes with textures or a blendbsdf only (rgb / mono; NULL / 0 otherwise; a blend scene without textures has bsdf_tex alone), at the END of the record: everything above keeps its offset, so the plain
     // kernels read what they always read.  bsdf_tex: per BSDF (the two default ones included) MTS_BSDF_SP_COUNT indices into
     // textures, in the order reflectance, rho_0, k, g, rho_c, transmittance; -1 = the constant in DBsdf.  Only the TEX
     // instantiations (integrator_dev.h: HitBsdf) read them.

@@ -1213,16 +1213,94 @@ DEV void bsdf_apply_textures(const DScene &sc, int bsdf_id, DBsdf &b, UV uv_of) 
     };
     put(t0, b.reflectance); put(t1, b.rho_0); put(t2, b.k); put(t3, b.g); put(t4, b.rho_c); put(t5, b.transmittance);
 }
+// ---- blendbsdf (bsdfs/blendbsdf.cpp:83-164; DBsdf in dscene.h says where a blend record keeps what).  TEX instantiations only: a
+// scene that holds a blend renders there, and a hit pays one test of its record's type.  Every surface site goes through the three
+// functions below -- the per-lane ones through HitBsdf, the ring machine's SURFACE / BSDF blocks directly (U: wave-uniform loads).
+// The ctx.component branches (:91-101, :131-139, :149-155) are never reached by path / volpath / volpathmis and are not restated.
+DEV int blend_child(const DBsdf &blend, int c) { return __float_as_int(blend.rho_0[c]); }
+// eval_weight (:162-164): clamp(weight->eval_1(si), 0, 1) -- the clamp after the interpolation.  eval_1: a uniform value as it is
+// (uniform.cpp:71-75); a one-channel bitmap's interpolated texel, the luminance (core/spectrum.h:246-248) of a three-channel one's
+// interpolated colour (bitmap.cpp:285-302); a checkerboard's eval_1 of the cell's colour (checkerboard.cpp:67-86), a uniform value
+// that the record holds three times.
+DEV float blend_weight(const DScene &sc, int blend_id, const DBsdf &blend, F2 uv) {
+    const int ti = as_global(sc.bsdf_tex)[MTS_BSDF_SP_COUNT * blend_id];
+    float w = blend.reflectance[0];
+    if (ti >= 0) {
+        const DTexture &t = sc.textures[ti];
+        const F3 c = texture_eval(t, uv);
+        w = (t.type == MTS_TEXTURE_BITMAP && t.channels == 3) ? c.x * 0.212671f + c.y * 0.715160f + c.z * 0.072169f : c.x;
+    }
+    return pm_min(pm_max(w, 0.f), 1.f);
+}
+// eval (:141-142) and pdf (:158-159): child 0, then child 1, one localised child record at a time (its own textures at the hit's uv);
+// the reference's two multiplies and one add each.
+template <bool U>
+DEV void blend_eval_pdf(const DScene &sc, const DBsdf &blend, float w, F2 uv, F3 wi, F3 wo, Spec &val, float &pdf) {
+    val = spec_s(0.f); pdf = 0.f;
+#pragma nounroll
+    for (int c = 0; c < 2; ++c) {
+        const int id = blend_child(blend, c);
+        DBsdf child = rload<U>(sc.bsdfs, id);
+        bsdf_apply_textures(sc, id, child, [&]() { return uv; });
+        const Spec v = bsdf_eval(child, wi, wo); const float p = bsdf_pdf(child, wi, wo);
+        if (c == 0) { val = v * (1.f - w); pdf = p * (1.f - w); }
+        else { val = val + v * w; pdf = pdf + p * w; }
+    }
+}
+// sample (:103-123): sample1 against the weight picks the child, which draws with the rescaled sample1 (true divisions); only that child
+// is localised.  The child's BSDFSample and weight come back unchanged: bs.pdf is the CHILD's density, not the mixture's, and the
+// integrators feed it to their MIS weights as it is -- a property of the reference, kept.
+template <bool U>
+DEV Spec blend_sample(const DScene &sc, const DBsdf &blend, float w, F2 uv, F3 wi, float sample1, F2 sample2, BSDFSample &bs) {
+    const bool first = sample1 > w;
+    const float s = first ? (sample1 - w) / (1.f - w) : sample1 / w;
+    Spec val = spec_s(0.f);
+#pragma nounroll
+    for (int c = 0; c < 2; ++c) {
+        if (first != (c == 0)) continue;
+        const int id = blend_child(blend, c);
+        DBsdf child = rload<U>(sc.bsdfs, id);
+        bsdf_apply_textures(sc, id, child, [&]() { return uv; });
+        val = bsdf_sample(child, wi, s, sample2, bs);
+    }
+    return val;
+}
+// eval + pdf, and sample, of the BSDF record `b` of a hit (a plain one localised already); TEX: a blend resolves through its children
+template <bool TEX, bool U>
+DEV void hit_bsdf_eval_pdf(const DScene &sc, const DBsdf &b, float w, F2 uv, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) {
+    if constexpr (TEX) if (b.type == MTS_BSDF_BLEND) { blend_eval_pdf<U>(sc, b, w, uv, wi, wo, val, pdf); return; }
+    val = bsdf_eval(b, wi, wo, cx, id); pdf = bsdf_pdf(b, wi, wo, cx, id);
+}
+template <bool TEX, bool U>
+DEV Spec hit_bsdf_sample(const DScene &sc, const DBsdf &b, float w, F2 uv, F3 wi, float sample1, F2 sample2, BSDFSample &bs, const SpecCtx &cx = SpecCtx(), int id = 0) {
+    if constexpr (TEX) if (b.type == MTS_BSDF_BLEND) return blend_sample<U>(sc, b, w, uv, wi, sample1, sample2, bs);
+    return bsdf_sample(b, wi, sample1, sample2, bs, cx, id);
+}
+// at(): the record of the hit; eval_pdf() / sample() on it.  TEX: a blend's weight and the hit's uv are evaluated once, in at(), and
+// serve eval, pdf and sample of that hit, as `local` does for colours.
 template <bool TEX> struct HitBsdf;
 template <> struct HitBsdf<false> {
     DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &, const Hit &) { return sc.bsdfs[bsdf_id]; }
+    DEV void eval_pdf(const DScene &sc, const DBsdf &b, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) const {
+        F2 none; none.x = none.y = 0.f; hit_bsdf_eval_pdf<false, false>(sc, b, 0.f, none, wi, wo, val, pdf, cx, id);
+    }
+    DEV Spec sample(const DScene &sc, const DBsdf &b, F3 wi, float sample1, F2 sample2, BSDFSample &bs, const SpecCtx &cx = SpecCtx(), int id = 0) const {
+        F2 none; none.x = none.y = 0.f; return hit_bsdf_sample<false, false>(sc, b, 0.f, none, wi, sample1, sample2, bs, cx, id);
+    }
 };
 template <> struct HitBsdf<true> {
-    DBsdf local;
+    DBsdf local; F2 uv; float w;
     DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &shape, const Hit &si) {
-        local = sc.bsdfs[bsdf_id];
-        bsdf_apply_textures(sc, bsdf_id, local, [&]() { return surface_uv(sc, shape, si); });
+        local = sc.bsdfs[bsdf_id]; uv.x = uv.y = 0.f; w = 0.f;
+        if (local.type == MTS_BSDF_BLEND) { uv = surface_uv(sc, shape, si); w = blend_weight(sc, bsdf_id, local, uv); }
+        else bsdf_apply_textures(sc, bsdf_id, local, [&]() { return surface_uv(sc, shape, si); });
         return local;
+    }
+    DEV void eval_pdf(const DScene &sc, const DBsdf &b, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) const {
+        hit_bsdf_eval_pdf<true, false>(sc, b, w, uv, wi, wo, val, pdf, cx, id);
+    }
+    DEV Spec sample(const DScene &sc, const DBsdf &b, F3 wi, float sample1, F2 sample2, BSDFSample &bs, const SpecCtx &cx = SpecCtx(), int id = 0) const {
+        return hit_bsdf_sample<true, false>(sc, b, w, uv, wi, sample1, sample2, bs, cx, id);
     }
 };
 
@@ -1468,13 +1546,13 @@ DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool
                 DirSample ds;
                 Spec emitted = volpath_sample_emitter<COUNT>(sc, si.p, false, rng, medium, channel, ds, cnt, cx);
                 F3 wo = to_local(sf.sh, ds.d);
-                Spec bsdf_val = bsdf_eval(bsdf, sf.wi, wo, cx, shape.bsdf);
-                float bpdf = bsdf_pdf(bsdf, sf.wi, wo, cx, shape.bsdf);
+                Spec bsdf_val; float bpdf;
+                hit_bsdf.eval_pdf(sc, bsdf, sf.wi, wo, bsdf_val, bpdf, cx, shape.bsdf);
                 result = result + throughput * bsdf_val * mis_weight(ds.pdf, ds.delta ? 0.f : bpdf) * emitted;
             }
             float s1 = rng.next_1d(); F2 s2 = rng.next_2d();
             BSDFSample bs;
-            Spec bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs, cx, shape.bsdf);
+            Spec bsdf_val = hit_bsdf.sample(sc, bsdf, sf.wi, s1, s2, bs, cx, shape.bsdf);
             throughput = throughput * bsdf_val;
             eta *= bs.eta;
             ray = spawn_ray(si.p, to_world(sf.sh, bs.wo));
@@ -1800,15 +1878,15 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
                 MisWeights<SPEC> nee_end, uni_end; DirSample ds;
                 Spec emitted = volpathmis_sample_emitter<COUNT, SPEC>(sc, si.p, false, rng, medium, p_over_f, channel, nee_end, uni_end, ds, cnt, cx);
                 F3 wo_local = to_local(sf.sh, ds.d);
-                Spec bsdf_val = bsdf_eval(bsdf, sf.wi, wo_local, cx, shape.bsdf);
-                float bpdf = bsdf_pdf(bsdf, sf.wi, wo_local, cx, shape.bsdf);
+                Spec bsdf_val; float bpdf;
+                hit_bsdf.eval_pdf(sc, bsdf, sf.wi, wo_local, bsdf_val, bpdf, cx, shape.bsdf);
                 update_weights(nee_end, 1.0f, bsdf_val, channel, true);
                 update_weights(uni_end, ds.delta ? 0.f : bpdf, bsdf_val, channel, true);
                 result = result + mis_weight_w(nee_end, uni_end) * emitted;
             }
             float s1 = rng.next_1d(); F2 s2 = rng.next_2d();
             BSDFSample bs;
-            Spec bsdf_weight = bsdf_sample(bsdf, sf.wi, s1, s2, bs, cx, shape.bsdf);
+            Spec bsdf_weight = hit_bsdf.sample(sc, bsdf, sf.wi, s1, s2, bs, cx, shape.bsdf);
             bool invalid_bsdf_sample = bs.pdf == 0.f;
             active_surface = active_surface && bs.pdf > 0.f;
             if (active_surface) eta *= bs.eta;
@@ -1862,14 +1940,14 @@ DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Co
             DirSample ds = sample_emitter_direction(sc, si.p, rng.next_2d(), true, emitter_val, cx);
             active_e = active_e && ds.pdf != 0.f;
             F3 wo = to_local(sf.sh, ds.d);
-            Spec bsdf_val = bsdf_eval(bsdf, sf.wi, wo, cx, bsdf_id);
-            float bpdf = bsdf_pdf(bsdf, sf.wi, wo, cx, bsdf_id);
+            Spec bsdf_val; float bpdf;
+            hit_bsdf.eval_pdf(sc, bsdf, sf.wi, wo, bsdf_val, bpdf, cx, bsdf_id);
             float mis = ds.delta ? 1.f : mis_weight(ds.pdf, bpdf);
             if (active_e) result = result + mis * throughput * bsdf_val * emitter_val;
         }
         float s1 = rng.next_1d(); F2 s2 = rng.next_2d();
         BSDFSample bs;
-        Spec bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs, cx, bsdf_id);
+        Spec bsdf_val = hit_bsdf.sample(sc, bsdf, sf.wi, s1, s2, bs, cx, bsdf_id);
         throughput = throughput * bsdf_val;
         active = active && any_nonzero(throughput);
         if (!active) break;

@@ -172,14 +172,14 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
                 DirSample ds = sample_emitter_direction(sc, si.p, rng.next_2d(), true, emitter_val MTS_CX);
                 active_e = active_e && ds.pdf != 0.f;
                 F3 wo = to_local(sf.sh, ds.d);
-                Spec bsdf_val = bsdf_eval(bsdf, sf.wi, wo MTS_CXI(bsdf_id));
-                float bpdf = bsdf_pdf(bsdf, sf.wi, wo MTS_CXI(bsdf_id));
+                Spec bsdf_val; float bpdf;
+                hit_bsdf.eval_pdf(sc, bsdf, sf.wi, wo, bsdf_val, bpdf MTS_CXI(bsdf_id));
                 float mis = ds.delta ? 1.f : mis_weight(ds.pdf, bpdf);
                 if (active_e) result = result + mis * throughput * bsdf_val * emitter_val;
             }
             float s1 = rng.next_1d(); F2 s2 = rng.next_2d();
             BSDFSample bs;
-            Spec bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs MTS_CXI(bsdf_id));
+            Spec bsdf_val = hit_bsdf.sample(sc, bsdf, sf.wi, s1, s2, bs MTS_CXI(bsdf_id));
             throughput = throughput * bsdf_val;
             ended = !any_nonzero(throughput);
             if (!ended) {
@@ -354,7 +354,7 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis_m
     ring_workgroup_async<VolpathMisRing<false, SPEC, WG, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
 }
 
-// ---- textured scenes (mts_scene_desc.textures): the per-lane kernels above with TEX = true -- every BSDF parameter of a hit goes
+// ---- textured scenes (mts_scene_desc.textures) and scenes with a blendbsdf: the per-lane kernels above with TEX = true -- every BSDF parameter of a hit goes
 // through its texture (integrator_dev.h: HitBsdf) -- under a name of their own: the plain instantiations stay what they are.
 // launch_render maps a row of the kernel table to one of these or to render_kernel_wga_tex below (kernel_names.h: kv::textured_variant).  FLAT: `path` as the flat
 // loop with regeneration; otherwise the nested formulation of whichever integrator the scene has, decided at run time.
@@ -656,7 +656,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
 
 hipError_t launch_sample(const DScene &sc, int32_t n, uint64_t seed_offset, const float *d_rays, float *d_rgb, uint8_t *d_valid, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sc.texture_count > 0 ? sample_kernel<true> : sample_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
+    hipLaunchKernelGGL(sc.bsdf_tex != nullptr ? sample_kernel<true> : sample_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
     return hipGetLastError();
 }
 

@@ -193,7 +193,7 @@ static DXf xf_perspective(float fov, float near_, float far_) {
 // Which promises of integrator_dev.h's scene traits (MT_*: what the lean translation units were compiled without) this scene keeps.
 // mts_render launches the leanest kernel whose promises are all kept; a scene that keeps none runs on the general kernels.
 static int scene_traits(const HostScene &hs, bool spectral) {
-    if (!hs.textures.empty()) return 0;                                 // a textured scene promises nothing: the general rgb / mono unit holds the TEX kernels
+    if (!hs.bsdf_tex.empty()) return 0;                                 // a scene with textures or a blendbsdf promises nothing: the general rgb / mono unit holds the TEX kernels
     int tr = 0;
     bool media = !hs.media.empty();
     for (size_t i = 0; i < hs.media.size(); ++i) {
@@ -433,14 +433,38 @@ static void build_pair_grid(const DVolume &a, const std::vector<float> &ga, cons
 }
 
 static DBsdf build_bsdf(const mts_bsdf &b) {
-    if (b.type < MTS_BSDF_DIFFUSE || b.type > MTS_BSDF_BILAMBERTIAN) throw std::runtime_error("unknown BSDF type");
+    if (b.type < MTS_BSDF_DIFFUSE || b.type > MTS_BSDF_BLEND) throw std::runtime_error("unknown BSDF type");
     DBsdf db; memset(&db, 0, sizeof(db));
-    db.type = b.type; memcpy(db.reflectance, b.reflectance, 12); memcpy(db.rho_0, b.rho_0, 12); memcpy(db.k, b.k, 12);
+    db.type = b.type;
+    if (b.type == MTS_BSDF_BLEND) {                          // blendbsdf.cpp:59-81; DBsdf (dscene.h) says where a blend keeps what; flags: resolve_blend
+        if (!std::isfinite(b.reflectance[0])) throw std::runtime_error("blendbsdf: \"reflectance[0]\" (the constant weight) is not finite");
+        db.reflectance[0] = b.reflectance[0];
+        memcpy(&db.rho_0[0], &b.spectrum[0], 4); memcpy(&db.rho_0[1], &b.spectrum[1], 4);
+        return db;
+    }
+    memcpy(db.reflectance, b.reflectance, 12); memcpy(db.rho_0, b.rho_0, 12); memcpy(db.k, b.k, 12);
     memcpy(db.g, b.g, 12); memcpy(db.rho_c, b.rho_c, 12); memcpy(db.transmittance, b.transmittance, 12); db.flags = bsdf_flags(b.type);
     return db;
 }
-// which of the six colour parameters each BSDF plugin reads (spectral variant: the spectra it needs)
-static const bool BSDF_SP_USED[4][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */ };
+static int32_t blend_child(const DBsdf &b, int c) { int32_t v; memcpy(&v, &b.rho_0[c], 4); return v; }
+// A blend's children, once every record of the description is built (a child may stand behind its blend): the two indices, the kinds
+// of BSDF this backend nests, and the blend's flags -- the union of its children's (blendbsdf.cpp:80).  n: the description's bsdf_count
+static void resolve_blend(DBsdf &db, int i, const std::vector<DBsdf> &all, int32_t n) {
+    for (int c = 0; c < 2; ++c) {
+        const std::string field = "bsdf " + std::to_string(i) + ": blendbsdf: \"spectrum[" + std::to_string(c) + "]\" (bsdf_" + std::to_string(c) + ")";
+        const int32_t ch = blend_child(db, c);
+        if (ch < 0 || ch >= n) throw std::runtime_error("index out of range: " + field);
+        if (ch == i) throw std::runtime_error(field + " is the blend itself");
+        const int t = all[(size_t) ch].type;
+        // a null or a nested child needs the component flags the integrators read (BSDFContext::component); a limit of this backend
+        if (t == MTS_BSDF_NULL) throw std::runtime_error(field + " is a null BSDF: null children are not supported by this backend");
+        if (t == MTS_BSDF_BLEND) throw std::runtime_error(field + " is a blendbsdf: nested blends are not supported by this backend");
+    }
+    db.flags = all[(size_t) blend_child(db, 0)].flags | all[(size_t) blend_child(db, 1)].flags;
+}
+// which of the six colour parameters each BSDF plugin reads (spectral variant: the spectra it needs); a blend: slot 0 is its weight's texture
+static const bool BSDF_SP_USED[5][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */,
+                                         { 1, 0, 0, 0, 0, 0 } /* blend */ };
 
 // A texture's record and (bitmap) its texels as the device holds them: validated as BitmapTexture's / Checkerboard's constructors
 // validate (bitmap.cpp:92-206, checkerboard.cpp:40-44).  `with_data` = false: the record alone (an update checks the frozen fields first).
@@ -539,12 +563,20 @@ static void build_media(const mts_scene_desc &d, bool spectral, HostScene &hs) {
 // BSDFs, and the default ones appended after the user's (shape.cpp:74-80): diffuse 0.5, and diffuse 0 for emitters
 struct DefaultBsdfs { int plain, emitter; };
 static DefaultBsdfs build_bsdfs(const mts_scene_desc &d, bool spectral, HostScene &hs) {
+    for (int i = 0; i < d.bsdf_count; ++i)                               // a blend is refused where textures are, and for the same reasons (build_textures)
+        if (d.bsdfs[i].type == MTS_BSDF_BLEND) {
+            if (spectral) throw std::runtime_error("bsdf " + std::to_string(i) + ": blendbsdf is not supported in the spectral variant");
+            if (d.integrator.moment != 0) throw std::runtime_error("bsdf " + std::to_string(i) + ": blendbsdf is not supported inside a moment integrator's scene");
+        }
     for (int i = 0; i < d.bsdf_count; ++i) {
         const mts_bsdf &b = d.bsdfs[i];
-        hs.bsdfs.push_back(build_bsdf(b));
+        try { hs.bsdfs.push_back(build_bsdf(b)); }
+        catch (const std::runtime_error &e) { if (b.type != MTS_BSDF_BLEND) throw; throw std::runtime_error("bsdf " + std::to_string(i) + ": " + e.what()); }
         if (spectral)                                                    // which of the six colour parameters each plugin reads
             for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(BSDF_SP_USED[b.type][k] ? spectrum_index(d, b.spectrum[k], "a BSDF parameter") : 0);
     }
+    for (int i = 0; i < d.bsdf_count; ++i)
+        if (hs.bsdfs[(size_t) i].type == MTS_BSDF_BLEND) resolve_blend(hs.bsdfs[(size_t) i], i, hs.bsdfs, d.bsdf_count);
     DefaultBsdfs ids; DBsdf def; memset(&def, 0, sizeof(def)); def.type = MTS_BSDF_DIFFUSE; def.flags = bsdf_flags(MTS_BSDF_DIFFUSE);
     def.reflectance[0] = def.reflectance[1] = def.reflectance[2] = .5f; ids.plain = (int) hs.bsdfs.size(); hs.bsdfs.push_back(def);
     def.reflectance[0] = def.reflectance[1] = def.reflectance[2] = 0.f; ids.emitter = (int) hs.bsdfs.size(); hs.bsdfs.push_back(def);
@@ -564,11 +596,15 @@ static void bsdf_texture_indices(const mts_scene_desc &d, int i, int32_t out[MTS
     }
 }
 // Textures (after the BSDFs: the table has a row for each of them, the two default ones included).  A scene without a texture
-// record keeps all three arrays empty, whatever its index table says.
+// record keeps all three arrays empty, whatever its index table says -- unless it holds a blendbsdf: then the table alone exists.
+// A non-empty table is what sends a scene to the TEX instantiations (scene_traits, capi.cpp).
 static void build_textures(const mts_scene_desc &d, bool spectral, HostScene &hs) {
     if (d.texture_count < 0 || (d.texture_count > 0 && !d.textures)) throw std::runtime_error("textures: a negative count, or records missing");
     if (d.texture_count == 0) {
         for (int i = 0; i < d.bsdf_count; ++i) { int32_t t[MTS_BSDF_SP_COUNT]; bsdf_texture_indices(d, i, t); }        // nothing but -1 is in range
+        // a blend renders in the TEX instantiations, which read the index table: all -1 under a constant weight and plain children
+        for (int i = 0; i < d.bsdf_count; ++i)
+            if (d.bsdfs[i].type == MTS_BSDF_BLEND) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
         return;
     }
     // rgb texels need the sRGB upsampling model (bitmap.cpp:169-178), whose data this backend has not got -- as for three-channel grids
@@ -943,7 +979,7 @@ void upload_host_scene(HostScene &hs, int device) {
     sc.sensor.rfilter.values = upload(hs, hs.rfilter_values);
     sc.sensor.multi = upload(hs, hs.multi_transforms);
     sc.textures = nullptr; sc.bsdf_tex = nullptr;
-    if (!hs.textures.empty()) {
+    if (!hs.bsdf_tex.empty()) {
         for (size_t i = 0; i < hs.textures.size(); ++i)
             if (hs.textures[i].type == MTS_TEXTURE_BITMAP) hs.textures[i].data = upload(hs, hs.texels[i]);
         sc.textures = upload(hs, hs.textures); sc.bsdf_tex = upload(hs, hs.bsdf_tex);
@@ -1078,11 +1114,18 @@ void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *
             if (spectral)
                 for (int s = 0; s < MTS_BSDF_SP_COUNT; ++s)
                     if (BSDF_SP_USED[b.type][s] && b.spectrum[s] != hs.bsdf_sp[(size_t) i * MTS_BSDF_SP_COUNT + s]) frozen(name, i, "spectrum");
-            if (n_textures > 0) {
+            if (!hs.bsdf_tex.empty()) {
                 int32_t t[MTS_BSDF_SP_COUNT]; bsdf_texture_indices(*d, i, t);
                 if (memcmp(t, &hs.bsdf_tex[(size_t) i * MTS_BSDF_SP_COUNT], sizeof(t)) != 0) frozen(name, i, "bsdf_textures");
             }
-            bsdfs[i] = build_bsdf(b);
+            try { bsdfs[i] = build_bsdf(b); }
+            catch (const std::runtime_error &e) { refuse(name, i, e.what()); }
+            if (b.type == MTS_BSDF_BLEND) {                    // the children are topology; their types are frozen too, so the flags stay
+                const DBsdf &old = hs.bsdfs[(size_t) i];
+                if (b.spectrum[0] != blend_child(old, 0)) frozen(name, i, "spectrum[0] (bsdf_0)");
+                if (b.spectrum[1] != blend_child(old, 1)) frozen(name, i, "spectrum[1] (bsdf_1)");
+                bsdfs[i].flags = old.flags;
+            }
             break; }
         case MTS_OBJ_TEXTURE: {                                // new texels / checkerboard colours (bitmap.cpp:562-564, checkerboard.cpp:92-96)
             if (!d->textures) refuse(name, i, "the description holds no texture records");

@@ -978,9 +978,9 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         Spec bsdf_val; float bpdf;
         WATERFALL_BEGIN(bsdf_id, bu)
             DBsdf bsdf = cload(sc.bsdfs + bu);
-            if constexpr (TEX) bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; });
-            bsdf_val = bsdf_eval(bsdf, sf.wi, wo MTS_CXI(bu));
-            bpdf = bsdf_pdf(bsdf, sf.wi, wo MTS_CXI(bu));
+            float blend_w = 0.f;                               // TEX: a blendbsdf's weight at the hit (the BSDF block evaluates the same again)
+            if constexpr (TEX) { if (bsdf.type == MTS_BSDF_BLEND) blend_w = blend_weight(sc, bu, bsdf, tex_uv); else bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; }); }
+            hit_bsdf_eval_pdf<TEX, true>(sc, bsdf, blend_w, tex_uv, sf.wi, wo, bsdf_val, bpdf MTS_CXI(bu));
         WATERFALL_END
         e.cold.put_spec(C_CW, p.thr * bsdf_val * mis_weight(ds.pdf, ds.delta ? 0.f : bpdf)); e.cold.put_spec(C_EMIT, emitter_val);
         e.cold.put_hit(p.si); e.cold.put3(C_SD, p.ray.d); e.cold.f(C_SMED) = __int_as_float(p.medium);
@@ -1012,8 +1012,9 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         } else {
             WATERFALL_BEGIN(bsdf_id, bu)
                 DBsdf bsdf = cload(sc.bsdfs + bu);
-                if constexpr (TEX) bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; });
-                bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs MTS_CXI(bu));
+                float blend_w = 0.f;                           // TEX: a blendbsdf's weight at the hit
+                if constexpr (TEX) { if (bsdf.type == MTS_BSDF_BLEND) blend_w = blend_weight(sc, bu, bsdf, tex_uv); else bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; }); }
+                bsdf_val = hit_bsdf_sample<TEX, true>(sc, bsdf, blend_w, tex_uv, sf.wi, s1, s2, bs MTS_CXI(bu));
             WATERFALL_END
         }
         p.thr = p.thr * bsdf_val;

@@ -71,6 +71,9 @@ def _collect(keep):
         if node[0] == "colour":                                 # srgb.cpp:59-61 / srgb_d65.cpp:63-65
             params[name + ".value"] = _Param(node[1], node[2], "rgb", node[3], node[4], node[5])
             return
+        if node[0] == "uniform":                                # uniform.cpp:108-112 in the rgb / mono variants: a blendbsdf's constant weight
+            params[name + ".value"] = _Param(node[1], node[2], "weight", node[3], node[4])
+            return
         if node[0] == "spectrum":
             plugin = keep.spectrum_plugins[node[1]]
             if plugin == "uniform":                             # uniform.cpp:108-112
@@ -151,6 +154,8 @@ class ParameterMap:
             return np.array(list(rec.to_uv), np.float32).reshape(3, 3)
         if p.what == "rgb":
             return np.array(list(getattr(rec, p.field.split("+")[0])), np.float32)
+        if p.what == "weight":
+            return getattr(rec, p.field)[0]
         if p.what == "range":
             return (rec.lambda_min, rec.lambda_max)
         if p.what == "values":
@@ -227,6 +232,8 @@ class ParameterMap:
             return arr, None
         if p.what == "rgb":
             return SD._color(value, p.where, emitter=p.emitter), None
+        if p.what == "weight":
+            return (SD._weight(value, p.where),) * 3, None
         if p.what == "range":
             lo, hi = (float(x) for x in value)
             return (lo, hi), None

@@ -346,6 +346,40 @@ def _color_rgb(v, where, default=None, emitter=False):
     raise RuntimeError("Cannot interpret %r as a colour in %s" % (v, where))
 
 
+def _weight(v, where):
+    """The constant "weight" of a blendbsdf: what Texture::eval_1 gives (blendbsdf.cpp:162-164).  A float or a `uniform` spectrum is its
+    value (uniform.cpp:71-75).  An rgb colour or a tabulated spectrum becomes an `srgb` texture in the rgb / mono variants (xml.cpp:1073-1170),
+    and src/spectra/srgb.cpp does not override eval_1: the reference throws there, so it is refused here."""
+    undefined = "eval_1 is not defined for an rgb colour (src/spectra/srgb.cpp implements eval only): give a float or a uniform spectrum"
+    if isinstance(v, dict):
+        t = v.get("type")
+        if t == "uniform" or (t == "spectrum" and _spectrum_pairs(v, where) is None):
+            val = v.get("value", 1.0)
+            if isinstance(val, (list, tuple, np.ndarray)):
+                raise RuntimeError("\"weight\" in %s takes one value" % where)
+            return float(val)
+        if t in ("rgb", "srgb", "srgb_d65", "spectrum"):
+            raise RuntimeError("\"weight\" in %s: %s" % (where, undefined))
+        raise RuntimeError("Unsupported texture / spectrum plugin \"%s\" in %s" % (t, where))
+    c = np.asarray(v, dtype=np.float32).reshape(-1)
+    if c.size != 1:
+        raise RuntimeError("\"weight\" in %s: %s" % (where, undefined))
+    return float(c[0])
+
+
+def _check_weight_texture(d, rec, where):
+    """A checkerboard under a blendbsdf's "weight" is read through eval_1 of its two colours (checkerboard.cpp:67-86): they must be
+    floats or uniform spectra, as a constant weight (_weight).  A bitmap has eval_1 for one and three channels (bitmap.cpp:285-302)."""
+    if rec.type != A.TEXTURE_CHECKERBOARD:
+        return
+    for key in ("color0", "color1"):
+        if isinstance(d, dict) and d.get("type") == "checkerboard":
+            if key in d:
+                _weight(d[key], where + "." + key)
+        elif not (getattr(rec, key)[0] == getattr(rec, key)[1] == getattr(rec, key)[2]):
+            raise RuntimeError("\"weight\" in %s: eval_1 is not defined for the rgb colour \"%s\" of the referenced checkerboard" % (where, key))
+
+
 def parse_fov(p, aspect):
     """src/librender/sensor.cpp:113-167."""
     if p.has("fov") and p.has("focal_length"):
@@ -470,6 +504,7 @@ class SceneBuilder:
         # textures behind BSDF colour parameters (rgb / mono): the records, six indices per BSDF (-1: the constant), each bitmap's
         # live (height, width, channels) array
         self.textures, self.bsdf_textures, self.bitmaps = [], [], {}
+        self.blends = []         # where each blendbsdf sits (what a refusal of the whole scene names)
 
     def _colour_node(self, kind, index, field, where, spectrum=-1, emitter=False):
         return ("spectrum", spectrum) if _SPECTRAL is not None else ("colour", kind, index, field, where, emitter)
@@ -778,6 +813,41 @@ class SceneBuilder:
                 textures[4] = textures[1]
                 if textures[1] < 0:
                     node[0] = ("object", "rho_0", ("colour", "bsdf", len(self.bsdfs), "rho_0+rho_c", where, False))
+        elif p.type == "blendbsdf":                                      # src/bsdfs/blendbsdf.cpp:59-81
+            rec.type = A.BSDF_BLEND
+            if spectral:
+                raise RuntimeError("\"blendbsdf\" is not supported in the spectral variant (%s): refused where textures are, its weight is one" % where)
+            children = []
+            for k, v in sorted_items(d):                                 # the nested BSDFs in Properties order (:61-69), whatever they are called
+                if k in ("type", "id", "weight") or not isinstance(v, dict):
+                    continue
+                if v.get("type") == "ref" and self.instances.get(v.get("id"), ("bsdf",))[0] != "bsdf":
+                    continue
+                if len(children) == 2:
+                    raise RuntimeError("BlendBSDF: Cannot specify more than two child BSDFs")
+                p.queried.add(k)
+                child = self.add_bsdf(v, where + "." + k)
+                for plugin, kind in (("null", A.BSDF_NULL), ("blendbsdf", A.BSDF_BLEND)):
+                    if self.bsdfs[child].type == kind:
+                        raise RuntimeError("\"blendbsdf\" %s: the nested BSDF \"%s\" is a \"%s\", which this backend cannot nest in a blend (a null or "
+                                           "nested child needs the component flags the integrators read)" % (where, k, plugin))
+                children.append(child)
+            if not p.has("weight"):
+                raise RuntimeError("Property \"weight\" has not been specified!")        # props.texture("weight"), :71
+            wv, wwhere = p.get("weight"), where + ".weight"
+            if len(children) != 2:
+                raise RuntimeError("BlendBSDF: Two child BSDFs must be specified!")
+            rec.spectrum[0], rec.spectrum[1] = children                  # mtsamd.h: a blend's use of the record
+            if self._is_texture(wv):
+                textures[0] = self.add_texture(wv, wwhere)
+                _check_weight_texture(wv, self.textures[textures[0]], wwhere)
+                rec.reflectance[:] = (0.5, 0.5, 0.5)                     # (what a reader that knows no textures sees)
+                node.append(("object", "weight", ("texture", textures[0])))
+            else:
+                rec.reflectance[:] = (_weight(wv, wwhere),) * 3
+                node.append(("object", "weight", ("uniform", "bsdf", len(self.bsdfs), "reflectance", wwhere)))
+            node += [("object", "bsdf_0", ("bsdf", children[0])), ("object", "bsdf_1", ("bsdf", children[1]))]      # :166-170
+            self.blends.append(where)
         else:
             raise RuntimeError("Unknown / unsupported BSDF plugin \"%s\"" % p.type)
         p.finish()
@@ -844,7 +914,7 @@ class SceneBuilder:
                 continue
             t = v.get("type")
             kind = self.instances.get(v.get("id"), ("",))[0] if t == "ref" else None
-            if t in ("diffuse", "null", "rpv", "bilambertian") or kind == "bsdf":
+            if t in ("diffuse", "null", "rpv", "bilambertian", "blendbsdf") or kind == "bsdf":
                 if rec.bsdf >= 0:
                     raise RuntimeError("Only a single BSDF child object can be specified per shape.")
                 p.queried.add(k)
@@ -1297,7 +1367,7 @@ class SceneBuilder:
                 if self.integrator is not None:
                     raise RuntimeError("Only one integrator can be specified per scene.")
                 self.set_integrator(v, k)
-            elif t in ("diffuse", "null", "rpv", "bilambertian"):
+            elif t in ("diffuse", "null", "rpv", "bilambertian", "blendbsdf"):
                 self.children.append((name, ("bsdf", self.add_bsdf(v, k))))
             elif t in ("homogeneous", "heterogeneous"):
                 self.children.append((name, ("medium", self.add_medium(v, k))))
@@ -1315,6 +1385,8 @@ class SceneBuilder:
             self.set_integrator({"type": "path"}, "integrator")          # scene.cpp:88-92
         if self.textures and self.integrator.moment:
             raise RuntimeError("Textures inside a moment integrator's scene are not supported by this backend")
+        if self.blends and self.integrator.moment:
+            raise RuntimeError("\"blendbsdf\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.blends))
         return self.finish()
 
     def finish(self):

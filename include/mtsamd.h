@@ -108,8 +108,17 @@ typedef struct mts_medium {
     int32_t has_spectral_extinction; /* default true (homogeneous.cpp:27, heterogeneous.cpp:27) */
 } mts_medium;
 
-/* ---- BSDFs (src/bsdfs/{diffuse,null,rpv,bilambertian}.cpp) ---- */
-enum { MTS_BSDF_DIFFUSE = 0, MTS_BSDF_NULL = 1, MTS_BSDF_RPV = 2, MTS_BSDF_BILAMBERTIAN = 3 };
+/* ---- BSDFs (src/bsdfs/{diffuse,null,rpv,bilambertian,blendbsdf}.cpp) ----
+ *      MTS_BSDF_BLEND (rgb / mono variants; not with mts_integrator.moment): blendbsdf.cpp, two nested BSDFs mixed by "weight".  It
+ *      adds no field -- a blend record uses the existing ones (a library from before it refuses type 4 as unknown):
+ *        reflectance[0]             the constant "weight" (clamped to [0, 1] where it is evaluated, blendbsdf.cpp:162-164)
+ *        spectrum[0], spectrum[1]   the indices of bsdf_0 and bsdf_1 in mts_scene_desc.bsdfs: the nested BSDFs in the name order of
+ *                                   the plugin's Properties (blendbsdf.cpp:61-69).  Neither a null BSDF nor another blend (limits of
+ *                                   this backend), nor the record itself; a child may stand before or behind its blend
+ *        bsdf_textures slot 0       the weight's texture, or -1: Texture::eval_1 of a bitmap (one channel: the texel; three: the
+ *                                   luminance of the interpolated colour, bitmap.cpp:285-302) or a checkerboard (colour 0 of the cell's
+ *                                   colour).  The children's rows hold their own textures as for any BSDF. */
+enum { MTS_BSDF_DIFFUSE = 0, MTS_BSDF_NULL = 1, MTS_BSDF_RPV = 2, MTS_BSDF_BILAMBERTIAN = 3, MTS_BSDF_BLEND = 4 };
 typedef struct mts_bsdf {
     int32_t type;
     float reflectance[3];     /* diffuse "reflectance" (rgb), default 0.5                        */
@@ -278,7 +287,7 @@ typedef struct mts_scene_desc {
     const mts_spectrum *spectra; int32_t spectrum_count;  /* spectral variant only */
     /* Textures (rgb / mono variants; not with mts_integrator.moment).  bsdf_textures: NULL = no texture anywhere, else six indices
        into `textures` per BSDF, in the order of mts_bsdf.spectrum[] (reflectance, rho_0, k, g, rho_c, transmittance); -1 = the
-       constant in mts_bsdf.  A zeroed tail means "no textures". */
+       constant in mts_bsdf (a blend's slot 0: its weight).  A zeroed tail means "no textures". */
     const mts_texture *textures; int32_t texture_count;
     const int32_t *bsdf_textures;                         /* 6 * bsdf_count, or NULL */
 } mts_scene_desc;
@@ -306,7 +315,7 @@ typedef struct mts_stats {
                                      (expensive blocks first; its samples are discarded)          */
     int32_t reserved_;
     double calibration_ms;    /* device time of that launch                                      */
-    int32_t textured;         /* 1 when a textured instantiation rendered (a scene with mts_scene_desc.textures): kernel_variant still names
+    int32_t textured;         /* 1 when the scene was rendered by the TEX instantiations (a scene with mts_scene_desc.textures or a blendbsdf): kernel_variant still names
                                  the row of the kernel table the scene gets; kernel_names.h: kv::textured_variant maps it to the kernel that ran */
     int32_t reserved2_;
 } mts_stats;

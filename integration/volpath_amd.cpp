@@ -229,7 +229,7 @@ private:
     }
 
     // ---- BSDFs: diffuse (diffuse.cpp:137-139 "reflectance"), null, rpv (rpv.cpp:169-174 "rho_0", "g", "k", "rho_c"), bilambertian
-    // (bilambertian.cpp:195-198 "reflectance", "transmittance")
+    // (bilambertian.cpp:195-198 "reflectance", "transmittance"), blendbsdf (blendbsdf.cpp:166-170 "weight", "bsdf_0", "bsdf_1")
     int32_t visit_bsdf(const BSDF *b) {
         if (auto it = m_bsdf_of.find(b); it != m_bsdf_of.end()) return it->second;
         const std::string cls = props_of(b).plugin_name();
@@ -245,6 +245,18 @@ private:
         } else if (cls == "bilambertian") {
             r.type = MTS_BSDF_BILAMBERTIAN;
             colour(tex("reflectance"), r.reflectance, r.spectrum[0]); colour(tex("transmittance"), r.transmittance, r.spectrum[5]);
+        } else if (cls == "blendbsdf") {                                            // blendbsdf.cpp:166-170: "weight", "bsdf_0", "bsdf_1"
+            // MTS_BSDF_BLEND (mtsamd.h): reflectance[0] = the constant weight, spectrum[0 / 1] = the children's indices.  This visitor
+            // hands over constants only (colour() above), so a weight that varies over the surface is refused rather than frozen at uv = 0.
+            if constexpr (is_spectral_v<Spectrum>) Throw("volpath_amd: blendbsdf is not supported in the spectral variants");
+            r.type = MTS_BSDF_BLEND;
+            const Texture *w = tex("weight");
+            if (props_of(w).plugin_name() != "uniform")
+                Throw("volpath_amd: blendbsdf weight \"%s\": only a constant (uniform) weight is handed over by this integration", props_of(w).plugin_name());
+            SurfaceInteraction3f si = zero<SurfaceInteraction3f>();
+            r.reflectance[0] = r.reflectance[1] = r.reflectance[2] = (float) w->eval_1(si, true);
+            r.spectrum[0] = visit_bsdf((const BSDF *) k.object("bsdf_0"));
+            r.spectrum[1] = visit_bsdf((const BSDF *) k.object("bsdf_1"));
         } else
             Throw("volpath_amd: BSDF plugin \"%s\"", cls);
         bsdfs.push_back(r); return m_bsdf_of[b] = (int32_t) bsdfs.size() - 1;
