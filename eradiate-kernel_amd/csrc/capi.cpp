@@ -320,7 +320,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
                                  (hs.integrator.moment ? "X, Y, Z, A, W + the moment integrator's m1.X, m1.Y, m1.Z, m2.X, m2.Y, m2.Z)" : "X, Y, Z, A, W + two per spectral bin)"));
     const KernelChoice kc = kernel_of(hs, block_size, sw, opts.collect_counters != 0);
     // a textured scene: the TEX instantiation that renders the table's row (kernel_names.h); mts_stats.kernel_variant keeps naming the row
-    const bool textured = !hs.bsdf_tex.empty();            // texture records or a blendbsdf (scene_host.cpp: build_textures)
+    const bool textured = !hs.bsdf_tex.empty();            // texture records, a blendbsdf or a twosided (scene_host.cpp: build_textures)
     const int variant = textured ? kv::textured_variant(kc.variant, hs.integrator.type, hs.scene.sensor.wavefront != 0, opts.collect_counters != 0) : kc.variant;
 #if defined(MTSAMD_HOST_ONLY)
     (void) stream; (void) t0; (void) stats; (void) variant;

@@ -67,6 +67,8 @@ struct DMedium {
 // A blendbsdf (MTS_BSDF_BLEND; TEX instantiations only) keeps in the same record: reflectance[0] = its constant weight, the bits of
 // rho_0[0] / rho_0[1] = the indices of bsdf_0 / bsdf_1, flags = the union of its children's (blendbsdf.cpp:80); slot 0 of its bsdf_tex
 // row = the weight's texture.
+// A twosided (MTS_BSDF_TWOSIDED; TEX instantiations only) keeps the bits of rho_0[0] / rho_0[1] = the indices of brdf_0 (the side
+// cos_theta(wi) > 0) / brdf_1 (< 0), equal when one child was given, and flags = the union of twosided.cpp:78-88; nothing else is read.
 struct DBsdf { int32_t type; float reflectance[3], rho_0[3], k[3], g[3], rho_c[3]; uint32_t flags; float transmittance[3]; };
 
 // Textures behind a BSDF's colour parameters (textures/bitmap.cpp, textures/checkerboard.cpp; rgb / mono variants).  to_uv: row-major
@@ -206,7 +208,7 @@ struct DScene {
     // shape: no emitter term, no emitter sample, no BSDF evaluation at such a hit.  The ring machines sort these hits into a class of
     // their own (volpath_flat.h: B_CROSS).  Set where the shape records are built (scene_host.cpp: add_shape); a shape beyond 63 has no bit.
     uint64_t cross_mask;
-    // Scenes with textures or a blendbsdf only (rgb / mono; NULL / 0 otherwise; a blend scene without textures has bsdf_tex alone), at the END of the record: everything above keeps its offset, so the plain
+    // Scenes with textures, a blendbsdf or a twosided only (rgb / mono; NULL / 0 otherwise; a blend or twosided scene without textures has bsdf_tex alone), at the END of the record: everything above keeps its offset, so the plain
     // kernels read what they always read.  bsdf_tex: per BSDF (the two default ones included) MTS_BSDF_SP_COUNT indices into
     // textures, in the order reflectance, rho_0, k, g, rho_c, transmittance; -1 = the constant in DBsdf.  Only the TEX
     // instantiations (integrator_dev.h: HitBsdf) read them.
@@ -218,6 +220,6 @@ struct DScene {
 // bsdf.h:38-124
 enum : uint32_t { F_Null = 0x1, F_DiffuseReflection = 0x2, F_DiffuseTransmission = 0x4, F_GlossyReflection = 0x8,
                   F_FrontSide = 0x8000, F_BackSide = 0x10000,
-                  F_Smooth = 0x2 | 0x4 | 0x8 | 0x10, F_Delta = 0x1 | 0x20 | 0x40 };
+                  F_Smooth = 0x2 | 0x4 | 0x8 | 0x10, F_Delta = 0x1 | 0x20 | 0x40, F_Transmission = 0x4 | 0x10 | 0x40 | 0x100 | 0x1 };
 
 } // namespace mtsamd

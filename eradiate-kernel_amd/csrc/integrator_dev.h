@@ -1276,11 +1276,31 @@ DEV Spec hit_bsdf_sample(const DScene &sc, const DBsdf &b, float w, F2 uv, F3 wi
     if constexpr (TEX) if (b.type == MTS_BSDF_BLEND) return blend_sample<U>(sc, b, w, uv, wi, sample1, sample2, bs);
     return bsdf_sample(b, wi, sample1, sample2, bs, cx, id);
 }
-// at(): the record of the hit; eval_pdf() / sample() on it.  TEX: a blend's weight and the hit's uv are evaluated once, in at(), and
+// ---- twosided (bsdfs/twosided.cpp:94-181; DBsdf in dscene.h says where the record keeps its children).  TEX instantiations only, as
+// a blend.  The record of a hit, given its BSDF id and the local wi: brdf_0 for cos_theta(wi) > 0, brdf_1 for < 0 (:106-107, :136-137,
+// :164-165) with `back` set -- the caller then negates wi.z, and wo.z before eval / pdf (:146-147, :174-175) and after sample (:118-121);
+// weight, pdf, eta and sampled_type stay the child's.  wi.z == 0 (or NaN) is neither side (`none`): eval and pdf are 0 by the
+// children's own tests of wi.z > 0, sample is the zero sample (:109).  Any other record resolves to itself.  Loads per lane: the side
+// differs from lane to lane, so the ring machine calls this BEFORE its waterfall and runs that over the resolved id.
+// The ctx.component arithmetic (:115-116, :143-144, :171-172) is never reached by path / volpath / volpathmis and is not restated.
+struct BsdfSide { int id; bool back, none; };
+DEV BsdfSide twosided_side(const DScene &sc, int bsdf_id, F3 wi) {
+    BsdfSide s; s.id = bsdf_id; s.back = s.none = false;
+    const MTS_GLOBAL_AS DBsdf *rec = as_global(sc.bsdfs) + bsdf_id;
+    if (rec->type == MTS_BSDF_TWOSIDED) {
+        s.back = wi.z < 0.f; s.none = !s.back && !(wi.z > 0.f);
+        s.id = __float_as_int(s.back ? rec->rho_0[1] : rec->rho_0[0]);
+    }
+    return s;
+}
+DEV void zero_bsdf_sample(BSDFSample &bs) { bs.wo = f3s(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.sampled_type = 0; }
+// at(): the record of the hit; eval_pdf() / sample() on it.  TEX: a twosided's side is resolved once, in at(), from the local wi --
+// `local` is then the child's record, its flags included (the child is smooth whenever the adapter's union is, for the children this
+// backend nests, so the callers' NEE test reads the same); a blend's weight and the hit's uv are evaluated once, in at(), too, and
 // serve eval, pdf and sample of that hit, as `local` does for colours.
 template <bool TEX> struct HitBsdf;
 template <> struct HitBsdf<false> {
-    DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &, const Hit &) { return sc.bsdfs[bsdf_id]; }
+    DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &, const Hit &, F3) { return sc.bsdfs[bsdf_id]; }
     DEV void eval_pdf(const DScene &sc, const DBsdf &b, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) const {
         F2 none; none.x = none.y = 0.f; hit_bsdf_eval_pdf<false, false>(sc, b, 0.f, none, wi, wo, val, pdf, cx, id);
     }
@@ -1289,18 +1309,25 @@ template <> struct HitBsdf<false> {
     }
 };
 template <> struct HitBsdf<true> {
-    DBsdf local; F2 uv; float w;
-    DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &shape, const Hit &si) {
+    DBsdf local; F2 uv; float w; bool back, none;
+    DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &shape, const Hit &si, F3 wi) {
+        const BsdfSide side = twosided_side(sc, bsdf_id, wi);
+        bsdf_id = side.id; back = side.back; none = side.none;
         local = sc.bsdfs[bsdf_id]; uv.x = uv.y = 0.f; w = 0.f;
         if (local.type == MTS_BSDF_BLEND) { uv = surface_uv(sc, shape, si); w = blend_weight(sc, bsdf_id, local, uv); }
         else bsdf_apply_textures(sc, bsdf_id, local, [&]() { return surface_uv(sc, shape, si); });
         return local;
     }
     DEV void eval_pdf(const DScene &sc, const DBsdf &b, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) const {
+        if (back) { wi.z = -wi.z; wo.z = -wo.z; }
         hit_bsdf_eval_pdf<true, false>(sc, b, w, uv, wi, wo, val, pdf, cx, id);
     }
     DEV Spec sample(const DScene &sc, const DBsdf &b, F3 wi, float sample1, F2 sample2, BSDFSample &bs, const SpecCtx &cx = SpecCtx(), int id = 0) const {
-        return hit_bsdf_sample<true, false>(sc, b, w, uv, wi, sample1, sample2, bs, cx, id);
+        if (none) { zero_bsdf_sample(bs); return spec_s(0.f); }
+        if (back) wi.z = -wi.z;
+        const Spec val = hit_bsdf_sample<true, false>(sc, b, w, uv, wi, sample1, sample2, bs, cx, id);
+        if (back) bs.wo.z = -bs.wo.z;
+        return val;
     }
 };
 
@@ -1540,7 +1567,7 @@ DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool
         if (active_surface) {
             const DShape &shape = sc.shapes[si.shape];
             HitBsdf<TEX> hit_bsdf;
-            const DBsdf &bsdf = hit_bsdf.at(sc, shape.bsdf, shape, si);
+            const DBsdf &bsdf = hit_bsdf.at(sc, shape.bsdf, shape, si, sf.wi);
             bool active_e = (bsdf.flags & F_Smooth) != 0 && (depth + 1 < max_depth);
             if (active_e) {
                 DirSample ds;
@@ -1872,7 +1899,7 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
         if (active_surface) {
             const DShape &shape = sc.shapes[si.shape];
             HitBsdf<TEX> hit_bsdf;
-            const DBsdf &bsdf = hit_bsdf.at(sc, shape.bsdf, shape, si);
+            const DBsdf &bsdf = hit_bsdf.at(sc, shape.bsdf, shape, si, sf.wi);
             bool active_e = (bsdf.flags & F_Smooth) != 0 && (depth + 1 < max_depth);
             if (active_e) {
                 MisWeights<SPEC> nee_end, uni_end; DirSample ds;
@@ -1933,7 +1960,7 @@ DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Co
         if ((uint32_t) depth >= (uint32_t) max_depth || !active) break;
         const int bsdf_id = sc.shapes[si.shape].bsdf;
         HitBsdf<TEX> hit_bsdf;
-        const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[si.shape], si);
+        const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[si.shape], si, sf.wi);
         bool active_e = (bsdf.flags & F_Smooth) != 0;
         if (active_e) {
             Spec emitter_val;

@@ -165,7 +165,7 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
         if (!ended) {
             const int bsdf_id = sc.shapes[si.shape].bsdf;
             HitBsdf<TEX> hit_bsdf;
-            const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[si.shape], si);
+            const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[si.shape], si, sf.wi);
             bool active_e = (bsdf.flags & F_Smooth) != 0;
             if (active_e) {
                 Spec emitter_val;
@@ -354,7 +354,7 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis_m
     ring_workgroup_async<VolpathMisRing<false, SPEC, WG, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
 }
 
-// ---- textured scenes (mts_scene_desc.textures) and scenes with a blendbsdf: the per-lane kernels above with TEX = true -- every BSDF parameter of a hit goes
+// ---- textured scenes (mts_scene_desc.textures) and scenes with a blendbsdf or a twosided: the per-lane kernels above with TEX = true -- every BSDF parameter of a hit goes
 // through its texture (integrator_dev.h: HitBsdf) -- under a name of their own: the plain instantiations stay what they are.
 // launch_render maps a row of the kernel table to one of these or to render_kernel_wga_tex below (kernel_names.h: kv::textured_variant).  FLAT: `path` as the flat
 // loop with regeneration; otherwise the nested formulation of whichever integrator the scene has, decided at run time.

@@ -16,7 +16,7 @@ struct RenderArgs {
     const uint32_t *tiles; uint32_t n_tiles;        // cost-sorted tiles of the regrouping kernels (volpath_flat.h, WgArgs::tiles) or NULL
     hipStream_t stream;
     bool moment;                                    // the `moment` integrator's eleven-channel film (general rgb / mono unit only; variant = kv::moment_variant())
-    bool textured;                                  // the scene has textures or a blendbsdf (general rgb / mono unit only; variant = kv::textured_variant())
+    bool textured;                                  // the scene has textures, a blendbsdf or a twosided (general rgb / mono unit only; variant = kv::textured_variant())
 };
 typedef hipError_t (*RenderLauncher)(const RenderArgs &);
 size_t render_workspace_floats(uint64_t paths, int variant);

@@ -193,7 +193,7 @@ static DXf xf_perspective(float fov, float near_, float far_) {
 // Which promises of integrator_dev.h's scene traits (MT_*: what the lean translation units were compiled without) this scene keeps.
 // mts_render launches the leanest kernel whose promises are all kept; a scene that keeps none runs on the general kernels.
 static int scene_traits(const HostScene &hs, bool spectral) {
-    if (!hs.bsdf_tex.empty()) return 0;                                 // a scene with textures or a blendbsdf promises nothing: the general rgb / mono unit holds the TEX kernels
+    if (!hs.bsdf_tex.empty()) return 0;                                 // a scene with textures, a blendbsdf or a twosided promises nothing: the general rgb / mono unit holds the TEX kernels
     int tr = 0;
     bool media = !hs.media.empty();
     for (size_t i = 0; i < hs.media.size(); ++i) {
@@ -433,9 +433,13 @@ static void build_pair_grid(const DVolume &a, const std::vector<float> &ga, cons
 }
 
 static DBsdf build_bsdf(const mts_bsdf &b) {
-    if (b.type < MTS_BSDF_DIFFUSE || b.type > MTS_BSDF_BLEND) throw std::runtime_error("unknown BSDF type");
+    if (b.type < MTS_BSDF_DIFFUSE || b.type > MTS_BSDF_TWOSIDED || b.type == 5) throw std::runtime_error("unknown BSDF type");      // 5: unassigned (mtsamd.h)
     DBsdf db; memset(&db, 0, sizeof(db));
     db.type = b.type;
+    if (b.type == MTS_BSDF_TWOSIDED) {                       // twosided.cpp:63-92: the two child indices and nothing else; flags: resolve_twosided
+        memcpy(&db.rho_0[0], &b.spectrum[0], 4); memcpy(&db.rho_0[1], &b.spectrum[1], 4);
+        return db;
+    }
     if (b.type == MTS_BSDF_BLEND) {                          // blendbsdf.cpp:59-81; DBsdf (dscene.h) says where a blend keeps what; flags: resolve_blend
         if (!std::isfinite(b.reflectance[0])) throw std::runtime_error("blendbsdf: \"reflectance[0]\" (the constant weight) is not finite");
         db.reflectance[0] = b.reflectance[0];
@@ -459,12 +463,30 @@ static void resolve_blend(DBsdf &db, int i, const std::vector<DBsdf> &all, int32
         // a null or a nested child needs the component flags the integrators read (BSDFContext::component); a limit of this backend
         if (t == MTS_BSDF_NULL) throw std::runtime_error(field + " is a null BSDF: null children are not supported by this backend");
         if (t == MTS_BSDF_BLEND) throw std::runtime_error(field + " is a blendbsdf: nested blends are not supported by this backend");
+        if (t == MTS_BSDF_TWOSIDED) throw std::runtime_error(field + " is a twosided: a twosided inside a blend is not supported by this backend");
     }
     db.flags = all[(size_t) blend_child(db, 0)].flags | all[(size_t) blend_child(db, 1)].flags;
 }
+// A twosided's children, once every record is built and every blend resolved (a blend child's flags are its own children's union): the
+// two indices, the nesting this backend lacks, the reference's transmission rule (twosided.cpp:90-91; Null is one of
+// BSDFFlags::Transmission's bits, bsdf.h) decided from the children's flags, and the record's own flags (:78-88).
+static void resolve_twosided(DBsdf &db, int i, const std::vector<DBsdf> &all, int32_t n) {
+    uint32_t side[2];
+    for (int c = 0; c < 2; ++c) {
+        const std::string field = "bsdf " + std::to_string(i) + ": twosided: \"spectrum[" + std::to_string(c) + "]\" (brdf_" + std::to_string(c) + ")";
+        const int32_t ch = blend_child(db, c);
+        if (ch < 0 || ch >= n) throw std::runtime_error("index out of range: " + field);
+        if (ch == i) throw std::runtime_error(field + " is the twosided itself");
+        if (all[(size_t) ch].type == MTS_BSDF_TWOSIDED) throw std::runtime_error(field + " is a twosided: nested twosided adapters are not supported by this backend");
+        side[c] = all[(size_t) ch].flags;
+    }
+    db.flags = ((side[0] & ~F_BackSide) | F_FrontSide) | ((side[1] & ~F_FrontSide) | F_BackSide);
+    if (db.flags & F_Transmission) throw std::runtime_error("bsdf " + std::to_string(i) + ": twosided: Only materials without a transmission component can be nested!");
+}
 // which of the six colour parameters each BSDF plugin reads (spectral variant: the spectra it needs); a blend: slot 0 is its weight's texture
-static const bool BSDF_SP_USED[5][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */,
-                                         { 1, 0, 0, 0, 0, 0 } /* blend */ };
+// twosided reads no colour parameter and no texture slot (type 5 is unassigned)
+static const bool BSDF_SP_USED[7][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */,
+                                         { 1, 0, 0, 0, 0, 0 } /* blend */, { 0, 0, 0, 0, 0, 0 } /* unassigned */, { 0, 0, 0, 0, 0, 0 } /* twosided */ };
 
 // A texture's record and (bitmap) its texels as the device holds them: validated as BitmapTexture's / Checkerboard's constructors
 // validate (bitmap.cpp:92-206, checkerboard.cpp:40-44).  `with_data` = false: the record alone (an update checks the frozen fields first).
@@ -567,16 +589,21 @@ static DefaultBsdfs build_bsdfs(const mts_scene_desc &d, bool spectral, HostScen
         if (d.bsdfs[i].type == MTS_BSDF_BLEND) {
             if (spectral) throw std::runtime_error("bsdf " + std::to_string(i) + ": blendbsdf is not supported in the spectral variant");
             if (d.integrator.moment != 0) throw std::runtime_error("bsdf " + std::to_string(i) + ": blendbsdf is not supported inside a moment integrator's scene");
+        } else if (d.bsdfs[i].type == MTS_BSDF_TWOSIDED) {               // and so is a twosided: it renders in the TEX instantiations alone
+            if (spectral) throw std::runtime_error("bsdf " + std::to_string(i) + ": twosided is not supported in the spectral variant");
+            if (d.integrator.moment != 0) throw std::runtime_error("bsdf " + std::to_string(i) + ": twosided is not supported inside a moment integrator's scene");
         }
     for (int i = 0; i < d.bsdf_count; ++i) {
         const mts_bsdf &b = d.bsdfs[i];
         try { hs.bsdfs.push_back(build_bsdf(b)); }
-        catch (const std::runtime_error &e) { if (b.type != MTS_BSDF_BLEND) throw; throw std::runtime_error("bsdf " + std::to_string(i) + ": " + e.what()); }
+        catch (const std::runtime_error &e) { if (b.type != MTS_BSDF_BLEND && b.type != MTS_BSDF_TWOSIDED) throw; throw std::runtime_error("bsdf " + std::to_string(i) + ": " + e.what()); }
         if (spectral)                                                    // which of the six colour parameters each plugin reads
             for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(BSDF_SP_USED[b.type][k] ? spectrum_index(d, b.spectrum[k], "a BSDF parameter") : 0);
     }
     for (int i = 0; i < d.bsdf_count; ++i)
         if (hs.bsdfs[(size_t) i].type == MTS_BSDF_BLEND) resolve_blend(hs.bsdfs[(size_t) i], i, hs.bsdfs, d.bsdf_count);
+    for (int i = 0; i < d.bsdf_count; ++i)                               // after every blend: a blend child's flags are read, wherever it stands
+        if (hs.bsdfs[(size_t) i].type == MTS_BSDF_TWOSIDED) resolve_twosided(hs.bsdfs[(size_t) i], i, hs.bsdfs, d.bsdf_count);
     DefaultBsdfs ids; DBsdf def; memset(&def, 0, sizeof(def)); def.type = MTS_BSDF_DIFFUSE; def.flags = bsdf_flags(MTS_BSDF_DIFFUSE);
     def.reflectance[0] = def.reflectance[1] = def.reflectance[2] = .5f; ids.plain = (int) hs.bsdfs.size(); hs.bsdfs.push_back(def);
     def.reflectance[0] = def.reflectance[1] = def.reflectance[2] = 0.f; ids.emitter = (int) hs.bsdfs.size(); hs.bsdfs.push_back(def);
@@ -596,15 +623,15 @@ static void bsdf_texture_indices(const mts_scene_desc &d, int i, int32_t out[MTS
     }
 }
 // Textures (after the BSDFs: the table has a row for each of them, the two default ones included).  A scene without a texture
-// record keeps all three arrays empty, whatever its index table says -- unless it holds a blendbsdf: then the table alone exists.
+// record keeps all three arrays empty, whatever its index table says -- unless it holds a blendbsdf or a twosided: then the table alone exists.
 // A non-empty table is what sends a scene to the TEX instantiations (scene_traits, capi.cpp).
 static void build_textures(const mts_scene_desc &d, bool spectral, HostScene &hs) {
     if (d.texture_count < 0 || (d.texture_count > 0 && !d.textures)) throw std::runtime_error("textures: a negative count, or records missing");
     if (d.texture_count == 0) {
         for (int i = 0; i < d.bsdf_count; ++i) { int32_t t[MTS_BSDF_SP_COUNT]; bsdf_texture_indices(d, i, t); }        // nothing but -1 is in range
-        // a blend renders in the TEX instantiations, which read the index table: all -1 under a constant weight and plain children
+        // a blend or a twosided renders in the TEX instantiations, which read the index table: all -1 under a constant weight and plain children
         for (int i = 0; i < d.bsdf_count; ++i)
-            if (d.bsdfs[i].type == MTS_BSDF_BLEND) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
+            if (d.bsdfs[i].type == MTS_BSDF_BLEND || d.bsdfs[i].type == MTS_BSDF_TWOSIDED) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
         return;
     }
     // rgb texels need the sRGB upsampling model (bitmap.cpp:169-178), whose data this backend has not got -- as for three-channel grids
@@ -1120,10 +1147,11 @@ void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *
             }
             try { bsdfs[i] = build_bsdf(b); }
             catch (const std::runtime_error &e) { refuse(name, i, e.what()); }
-            if (b.type == MTS_BSDF_BLEND) {                    // the children are topology; their types are frozen too, so the flags stay
+            if (b.type == MTS_BSDF_BLEND || b.type == MTS_BSDF_TWOSIDED) {     // the children are topology; their types are frozen too, so the flags stay
                 const DBsdf &old = hs.bsdfs[(size_t) i];
-                if (b.spectrum[0] != blend_child(old, 0)) frozen(name, i, "spectrum[0] (bsdf_0)");
-                if (b.spectrum[1] != blend_child(old, 1)) frozen(name, i, "spectrum[1] (bsdf_1)");
+                const bool two = b.type == MTS_BSDF_TWOSIDED;
+                if (b.spectrum[0] != blend_child(old, 0)) frozen(name, i, two ? "spectrum[0] (brdf_0)" : "spectrum[0] (bsdf_0)");
+                if (b.spectrum[1] != blend_child(old, 1)) frozen(name, i, two ? "spectrum[1] (brdf_1)" : "spectrum[1] (bsdf_1)");
                 bsdfs[i].flags = old.flags;
             }
             break; }

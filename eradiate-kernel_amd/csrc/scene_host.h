@@ -41,7 +41,7 @@ struct HostScene {
     std::vector<int32_t> bsdf_sp, emitter_sp; std::vector<DVolumeSp> volume_sp;
     // textured scenes (DScene::textures ...): the records, each bitmap's texels as the device holds them (three-channel texels padded
     // to four floats), and the per-BSDF index table; all three empty in a scene without textures -- but for the table of a scene that
-    // holds a blendbsdf: a non-empty table is what sends a scene to the TEX instantiations
+    // holds a blendbsdf or a twosided: a non-empty table is what sends a scene to the TEX instantiations
     std::vector<DTexture> textures; std::vector<std::vector<float>> texels; std::vector<int32_t> bsdf_tex;
     std::vector<void *> device_allocs;
     // mts_scene_update: two words per volume the grid pass reduces into (launch.h: GridUpdateJob::stats), allocated by the first update

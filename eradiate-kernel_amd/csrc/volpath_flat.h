@@ -974,13 +974,22 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         Spec emitter_val;                                      // volpath.cpp:200-212 -> sample_emitter :261-281
         DirSample ds = sample_emitter_direction(sc, p.si.p, p.rng.next_2d(), false, emitter_val MTS_CX);
         if (ds.pdf == 0.f) return;
-        F3 wo = to_local(sf.sh, ds.d);
+        F3 wo = to_local(sf.sh, ds.d), wi = sf.wi;
         Spec bsdf_val; float bpdf;
+        // TEX: a twosided's child depends on the lane -- its side of incidence -- so it is resolved per lane, with three per-lane
+        // dword loads of the hit's own record, BEFORE the waterfall; that then runs over the resolved id and its record loads stay
+        // wave-uniform (scalar loads into SGPRs).  The flips are per lane too; emitter_eval above read the unflipped sf.wi.z.
+        // active_e above read the flags of the hit's own record, the union of both sides' (twosided.cpp:78-88).
+        if constexpr (TEX) {
+            const BsdfSide side = twosided_side(sc, bsdf_id, wi);
+            bsdf_id = side.id;
+            if (side.back) { wi.z = -wi.z; wo.z = -wo.z; }
+        }
         WATERFALL_BEGIN(bsdf_id, bu)
             DBsdf bsdf = cload(sc.bsdfs + bu);
             float blend_w = 0.f;                               // TEX: a blendbsdf's weight at the hit (the BSDF block evaluates the same again)
             if constexpr (TEX) { if (bsdf.type == MTS_BSDF_BLEND) blend_w = blend_weight(sc, bu, bsdf, tex_uv); else bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; }); }
-            hit_bsdf_eval_pdf<TEX, true>(sc, bsdf, blend_w, tex_uv, sf.wi, wo, bsdf_val, bpdf MTS_CXI(bu));
+            hit_bsdf_eval_pdf<TEX, true>(sc, bsdf, blend_w, tex_uv, wi, wo, bsdf_val, bpdf MTS_CXI(bu));
         WATERFALL_END
         e.cold.put_spec(C_CW, p.thr * bsdf_val * mis_weight(ds.pdf, ds.delta ? 0.f : bpdf)); e.cold.put_spec(C_EMIT, emitter_val);
         e.cold.put_hit(p.si); e.cold.put3(C_SD, p.ray.d); e.cold.f(C_SMED) = __int_as_float(p.medium);
@@ -1010,12 +1019,22 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
             DBsdf bsdf = {}; bsdf.type = MTS_BSDF_NULL;            // null.cpp:41-58 reads nothing else of it
             bsdf_val = bsdf_sample(bsdf, sf.wi, s1, s2, bs MTS_CXI(bsdf_id));
         } else {
-            WATERFALL_BEGIN(bsdf_id, bu)
+            F3 wi = sf.wi;
+            BsdfSide side; side.id = bsdf_id; side.back = side.none = false;
+            if constexpr (TEX) {                               // a twosided's child, per lane and before the waterfall, as in blk_surf
+                side = twosided_side(sc, bsdf_id, wi);
+                if (side.back) wi.z = -wi.z;
+            }
+            WATERFALL_BEGIN(side.id, bu)
                 DBsdf bsdf = cload(sc.bsdfs + bu);
                 float blend_w = 0.f;                           // TEX: a blendbsdf's weight at the hit
                 if constexpr (TEX) { if (bsdf.type == MTS_BSDF_BLEND) blend_w = blend_weight(sc, bu, bsdf, tex_uv); else bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; }); }
-                bsdf_val = hit_bsdf_sample<TEX, true>(sc, bsdf, blend_w, tex_uv, sf.wi, s1, s2, bs MTS_CXI(bu));
+                bsdf_val = hit_bsdf_sample<TEX, true>(sc, bsdf, blend_w, tex_uv, wi, s1, s2, bs MTS_CXI(bu));
             WATERFALL_END
+            if constexpr (TEX) {
+                if (side.back) bs.wo.z = -bs.wo.z;             // twosided.cpp:121
+                if (side.none) { zero_bsdf_sample(bs); bsdf_val = spec_s(0.f); }     // wi.z == 0: neither side (:109)
+            }
         }
         p.thr = p.thr * bsdf_val;
         p.eta *= bs.eta;

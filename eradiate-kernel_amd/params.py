@@ -53,7 +53,7 @@ class _Param:
 
 def _collect(keep):
     """The reference's SceneTraversal (util.py:149-188) over the builder's notes: {key: _Param}, in traversal order."""
-    params, seen, prefixes = {}, set(), set()
+    params, seen, prefixes, named = {}, set(), set(), {}
 
     def unique(name):
         base, ctr = name, 1
@@ -68,6 +68,7 @@ def _collect(keep):
             return
         seen.add(node)
         name = unique(name)
+        named[node] = name
         if node[0] == "colour":                                 # srgb.cpp:59-61 / srgb_d65.cpp:63-65
             params[name + ".value"] = _Param(node[1], node[2], "rgb", node[3], node[4], node[5])
             return
@@ -90,6 +91,12 @@ def _collect(keep):
         for entry in keep.nodes.get(node, []):
             if entry[0] == "param":
                 params[name + "." + entry[1]] = _Param(node[0], node[1], entry[2], entry[3])
+            elif entry[0] == "alias":                           # twosided.cpp:183-186 with one child: brdf_1 is brdf_0, whose keys it repeats
+                src = name + ".brdf_0"
+                if named.get(entry[2]) == src:                  # (listed elsewhere before, a shared object: under neither name, as ever)
+                    dst = unique(name + "." + entry[1])
+                    for k in [k for k in params if k.startswith(src + ".")]:
+                        params[dst + k[len(src):]] = params[k]
             else:
                 visit(entry[2], name + "." + entry[1])
 

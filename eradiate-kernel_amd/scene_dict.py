@@ -346,6 +346,10 @@ def _color_rgb(v, where, default=None, emitter=False):
     raise RuntimeError("Cannot interpret %r as a colour in %s" % (v, where))
 
 
+# BSDFFlags (bsdf.h:38-124) that the twosided adapter's constructor reads; Transmission holds Null
+_F_FRONT, _F_BACK, _F_TRANSMISSION = 0x8000, 0x10000, 0x4 | 0x10 | 0x40 | 0x100 | 0x1
+
+
 def _weight(v, where):
     """The constant "weight" of a blendbsdf: what Texture::eval_1 gives (blendbsdf.cpp:162-164).  A float or a `uniform` spectrum is its
     value (uniform.cpp:71-75).  An rgb colour or a tabulated spectrum becomes an `srgb` texture in the rgb / mono variants (xml.cpp:1073-1170),
@@ -496,7 +500,8 @@ class SceneBuilder:
         self.mono = self.spectral = False
         # traverse() (params.py): what each record exposes, written down while it is built.  nodes[(kind, index)] lists, in the order of
         # the reference plugin's traverse(), ("param", name, what, field) and ("object", name, node) entries; a colour is a node of its
-        # own (`srgb` / `uniform` texture): ("colour", kind, index, field, where, emitter) in rgb / mono, ("spectrum", index) in spectral
+        # own (`srgb` / `uniform` texture): ("colour", kind, index, field, where, emitter) in rgb / mono, ("spectrum", index) in spectral.
+        # ("alias", name, node): a one-child twosided's brdf_1, the node listed under brdf_0 just before -- its keys again, under this name
         self.nodes = {}
         self.children = []       # the scene's own children: (key, node)
         self.grids, self.grid_mono_max, self.tabs = {}, {}, {}
@@ -505,6 +510,7 @@ class SceneBuilder:
         # live (height, width, channels) array
         self.textures, self.bsdf_textures, self.bitmaps = [], [], {}
         self.blends = []         # where each blendbsdf sits (what a refusal of the whole scene names)
+        self.twosided = []       # and each twosided
 
     def _colour_node(self, kind, index, field, where, spectrum=-1, emitter=False):
         return ("spectrum", spectrum) if _SPECTRAL is not None else ("colour", kind, index, field, where, emitter)
@@ -827,7 +833,7 @@ class SceneBuilder:
                     raise RuntimeError("BlendBSDF: Cannot specify more than two child BSDFs")
                 p.queried.add(k)
                 child = self.add_bsdf(v, where + "." + k)
-                for plugin, kind in (("null", A.BSDF_NULL), ("blendbsdf", A.BSDF_BLEND)):
+                for plugin, kind in (("null", A.BSDF_NULL), ("blendbsdf", A.BSDF_BLEND), ("twosided", A.BSDF_TWOSIDED)):
                     if self.bsdfs[child].type == kind:
                         raise RuntimeError("\"blendbsdf\" %s: the nested BSDF \"%s\" is a \"%s\", which this backend cannot nest in a blend (a null or "
                                            "nested child needs the component flags the integrators read)" % (where, k, plugin))
@@ -848,6 +854,36 @@ class SceneBuilder:
                 node.append(("object", "weight", ("uniform", "bsdf", len(self.bsdfs), "reflectance", wwhere)))
             node += [("object", "bsdf_0", ("bsdf", children[0])), ("object", "bsdf_1", ("bsdf", children[1]))]      # :166-170
             self.blends.append(where)
+        elif p.type == "twosided":                                       # src/bsdfs/twosided.cpp:63-92
+            rec.type = A.BSDF_TWOSIDED
+            if spectral:
+                raise RuntimeError("\"twosided\" is not supported in the spectral variant (%s): it renders in the kernels of textured scenes, "
+                                   "which that variant has not got" % where)
+            children = []
+            for k, v in sorted_items(d):                                 # the nested BSDFs in Properties order (:64-70), whatever they are called
+                if k in ("type", "id") or not isinstance(v, dict):
+                    continue
+                if v.get("type") == "ref" and self.instances.get(v.get("id"), ("bsdf",))[0] != "bsdf":
+                    continue
+                if len(children) == 2:
+                    raise RuntimeError("At most two nested BSDFs can be specified!")
+                p.queried.add(k)
+                child = self.add_bsdf(v, where + "." + k)
+                if self.bsdfs[child].type == A.BSDF_TWOSIDED:
+                    raise RuntimeError("\"twosided\" %s: the nested BSDF \"%s\" is a \"twosided\", which this backend cannot nest in another" % (where, k))
+                children.append(child)
+            if not children:
+                raise RuntimeError("A nested one-sided material is required!")
+            if len(children) == 1:
+                children.append(children[0])                             # :74-75
+            flags = ((self._bsdf_flags(children[0]) & ~_F_BACK) | _F_FRONT) | ((self._bsdf_flags(children[1]) & ~_F_FRONT) | _F_BACK)     # :78-88
+            if flags & _F_TRANSMISSION:
+                raise RuntimeError("Only materials without a transmission component can be nested!")
+            rec.spectrum[0], rec.spectrum[1] = children                  # mtsamd.h: a twosided's use of the record
+            # :183-186.  One child under both names: brdf_1 lists the keys of brdf_0 again, and an update through either rewrites the one record
+            node += [("object", "brdf_0", ("bsdf", children[0])),
+                     ("alias" if children[0] == children[1] else "object", "brdf_1", ("bsdf", children[1]))]
+            self.twosided.append(where)
         else:
             raise RuntimeError("Unknown / unsupported BSDF plugin \"%s\"" % p.type)
         p.finish()
@@ -856,6 +892,14 @@ class SceneBuilder:
         self.bsdfs.append(rec)
         self._register(d, "bsdf", len(self.bsdfs) - 1)
         return len(self.bsdfs) - 1
+
+    def _bsdf_flags(self, i):
+        """BSDFFlags of record i as the library computes them (scene_host.cpp: bsdf_flags, resolve_blend, resolve_twosided)."""
+        rec = self.bsdfs[i]
+        if rec.type in (A.BSDF_BLEND, A.BSDF_TWOSIDED):
+            return self._bsdf_flags(rec.spectrum[0]) | self._bsdf_flags(rec.spectrum[1])
+        return {A.BSDF_DIFFUSE: 0x2 | _F_FRONT, A.BSDF_NULL: 0x1 | _F_FRONT | _F_BACK, A.BSDF_RPV: 0x8 | _F_FRONT,
+                A.BSDF_BILAMBERTIAN: 0x2 | 0x4 | _F_FRONT | _F_BACK}[rec.type]
 
     # ------------------------------------------------------------ shapes
     def make_shape(self, d, where, in_scene=True):
@@ -914,7 +958,7 @@ class SceneBuilder:
                 continue
             t = v.get("type")
             kind = self.instances.get(v.get("id"), ("",))[0] if t == "ref" else None
-            if t in ("diffuse", "null", "rpv", "bilambertian", "blendbsdf") or kind == "bsdf":
+            if t in ("diffuse", "null", "rpv", "bilambertian", "blendbsdf", "twosided") or kind == "bsdf":
                 if rec.bsdf >= 0:
                     raise RuntimeError("Only a single BSDF child object can be specified per shape.")
                 p.queried.add(k)
@@ -1367,7 +1411,7 @@ class SceneBuilder:
                 if self.integrator is not None:
                     raise RuntimeError("Only one integrator can be specified per scene.")
                 self.set_integrator(v, k)
-            elif t in ("diffuse", "null", "rpv", "bilambertian", "blendbsdf"):
+            elif t in ("diffuse", "null", "rpv", "bilambertian", "blendbsdf", "twosided"):
                 self.children.append((name, ("bsdf", self.add_bsdf(v, k))))
             elif t in ("homogeneous", "heterogeneous"):
                 self.children.append((name, ("medium", self.add_medium(v, k))))
@@ -1387,6 +1431,8 @@ class SceneBuilder:
             raise RuntimeError("Textures inside a moment integrator's scene are not supported by this backend")
         if self.blends and self.integrator.moment:
             raise RuntimeError("\"blendbsdf\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.blends))
+        if self.twosided and self.integrator.moment:
+            raise RuntimeError("\"twosided\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.twosided))
         return self.finish()
 
     def finish(self):

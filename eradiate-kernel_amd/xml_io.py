@@ -202,7 +202,7 @@ class _Parser:
                     # props.objects()); the dictionary loader finds them by key, so a lone film / sampler / rfilter / bsdf /
                     # phase / emitter / medium child takes its tag as its name.  Everything else keeps the `_arg_N` of xml.cpp.
                     unique = tag in ("film", "sampler", "rfilter", "bsdf", "phase", "emitter", "medium") and node.tag != "scene" \
-                        and out.get("type") not in ("blendphase", "blendbsdf") and tag not in out and sum(1 for c in node if c.tag == tag and "name" not in c.attrib) == 1
+                        and out.get("type") not in ("blendphase", "blendbsdf", "twosided") and tag not in out and sum(1 for c in node if c.tag == tag and "name" not in c.attrib) == 1
                     if unique:
                         name = tag
                     else:

@@ -108,7 +108,7 @@ typedef struct mts_medium {
     int32_t has_spectral_extinction; /* default true (homogeneous.cpp:27, heterogeneous.cpp:27) */
 } mts_medium;
 
-/* ---- BSDFs (src/bsdfs/{diffuse,null,rpv,bilambertian,blendbsdf}.cpp) ----
+/* ---- BSDFs (src/bsdfs/{diffuse,null,rpv,bilambertian,blendbsdf,twosided}.cpp) ----
  *      MTS_BSDF_BLEND (rgb / mono variants; not with mts_integrator.moment): blendbsdf.cpp, two nested BSDFs mixed by "weight".  It
  *      adds no field -- a blend record uses the existing ones (a library from before it refuses type 4 as unknown):
  *        reflectance[0]             the constant "weight" (clamped to [0, 1] where it is evaluated, blendbsdf.cpp:162-164)
@@ -117,8 +117,18 @@ typedef struct mts_medium {
  *                                   this backend), nor the record itself; a child may stand before or behind its blend
  *        bsdf_textures slot 0       the weight's texture, or -1: Texture::eval_1 of a bitmap (one channel: the texel; three: the
  *                                   luminance of the interpolated colour, bitmap.cpp:285-302) or a checkerboard (colour 0 of the cell's
- *                                   colour).  The children's rows hold their own textures as for any BSDF. */
-enum { MTS_BSDF_DIFFUSE = 0, MTS_BSDF_NULL = 1, MTS_BSDF_RPV = 2, MTS_BSDF_BILAMBERTIAN = 3, MTS_BSDF_BLEND = 4 };
+ *                                   colour).  The children's rows hold their own textures as for any BSDF.
+ *      MTS_BSDF_TWOSIDED (rgb / mono variants; not with mts_integrator.moment): twosided.cpp, a front and a back material for one
+ *      surface.  It adds no field either (a library from before it refuses type 6 as unknown):
+ *        spectrum[0], spectrum[1]   the indices of brdf_0 (the side cos_theta(wi) > 0) and brdf_1 (cos_theta(wi) < 0) in
+ *                                   mts_scene_desc.bsdfs: the nested BSDFs in the name order of the plugin's Properties
+ *                                   (twosided.cpp:64-75), equal when one was given.  A diffuse, an rpv or a blend of those: the union
+ *                                   of the children's flags may hold no transmission bit (twosided.cpp:90-91; Null is one).  Neither
+ *                                   another twosided (a limit of this backend, as is a twosided inside a blend) nor the record itself;
+ *                                   a child may stand before or behind its parent.
+ *      Nothing else of a twosided record is read: no colour parameter, no texture slot.  The value 5 is left unassigned and stays refused
+ *      as "unknown BSDF type": the test suite probes 5 as the first unknown type. */
+enum { MTS_BSDF_DIFFUSE = 0, MTS_BSDF_NULL = 1, MTS_BSDF_RPV = 2, MTS_BSDF_BILAMBERTIAN = 3, MTS_BSDF_BLEND = 4, MTS_BSDF_TWOSIDED = 6 };
 typedef struct mts_bsdf {
     int32_t type;
     float reflectance[3];     /* diffuse "reflectance" (rgb), default 0.5                        */

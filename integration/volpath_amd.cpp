@@ -229,7 +229,8 @@ private:
     }
 
     // ---- BSDFs: diffuse (diffuse.cpp:137-139 "reflectance"), null, rpv (rpv.cpp:169-174 "rho_0", "g", "k", "rho_c"), bilambertian
-    // (bilambertian.cpp:195-198 "reflectance", "transmittance"), blendbsdf (blendbsdf.cpp:166-170 "weight", "bsdf_0", "bsdf_1")
+    // (bilambertian.cpp:195-198 "reflectance", "transmittance"), blendbsdf (blendbsdf.cpp:166-170 "weight", "bsdf_0", "bsdf_1"),
+    // twosided (twosided.cpp:183-186 "brdf_0", "brdf_1")
     int32_t visit_bsdf(const BSDF *b) {
         if (auto it = m_bsdf_of.find(b); it != m_bsdf_of.end()) return it->second;
         const std::string cls = props_of(b).plugin_name();
@@ -257,6 +258,12 @@ private:
             r.reflectance[0] = r.reflectance[1] = r.reflectance[2] = (float) w->eval_1(si, true);
             r.spectrum[0] = visit_bsdf((const BSDF *) k.object("bsdf_0"));
             r.spectrum[1] = visit_bsdf((const BSDF *) k.object("bsdf_1"));
+        } else if (cls == "twosided") {                                             // twosided.cpp:183-186: "brdf_0", "brdf_1" (one object under both names when one child was given)
+            // MTS_BSDF_TWOSIDED (mtsamd.h): spectrum[0 / 1] = the children's indices; the library applies the constructor's rules
+            if constexpr (is_spectral_v<Spectrum>) Throw("volpath_amd: twosided is not supported in the spectral variants");
+            r.type = MTS_BSDF_TWOSIDED;
+            r.spectrum[0] = visit_bsdf((const BSDF *) k.object("brdf_0"));
+            r.spectrum[1] = visit_bsdf((const BSDF *) k.object("brdf_1"));
         } else
             Throw("volpath_amd: BSDF plugin \"%s\"", cls);
         bsdfs.push_back(r); return m_bsdf_of[b] = (int32_t) bsdfs.size() - 1;
