@@ -26,6 +26,9 @@ MEDIUM_HOMOGENEOUS, MEDIUM_HETEROGENEOUS = 0, 1
 BSDF_DIFFUSE, BSDF_NULL, BSDF_RPV, BSDF_BILAMBERTIAN, BSDF_BLEND = 0, 1, 2, 3, 4
 BSDF_TWOSIDED = 6                # 5 stays unassigned (mtsamd.h)
 SHAPE_RECTANGLE, SHAPE_CUBE, SHAPE_SPHERE, SHAPE_MESH, SHAPE_DISK = 0, 1, 2, 3, 4
+# instanced geometry on the existing record (mtsamd.h): a group's face_count = its member count, the members follow it; an instance's
+# vertex_count = the index of its group's record
+SHAPE_SHAPEGROUP, SHAPE_INSTANCE = 5, 6
 EMITTER_DIRECTIONAL, EMITTER_AREA, EMITTER_CONSTANT, EMITTER_POINT = 0, 1, 2, 3
 SENSOR_PERSPECTIVE, SENSOR_DISTANT, SENSOR_MRADIANCEMETER, SENSOR_MDISTANT, SENSOR_DISTANTFLUX = 0, 1, 2, 3, 4
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
@@ -181,6 +184,7 @@ def lib():
     L.mts_debug_update_plan.argtypes = [C.POINTER(SceneDesc), C.POINTER(SceneDesc), C.POINTER(Dirty), i32, C.POINTER(i32), C.POINTER(i32)]
     L.mts_debug_scene_digest.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mts_debug_desc_digest.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint64)]
+    L.mts_debug_scene_geometry.argtypes = [C.POINTER(SceneDesc), C.POINTER(i32), C.POINTER(C.c_float)]
     L.mts_abi_sizeof.argtypes = [C.c_char_p]
     L.mts_abi_sizeof.restype = C.c_int
     if L.mts_abi_version() != MTS_ABI_VERSION:

@@ -283,6 +283,20 @@ int mts_debug_desc_digest(const mts_scene_desc *desc, uint64_t *out8) {
     API_CATCH
 }
 
+// Not part of the ABI: how a description's geometry is laid out on the host.  counts[6]: the scene level's primitives (an instance is
+// one), all primitives (the groups' members behind the scene's), instances, groups, the scene level's BVH nodes, all BVH nodes;
+// bbox[6]: the scene's bounding box, min then max.  Host only (tests/test_instance.py: members are not scene geometry).
+int mts_debug_scene_geometry(const mts_scene_desc *desc, int32_t *counts, float *bbox) {
+    API_TRY
+    if (!counts || !bbox) throw std::runtime_error("mts_debug_scene_geometry: NULL output");
+    HostScene *hs = build_host_scene(desc);
+    counts[0] = hs->scene.prim_count; counts[1] = (int32_t) hs->prims.size(); counts[2] = (int32_t) hs->instances.size(); counts[3] = (int32_t) hs->groups.size();
+    counts[4] = hs->scene.bvh_node_count; counts[5] = (int32_t) (hs->bvh_nodes.size() / 8);
+    for (int k = 0; k < 3; ++k) { bbox[k] = hs->scene.bbox.min[k]; bbox[3 + k] = hs->scene.bbox.max[k]; }
+    free_host_scene(hs);
+    API_CATCH
+}
+
 #if !defined(MTSAMD_HOST_ONLY)
 // the launcher of each unit (UNIT_GENERAL: launch_render, or launch_render_spectral for a scene of the spectral variant)
 #if defined(MTSAMD_BLOCKSTATS)
@@ -320,10 +334,11 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
                                  (hs.integrator.moment ? "X, Y, Z, A, W + the moment integrator's m1.X, m1.Y, m1.Z, m2.X, m2.Y, m2.Z)" : "X, Y, Z, A, W + two per spectral bin)"));
     const KernelChoice kc = kernel_of(hs, block_size, sw, opts.collect_counters != 0);
     // a textured scene: the TEX instantiation that renders the table's row (kernel_names.h); mts_stats.kernel_variant keeps naming the row
-    const bool textured = !hs.bsdf_tex.empty();            // texture records, a blendbsdf or a twosided (scene_host.cpp: build_textures)
+    const bool textured = !hs.bsdf_tex.empty();            // texture records, a blendbsdf or a twosided (scene_host.cpp: build_textures); an instanced scene has the table too
+    const bool instanced = !hs.instances.empty();          // the INST kernels (kernels.hip): the TEX instantiations over the two-level traversal, mapped from the row alike
     const int variant = textured ? kv::textured_variant(kc.variant, hs.integrator.type, hs.scene.sensor.wavefront != 0, opts.collect_counters != 0) : kc.variant;
 #if defined(MTSAMD_HOST_ONLY)
-    (void) stream; (void) t0; (void) stats; (void) variant;
+    (void) stream; (void) t0; (void) stats; (void) variant; (void) instanced;
     HOST_ONLY_STOP("mts_render");
 #else
     RenderCache &rc = scene->cache;
@@ -360,6 +375,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
     };
     try {
         last_variant = kv::stat(kc.variant, kc.unit);
+        if (instanced && (kc.unit != UNIT_GENERAL || hs.integrator.spectral || !textured)) throw std::runtime_error("mts_render: an instanced scene outside the general rgb / mono unit");
         const RenderLauncher launcher = kc.unit == UNIT_GENERAL && hs.integrator.spectral ? launch_render_spectral : RENDER_LAUNCHERS[kc.unit];
 
         // one launch over `blocks` with `spp` samples per pixel, watched for cancel() / the timeout (which reach the kernel through the stop word).
@@ -379,7 +395,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
             const size_t ws_records = hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS ? 2 : 1;
             float *d_ws = (float *) rc.get(BUF_WORKSPACE, render_workspace_floats(paths, variant) * ws_records * sizeof(float));
             const RenderArgs args = { &hs.scene, d_blocks, (uint32_t) blocks.size(), block_size, spp, d_target, d_counters, opts.collect_counters != 0, variant,
-                                      d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream, hs.integrator.moment != 0, textured };
+                                      d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream, hs.integrator.moment != 0, textured, instanced };
             HIP_CHECK(launcher(args));
             HIP_CHECK(hipEventRecord(rc.ev1, stream));
             for (;;) {
@@ -438,7 +454,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
             memset(stats, 0, sizeof(*stats));
             stats->samples = plan.samples; stats->n_iter = h_counters[0]; stats->n_lookup = h_counters[1]; stats->n_nee_step = h_counters[2];
             stats->kernel_ms = kernel_ms; stats->kernel_launches = launches; stats->cancelled = cancelled ? 1 : 0; stats->timed_out = timed_out ? 1 : 0; stats->kernel_variant = last_variant;
-            stats->calibration_ms = calibration_ms; stats->calibration_launches = calibration_launches; stats->textured = textured ? 1 : 0;
+            stats->calibration_ms = calibration_ms; stats->calibration_launches = calibration_launches; stats->textured = instanced ? 2 : textured ? 1 : 0;
             stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
     } catch (...) { (void) hipStreamSynchronize(stream); throw; }     // nothing of this render may still be using the cached buffers

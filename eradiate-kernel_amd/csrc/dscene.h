@@ -99,6 +99,20 @@ struct DPrim { int32_t shape, index; };
 // chain prim -> shape -> geometry): triangle: p0, e1, e2; rectangle: rows 0..2 of to_object; sphere: center, radius.
 struct DWalkPrim { int32_t type, shape, index, pad; float f[12]; };
 
+// Instanced geometry (shapes/shapegroup.cpp, shapes/instance.cpp, librender/shapegroup.cpp; read by the INST kernels only, kernels.hip: render_kernel_inst).
+// A shapegroup's members are DShape records like any other, but their primitives are not the scene's: they stand behind the scene's
+// own in prims / walk / tri / tri_attr / area_*, group by group, in GROUP space (the members' own to_world and nothing else), and a
+// group with more primitives than the BVH threshold has a BVH of its own behind the scene's in bvh_nodes / bvh_prims (node and leaf
+// indices absolute).  An instance is ONE primitive of the scene: a DWalkPrim of type MTS_SHAPE_INSTANCE whose shape = its index in
+// DScene::instances, index = its group's in DScene::groups, f = rows 0..2 of to_object -- the ray transform (instance.cpp:111-112)
+// needs that one record.  DScene::prim_count / bvh_node_count count the scene's own level.
+struct DGroup { DBBox bbox; int32_t node_first, node_count, prim_first, prim_count, shape, pad; };      // bbox: of the members (shapegroup.cpp: the group's kd-tree bbox); shape: the group's record
+struct DInstance { DXf to_world, to_object; int32_t group, shape, pad[2]; };                            // shape: the instance's record in DScene::shapes
+// A hit inside an instance keeps 1 + the instance's index in the bits of Hit::shape above the member's shape index (INST kernels only)
+#define MTS_INST_SHAPE_BITS 10
+#define MTS_INST_MAX_SHAPES (1 << MTS_INST_SHAPE_BITS)                  // shape records of an instanced scene
+#define MTS_INST_MAX_INSTANCES ((1 << (31 - MTS_INST_SHAPE_BITS)) - 2)  // 2^21 - 2 instances
+
 struct DEmitter { int32_t type; DXf to_world; float radiance[3]; int32_t shape; float bsphere_center[3], bsphere_radius; };
 
 struct DRFilter { int32_t type; float radius, stddev, alpha, bias; const float *values /* device, 32 entries (rfilter.cpp:9-20) */; float scale_factor; int32_t border_size; };
@@ -215,6 +229,10 @@ struct DScene {
     const DTexture *textures;
     const int32_t *bsdf_tex;
     int32_t texture_count, pad_;
+    // Instanced scenes only (NULL / 0 otherwise), behind the textured tail: nothing above moves.  Only the INST kernels read them.
+    const DInstance *instances;
+    const DGroup *groups;
+    int32_t instance_count, group_count;
 };
 
 // bsdf.h:38-124

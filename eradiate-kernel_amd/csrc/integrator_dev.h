@@ -126,6 +126,19 @@ DEV uint64_t wavefront_increment(const DSensor &se, const DBlock &blk, uint32_t 
 struct Hit { float t; F3 p; F2 uv; int32_t shape, prim; };
 struct Surf { F3 n; Frame3 sh; F3 wi; };
 DEV bool hit_valid(const Hit &h) { return h.t != pm_inf(); }
+// The shape record of a hit.  INST instantiations (instanced scenes: the TEX instantiations with TEX = TEX_INST): Hit::shape also carries 1 + the instance the hit lies in, above the
+// MTS_INST_SHAPE_BITS bits of the member's shape index (0: the scene's own geometry); every other kernel reads the field as it is.
+template <bool INST = false> DEV int hit_shape(const Hit &h) { if constexpr (INST) return h.shape < 0 ? 0 : (h.shape & (MTS_INST_MAX_SHAPES - 1)); else return h.shape; }
+DEV int hit_instance(const Hit &h) { return h.shape < 0 ? -1 : (h.shape >> MTS_INST_SHAPE_BITS) - 1; }
+// rows 0..2 of one matrix of an instance record, per lane (vector loads): `at` = 0 to_world.m, 16 to_world.it, 32 to_object.m
+DEV void instance_rows(const DScene &sc, int inst, int at, float out[12]) {
+    typedef int mts_int4 __attribute__((ext_vector_type(4)));
+    const MTS_GLOBAL_AS mts_int4 *rec = (const MTS_GLOBAL_AS mts_int4 *) as_global((const float *) (sc.instances + inst) + at);
+    const mts_int4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+    out[0] = __int_as_float(r0.x); out[1] = __int_as_float(r0.y); out[2] = __int_as_float(r0.z); out[3] = __int_as_float(r0.w);
+    out[4] = __int_as_float(r1.x); out[5] = __int_as_float(r1.y); out[6] = __int_as_float(r1.z); out[7] = __int_as_float(r1.w);
+    out[8] = __int_as_float(r2.x); out[9] = __int_as_float(r2.y); out[10] = __int_as_float(r2.z); out[11] = __int_as_float(r2.w);
+}
 
 // core/bbox.h:302-325
 DEV bool bbox_ray_intersect(const DBBox &b, const DRay &ray, float &mint, float &maxt) {
@@ -283,13 +296,100 @@ DEV_NOINLINE Hit bvh_intersect(const BvhArgs a, DRay ray) {
     return h;
 }
 
+// Two-level traversal of an instanced scene (shapes/instance.cpp:107-122, librender/shapegroup.cpp): ONE loop with a top / bottom state.
+// A level is walked as a list (`direct`: [lk, lend) are primitive indices) or through its BVH ([cur, end) are node indices, [lk, lend)
+// the pending leaf's entries of leaf_prims), each by the threshold rule on its own primitive count.  An instance primitive met at the
+// scene level takes the lane's ray to group space -- to_object.transform_affine(ray): direction not renormalised, mint / maxt kept, so
+// t means the same in both spaces -- tests it against the group's bbox (the early exit of the group's own kd-tree, kdtree.h:2095-2098)
+// and moves the cursors to the group's range; when that range is exhausted the world ray comes back, with the shrunk maxt, and the
+// scene level goes on behind the instance.  Lanes of a wave inside different instances share the loop body.  The winner is the closest
+// t, ties to the later (scene primitive, group primitive) pair: the order-independent form of the sequential rule at both levels.
+// Walk, group and node records are indexed per lane: vector loads.
+struct InstArgs { const float *nodes; const int32_t *leaf_prims; const DWalkPrim *walk; const DGroup *groups; int32_t top_nodes, top_prims;
+                  const float *lds_nodes; int32_t lds_count; };
 template <bool ShadowRay>
+DEV_NOINLINE Hit inst_intersect(const InstArgs a, DRay wray) {
+    typedef int mts_int4 __attribute__((ext_vector_type(4)));
+    Hit h; h.t = pm_inf(); h.p = f3s(0.f); h.uv.x = h.uv.y = 0.f; h.shape = -1; h.prim = 0;
+    int best_top = -1, best_bot = -1;
+    const MTS_GLOBAL_AS float *nodes = as_global(a.nodes);
+    const MTS_GLOBAL_AS int32_t *leaf_prims = as_global(a.leaf_prims);
+    BvhArgs pa; pa.nodes = a.nodes; pa.leaf_prims = a.leaf_prims; pa.node_count = 0; pa.walk = a.walk; pa.lds_nodes = a.lds_nodes; pa.lds_count = a.lds_count;
+    DRay ray = wray;
+    const bool top_direct = a.top_nodes == 0;
+    int cur = 0, end = a.top_nodes, lk = 0, lend = top_direct ? a.top_prims : 0;
+    bool direct = top_direct;
+    int s_cur = 0, s_lk = 0, s_lend = 0, top_pi = -1, inst = -1;   // the scene level's cursors while the lane is inside instance `inst`
+    for (;;) {
+        if (lk < lend) {                                       // one primitive
+            const int pi = direct ? lk : leaf_prims[lk];
+            ++lk;
+            const MTS_GLOBAL_AS mts_int4 *rec = (const MTS_GLOBAL_AS mts_int4 *) as_global(a.walk + pi);
+            const mts_int4 hd = rec[0];
+            if (hd.x == MTS_SHAPE_INSTANCE) {                  // scene level only (the host refuses nested instancing)
+                const mts_int4 g0 = rec[1], g1 = rec[2], g2 = rec[3];
+                const float f[12] = { __int_as_float(g0.x), __int_as_float(g0.y), __int_as_float(g0.z), __int_as_float(g0.w),
+                                      __int_as_float(g1.x), __int_as_float(g1.y), __int_as_float(g1.z), __int_as_float(g1.w),
+                                      __int_as_float(g2.x), __int_as_float(g2.y), __int_as_float(g2.z), __int_as_float(g2.w) };
+                const MTS_GLOBAL_AS mts_int4 *grp = (const MTS_GLOBAL_AS mts_int4 *) as_global(a.groups + hd.z);
+                const mts_int4 b0 = grp[0], b1 = grp[1], b2 = grp[2];
+                const DRay gray = make_ray(mat_point_affine(f, wray.o), mat_vector(f, wray.d), wray.mint, ray.maxt);
+                DBBox bb;
+                bb.min[0] = __int_as_float(b0.x); bb.min[1] = __int_as_float(b0.y); bb.min[2] = __int_as_float(b0.z);
+                bb.max[0] = __int_as_float(b0.w); bb.max[1] = __int_as_float(b1.x); bb.max[2] = __int_as_float(b1.y);
+                float bmint, bmaxt;
+                bbox_ray_intersect(bb, gray, bmint, bmaxt);
+                if (!(pm_max(gray.mint, bmint) <= pm_min(gray.maxt, bmaxt))) continue;
+                s_cur = cur; s_lk = lk; s_lend = lend; top_pi = pi; inst = hd.y;
+                ray = gray;
+                const int node_first = b1.z, node_count = b1.w, prim_first = b2.x, prim_count = b2.y;
+                if (node_count > 0) { cur = node_first; end = node_first + node_count; lk = lend = 0; direct = false; }
+                else { cur = end = 0; lk = prim_first; lend = prim_first + prim_count; direct = true; }
+                continue;
+            }
+            F2 uv; int shape, index;
+            const float t = prim_intersect_lane(pa, pi, ray, uv, shape, index);
+            const int tp = inst >= 0 ? top_pi : pi, bp = inst >= 0 ? pi : -1;
+            // the tests accept t <= ray.maxt == h.t: equal t goes to the later primitive, scene level first
+            if (t != pm_inf() && (t < h.t || tp > best_top || (tp == best_top && bp > best_bot))) {
+                h.t = t; h.uv = uv; h.shape = shape | ((inst + 1) << MTS_INST_SHAPE_BITS); h.prim = index; best_top = tp; best_bot = bp;
+                if (ShadowRay) return h;
+                ray.maxt = t;
+            }
+        } else if (cur < end) {                                // one node of the level's BVH, as bvh_intersect
+            float nd[8];                                       // the scene's top levels come from LDS when the kernel staged them
+            if (inst < 0 && cur < a.lds_count) { for (int k = 0; k < 8; ++k) nd[k] = a.lds_nodes[8 * cur + k]; }
+            else { for (int k = 0; k < 8; ++k) nd[k] = nodes[8 * cur + k]; }
+            const float t1x = (nd[0] - ray.o.x) * ray.d_rcp.x, t2x = (nd[3] - ray.o.x) * ray.d_rcp.x;
+            const float t1y = (nd[1] - ray.o.y) * ray.d_rcp.y, t2y = (nd[4] - ray.o.y) * ray.d_rcp.y;
+            const float t1z = (nd[2] - ray.o.z) * ray.d_rcp.z, t2z = (nd[5] - ray.o.z) * ray.d_rcp.z;
+            const float tnear = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t1x, t2x), __builtin_fminf(t1y, t2y)), __builtin_fminf(t1z, t2z));
+            const float tfar = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t1x, t2x), __builtin_fmaxf(t1y, t2y)), __builtin_fmaxf(t1z, t2z));
+            const int skip = __float_as_int(nd[6]), link = __float_as_int(nd[7]);
+            if (!(tnear <= tfar && tfar >= ray.mint && tnear <= ray.maxt)) { cur = skip; continue; }
+            if (link < 0) { cur = -link; continue; }
+            lk = link >> 3; lend = lk + (link & 7);
+            cur = skip;
+        } else if (inst >= 0) {                                // the group is done: back to the scene level, behind the instance
+            wray.maxt = ray.maxt; ray = wray;
+            cur = s_cur; end = a.top_nodes; lk = s_lk; lend = s_lend; direct = top_direct; inst = -1;
+        } else break;
+    }
+    return h;
+}
+
+template <bool ShadowRay, bool INST = false>
 DEV Hit ray_intersect_preliminary(const DScene &sc, DRay ray) {
     Hit h; h.t = pm_inf(); h.p = f3s(0.f); h.uv.x = h.uv.y = 0.f; h.shape = -1; h.prim = 0;
     float bmint, bmaxt;
     bbox_ray_intersect(sc.bbox, ray, bmint, bmaxt);
     float mint = pm_max(ray.mint, bmint), maxt = pm_min(ray.maxt, bmaxt);
     if (!(mint <= maxt)) return h;
+    if constexpr (INST) {
+        InstArgs a; a.nodes = sc.bvh_nodes; a.leaf_prims = sc.bvh_prims; a.walk = sc.walk; a.groups = sc.groups; a.top_nodes = sc.bvh_node_count; a.top_prims = sc.prim_count;
+        a.lds_nodes = sc.bvh_lds; a.lds_count = sc.bvh_lds_count;
+        return inst_intersect<ShadowRay>(a, ray);
+    }
 #if !(MTS_TRAITS & MT_NO_BVH)
     if (sc.bvh_node_count > 0) {
         BvhArgs a; a.nodes = sc.bvh_nodes; a.leaf_prims = sc.bvh_prims; a.node_count = sc.bvh_node_count; a.walk = sc.walk; a.lds_nodes = sc.bvh_lds; a.lds_count = sc.bvh_lds_count;
@@ -367,25 +467,42 @@ DEV void hit_point(const DScene &sc, const DShape &s, const DRay &ray, Hit &h, b
 }
 
 // librender/scene_native.inl:23-41
-template <bool TAB = false>
+template <bool TAB = false, bool INST = false>
 DEV Hit ray_intersect(const DScene &sc, const DRay &ray) {
     const bool tab = TAB && geom_table_holds(sc);              // wave-uniform
-    Hit h = ray_intersect_preliminary<false>(sc, ray);
+    Hit h = ray_intersect_preliminary<false, INST>(sc, ray);
     if (hit_valid(h)) {
+      if constexpr (INST) {
+        // instance.cpp:130-133: the interaction from the group-space ray, then p = to_world * p; the instance per lane, ahead of the waterfall
+        const int inst = hit_instance(h);
+        DRay gray = ray;
+        if (inst >= 0) { float O[12]; instance_rows(sc, inst, 32, O); gray = make_ray(mat_point_affine(O, ray.o), mat_vector(O, ray.d), ray.mint, ray.maxt); }
+        WATERFALL_BEGIN(hit_shape<true>(h), su)
+            hit_point<TAB>(sc, cload(sc.shapes + su), gray, h, tab);
+        WATERFALL_END
+        if (inst >= 0) { float W[12]; instance_rows(sc, inst, 0, W); h.p = mat_point_affine(W, h.p); }
+      } else {
         WATERFALL_BEGIN(h.shape, su)
             hit_point<TAB>(sc, cload(sc.shapes + su), ray, h, tab);
         WATERFALL_END
+      }
     }
     return h;
 }
-DEV bool ray_test(const DScene &sc, const DRay &ray) { return hit_valid(ray_intersect_preliminary<true>(sc, ray)); }
+template <bool INST = false>
+DEV bool ray_test(const DScene &sc, const DRay &ray) { return hit_valid(ray_intersect_preliminary<true, INST>(sc, ray)); }
 
 // Rebuild n, shading frame and wi: rectangle.cpp:186-193, mesh.cpp:485-545, sphere.cpp:328-371,
 // interaction.h:153-156,571-596.  `d` is the direction of the ray that produced the hit.
-template <bool TAB = false>
+template <bool TAB = false, bool INST = false>
 DEV void complete_surface(const DScene &sc, const DShape &s, const Hit &h, F3 d, Surf &sf) {
     const bool tab = TAB && geom_table_holds(sc);              // wave-uniform
     F3 dp_du, dp_dv, shn;
+    F3 hp = h.p;
+    // INST: a hit inside an instance: n, the shading normal and dp_du in GROUP space from the member's records, then to world space below.
+    // h.p is a world-space point; the group-space one a sphere needs is what hit_point() made of the parked normal
+    const int inst = INST ? hit_instance(h) : -1;
+    if constexpr (INST) if (inst >= 0 && s.type == MTS_SHAPE_SPHERE) hp = fmadd(f3(h.uv.x, h.uv.y, pm_from_bits((uint32_t) h.prim)), s.radius, f3(s.center));
     if (s.type == MTS_SHAPE_RECTANGLE) {
         sf.n = f3(s.frame_n); shn = sf.n; dp_du = f3(s.frame_s);
     } else if (s.type == MTS_SHAPE_DISK) {                                                    // disk.cpp:190-207, h.uv = prim_uv
@@ -396,7 +513,7 @@ DEV void complete_surface(const DScene &sc, const DShape &s, const Hit &h, F3 d,
     } else if (s.type == MTS_SHAPE_SPHERE) {
         // hit_point() parked the unit normal normalize(ray(t) - center) in (uv.x, uv.y, bits(prim))
         shn = f3(h.uv.x, h.uv.y, pm_from_bits((uint32_t) h.prim));
-        F3 local = mat_point_affine(s.to_object.m, h.p);
+        F3 local = mat_point_affine(s.to_object.m, hp);
         dp_du = mat_vector(s.to_world.m, f3(-local.y, local.x, 0.f)) * (2.f * MTS_PI);
         if (s.flip_normals) shn = -shn;
         sf.n = shn;
@@ -421,15 +538,22 @@ DEV void complete_surface(const DScene &sc, const DShape &s, const Hit &h, F3 d,
             shn = normalize(n0 * b0 + n1 * b1 + n2 * b2);
         } else shn = sf.n;
     }
+    if constexpr (INST) if (inst >= 0) {                       // instance.cpp:134-143: normals through the inverse transpose, dp_du as a vector; the frame is rebuilt below
+        float W[12], IT[12]; instance_rows(sc, inst, 0, W); instance_rows(sc, inst, 16, IT);
+        sf.n = normalize(mat_vector(IT, sf.n));
+        shn = normalize(mat_vector(IT, shn));
+        dp_du = mat_vector(W, dp_du);
+    }
     sf.sh.n = shn;
     sf.sh.s = normalize(fnmadd(shn, dot(shn, dp_du), dp_du));
     sf.sh.t = cross(shn, sf.sh.s);
     sf.wi = to_local(sf.sh, -d);
 }
 
+template <bool INST = false>
 DEV void complete_surface(const DScene &sc, const Hit &h, F3 d, Surf &sf) {
-    WATERFALL_BEGIN(h.shape, su)
-        complete_surface(sc, cload(sc.shapes + su), h, d, sf);
+    WATERFALL_BEGIN(hit_shape<INST>(h), su)
+        complete_surface<false, INST>(sc, cload(sc.shapes + su), h, d, sf);
     WATERFALL_END
 }
 
@@ -1097,6 +1221,7 @@ DEV DirSample emitter_sample_direction(const DScene &sc, int ei, F3 ref_p, F2 sa
     return ds;
 }
 // librender/scene.cpp:168-218
+template <bool INST = false>
 DEV DirSample sample_emitter_direction(const DScene &sc, F3 ref_p, F2 sample, bool test_visibility, Spec &spec, const SpecCtx &cx = SpecCtx()) {
     DirSample ds; ds.pdf = 0.f; ds.dist = 0.f; ds.delta = false; ds.emitter = -1; ds.p = ds.n = ds.d = f3s(0.f);
     if (sc.emitter_count == 0) { spec = spec_s(0.f); return ds; }
@@ -1111,7 +1236,7 @@ DEV DirSample sample_emitter_direction(const DScene &sc, F3 ref_p, F2 sample, bo
     }
     if (test_visibility && ds.pdf != 0.f) {
         DRay ray = make_ray(ref_p, ds.d, MTS_RAY_EPSILON * (1.f + hmax_abs(ref_p)), ds.dist * (1.f - MTS_SHADOW_EPSILON));
-        if (ray_test(sc, ray)) spec = spec_s(0.f);
+        if (ray_test<INST>(sc, ray)) spec = spec_s(0.f);
     }
     return ds;
 }
@@ -1126,7 +1251,8 @@ DEV float pdf_emitter_direction(const DScene &sc, F3 ref_p, const DirSample &ds)
     return value * pm_rcp((float) sc.emitter_count);
 }
 // si.emitter(scene), render/scene.h:243-253 ; emitter->eval: area.cpp:63-71, constant.cpp:41-44, directional.cpp:75-78
-DEV int hit_emitter(const DScene &sc, const Hit &h) { return hit_valid(h) ? sc.shapes[h.shape].emitter : sc.environment; }
+template <bool INST = false>
+DEV int hit_emitter(const DScene &sc, const Hit &h) { return hit_valid(h) ? sc.shapes[hit_shape<INST>(h)].emitter : sc.environment; }
 DEV Spec emitter_eval(const DScene &sc, int ei, float wi_z, const SpecCtx &cx = SpecCtx()) {
     const DEmitter &e = sc.emitters[ei];
     if (e.type == MTS_EMITTER_AREA) return wi_z > 0.f ? EMITTER_COLOR(e, cx, ei) : spec_s(0.f);
@@ -1143,6 +1269,7 @@ DEV float mis_weight(float pdf_a, float pdf_b) { pdf_a *= pdf_a; pdf_b *= pdf_b;
 // read constants from DBsdf; an instantiation with TEX = true makes a local copy of the record at each hit and overwrites the textured
 // fields (HitBsdf), so bsdf_eval / pdf / sample stay what they are and every use at one hit sees one value.
 // si.uv of the reference from what a Hit keeps of the primitive's own parameter
+template <bool INST = false>
 DEV F2 surface_uv(const DScene &sc, const DShape &s, const Hit &h) {
     F2 uv;
     if (s.type == MTS_SHAPE_RECTANGLE) {                                                      // rectangle.cpp:205
@@ -1152,7 +1279,9 @@ DEV F2 surface_uv(const DScene &sc, const DShape &s, const Hit &h) {
         if (v < 0.f) v += 1.f;
         uv.x = pm_sqrt(pm_fma(h.uv.y, h.uv.y, h.uv.x * h.uv.x)); uv.y = v;
     } else if (s.type == MTS_SHAPE_SPHERE) {                                                  // sphere.cpp:362-370; h.p is the re-projected point
-        const F3 local = mat_point_affine(s.to_object.m, h.p);
+        F3 hp = h.p;
+        if constexpr (INST) if (hit_instance(h) >= 0) hp = fmadd(f3(h.uv.x, h.uv.y, pm_from_bits((uint32_t) h.prim)), s.radius, f3(s.center));     // the group-space point (complete_surface)
+        const F3 local = mat_point_affine(s.to_object.m, hp);
         const float temp = asinf(.5f * norm(f3(local.x, local.y, local.z - pm_mulsign(1.f, local.z)))) * 2.f;      // unit_angle_z (core/vector.h)
         const float theta = local.z >= 0.f ? temp : MTS_PI - temp;
         float phi = atan2f(local.y, local.x);
@@ -1266,14 +1395,14 @@ DEV Spec blend_sample(const DScene &sc, const DBsdf &blend, float w, F2 uv, F3 w
     return val;
 }
 // eval + pdf, and sample, of the BSDF record `b` of a hit (a plain one localised already); TEX: a blend resolves through its children
-template <bool TEX, bool U>
+template <int TEX, bool U>
 DEV void hit_bsdf_eval_pdf(const DScene &sc, const DBsdf &b, float w, F2 uv, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) {
-    if constexpr (TEX) if (b.type == MTS_BSDF_BLEND) { blend_eval_pdf<U>(sc, b, w, uv, wi, wo, val, pdf); return; }
+    if constexpr (TEX != 0) if (b.type == MTS_BSDF_BLEND) { blend_eval_pdf<U>(sc, b, w, uv, wi, wo, val, pdf); return; }
     val = bsdf_eval(b, wi, wo, cx, id); pdf = bsdf_pdf(b, wi, wo, cx, id);
 }
-template <bool TEX, bool U>
+template <int TEX, bool U>
 DEV Spec hit_bsdf_sample(const DScene &sc, const DBsdf &b, float w, F2 uv, F3 wi, float sample1, F2 sample2, BSDFSample &bs, const SpecCtx &cx = SpecCtx(), int id = 0) {
-    if constexpr (TEX) if (b.type == MTS_BSDF_BLEND) return blend_sample<U>(sc, b, w, uv, wi, sample1, sample2, bs);
+    if constexpr (TEX != 0) if (b.type == MTS_BSDF_BLEND) return blend_sample<U>(sc, b, w, uv, wi, sample1, sample2, bs);
     return bsdf_sample(b, wi, sample1, sample2, bs, cx, id);
 }
 // ---- twosided (bsdfs/twosided.cpp:94-181; DBsdf in dscene.h says where the record keeps its children).  TEX instantiations only, as
@@ -1298,8 +1427,11 @@ DEV void zero_bsdf_sample(BSDFSample &bs) { bs.wo = f3s(0.f); bs.pdf = 0.f; bs.e
 // `local` is then the child's record, its flags included (the child is smooth whenever the adapter's union is, for the children this
 // backend nests, so the callers' NEE test reads the same); a blend's weight and the hit's uv are evaluated once, in at(), too, and
 // serve eval, pdf and sample of that hit, as `local` does for colours.
-template <bool TEX> struct HitBsdf;
-template <> struct HitBsdf<false> {
+// TEX: TEX_NONE the plain instantiations, TEX_ON the textured ones, TEX_INST the textured ones of an instanced scene -- two-level
+// traversal, the instance of a hit in Hit::shape, a member's surface carried to world space (INST = true in the functions above)
+enum { TEX_NONE = 0, TEX_ON = 1, TEX_INST = 2 };
+template <int TEX> struct HitBsdf;
+template <> struct HitBsdf<TEX_NONE> {
     DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &, const Hit &, F3) { return sc.bsdfs[bsdf_id]; }
     DEV void eval_pdf(const DScene &sc, const DBsdf &b, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) const {
         F2 none; none.x = none.y = 0.f; hit_bsdf_eval_pdf<false, false>(sc, b, 0.f, none, wi, wo, val, pdf, cx, id);
@@ -1308,14 +1440,14 @@ template <> struct HitBsdf<false> {
         F2 none; none.x = none.y = 0.f; return hit_bsdf_sample<false, false>(sc, b, 0.f, none, wi, sample1, sample2, bs, cx, id);
     }
 };
-template <> struct HitBsdf<true> {
+template <bool INST> struct HitBsdfTex {
     DBsdf local; F2 uv; float w; bool back, none;
     DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &shape, const Hit &si, F3 wi) {
         const BsdfSide side = twosided_side(sc, bsdf_id, wi);
         bsdf_id = side.id; back = side.back; none = side.none;
         local = sc.bsdfs[bsdf_id]; uv.x = uv.y = 0.f; w = 0.f;
-        if (local.type == MTS_BSDF_BLEND) { uv = surface_uv(sc, shape, si); w = blend_weight(sc, bsdf_id, local, uv); }
-        else bsdf_apply_textures(sc, bsdf_id, local, [&]() { return surface_uv(sc, shape, si); });
+        if (local.type == MTS_BSDF_BLEND) { uv = surface_uv<INST>(sc, shape, si); w = blend_weight(sc, bsdf_id, local, uv); }
+        else bsdf_apply_textures(sc, bsdf_id, local, [&]() { return surface_uv<INST>(sc, shape, si); });
         return local;
     }
     DEV void eval_pdf(const DScene &sc, const DBsdf &b, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) const {
@@ -1330,18 +1462,21 @@ template <> struct HitBsdf<true> {
         return val;
     }
 };
+template <> struct HitBsdf<TEX_ON> : HitBsdfTex<false> { };
+template <> struct HitBsdf<TEX_INST> : HitBsdfTex<true> { };
 
 // Geometric normal of a hit without the full shading frame (only needed for medium transitions)
-template <bool TAB = false>
+template <bool TAB = false, bool INST = false>
 DEV F3 hit_geo_normal(const DScene &sc, const DShape &s, const Hit &h) {
-    if (s.type == MTS_SHAPE_RECTANGLE || s.type == MTS_SHAPE_DISK) return f3(s.frame_n);
-    Surf sf; complete_surface<TAB>(sc, s, h, f3(0.f, 0.f, 1.f), sf);
+    if ((s.type == MTS_SHAPE_RECTANGLE || s.type == MTS_SHAPE_DISK) && (!INST || hit_instance(h) < 0)) return f3(s.frame_n);
+    Surf sf; complete_surface<TAB, INST>(sc, s, h, f3(0.f, 0.f, 1.f), sf);
     return sf.n;
 }
+template <bool INST = false>
 DEV F3 hit_geo_normal(const DScene &sc, const Hit &h) {
     F3 n = f3s(0.f);
-    WATERFALL_BEGIN(h.shape, su)
-        n = hit_geo_normal(sc, cload(sc.shapes + su), h);
+    WATERFALL_BEGIN(hit_shape<INST>(h), su)
+        n = hit_geo_normal<false, INST>(sc, cload(sc.shapes + su), h);
     WATERFALL_END
     return n;
 }
@@ -1354,10 +1489,10 @@ DEV Spec transmittance_exp(float t, Spec combined) { return spec4(pm_exp(-t * co
 
 // ---------------------------------------------------------------- volpath
 // integrators/volpath.cpp:261-367: NEE with ratio tracking through media and null surfaces
-template <bool COUNT>
+template <bool COUNT, bool INST = false>
 DEV Spec volpath_sample_emitter(const DScene &sc, F3 ref_p, bool is_medium_interaction, Pcg32 &rng, int medium, uint32_t channel, DirSample &ds, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     Spec transmittance = spec_s(1.f), emitter_val;
-    ds = sample_emitter_direction(sc, ref_p, rng.next_2d(), false, emitter_val, cx);
+    ds = sample_emitter_direction<INST>(sc, ref_p, rng.next_2d(), false, emitter_val, cx);
     if (ds.pdf == 0.f) return spec_s(0.f);
     bool active = true;
     DRay ray = spawn_ray(ref_p, ds.d);
@@ -1376,7 +1511,7 @@ DEV Spec volpath_sample_emitter(const DScene &sc, F3 ref_p, bool is_medium_inter
             const DMedium &m = sc.media[medium];
             MediumSample mi = medium_sample_interaction<COUNT>(sc, medium, ray, rng.next_1d(), channel, cnt, cx);
             if (m.is_homogeneous && ms_valid(mi)) ray.maxt = pm_min(mi.t, remaining_dist);
-            if (needs_intersection) si = ray_intersect(sc, ray);
+            if (needs_intersection) si = ray_intersect<false, INST>(sc, ray);
             if (si.t < mi.t) mi.t = pm_inf();
             needs_intersection = false;
             bool is_spectral = m.has_spectral_extinction != 0, not_spectral = !is_spectral;
@@ -1399,26 +1534,26 @@ DEV Spec volpath_sample_emitter(const DScene &sc, F3 ref_p, bool is_medium_inter
             }
         }
         bool intersect = active_surface && needs_intersection;
-        if (intersect) si = ray_intersect(sc, ray);
+        if (intersect) si = ray_intersect<false, INST>(sc, ray);
         needs_intersection = needs_intersection && !intersect;
         active_surface = active_surface || escaped_medium;
         if (active_surface) total_dist += si.t;
         active_surface = active_surface && hit_valid(si) && active && !active_medium;
         if (active_surface) {
-            const DShape &s = sc.shapes[si.shape];
+            const DShape &s = sc.shapes[hit_shape<INST>(si)];
             transmittance = transmittance * null_transmission(sc, s);
             ray = spawn_ray(si.p, ray.d);
         }
         ray.maxt = remaining_dist;
         needs_intersection = needs_intersection || active_surface;
         active = active && (active_medium || active_surface) && any_nonzero(transmittance);
-        if (active_surface && sc.shapes[si.shape].is_medium_transition) medium = target_medium(sc.shapes[si.shape], hit_geo_normal(sc, si), ray.d);
+        if (active_surface && sc.shapes[hit_shape<INST>(si)].is_medium_transition) medium = target_medium(sc.shapes[hit_shape<INST>(si)], hit_geo_normal<INST>(sc, si), ray.d);
     }
     return transmittance * emitter_val;
 }
 
 // integrators/volpath.cpp:370-465
-template <bool COUNT>
+template <bool COUNT, bool INST = false>
 DEV Spec volpath_evaluate_direct_light(const DScene &sc, F3 ref_p, Pcg32 &rng, int medium, DRay ray, Hit si, uint32_t channel, bool active, float &emitter_pdf, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     Spec emitter_val = spec_s(0.f), transmittance = spec_s(1.f);
     bool needs_intersection = false;
@@ -1430,7 +1565,7 @@ DEV Spec volpath_evaluate_direct_light(const DScene &sc, F3 ref_p, Pcg32 &rng, i
             const DMedium &m = sc.media[medium];
             MediumSample mi = medium_sample_interaction<COUNT>(sc, medium, ray, rng.next_1d(), channel, cnt, cx);
             if (m.is_homogeneous && ms_valid(mi)) ray.maxt = mi.t;
-            if (needs_intersection) si = ray_intersect(sc, ray);
+            if (needs_intersection) si = ray_intersect<false, INST>(sc, ray);
             if (si.t < mi.t) mi.t = pm_inf();
             bool is_spectral = m.has_spectral_extinction != 0, not_spectral = !is_spectral;
             if (is_spectral) {
@@ -1450,13 +1585,13 @@ DEV Spec volpath_evaluate_direct_light(const DScene &sc, F3 ref_p, Pcg32 &rng, i
             }
         }
         bool intersect = active_surface && needs_intersection;
-        if (intersect) si = ray_intersect(sc, ray);
+        if (intersect) si = ray_intersect<false, INST>(sc, ray);
         needs_intersection = needs_intersection && !intersect;
         active_surface = active_surface || escaped_medium;
-        int emitter = active_surface ? hit_emitter(sc, si) : -1;
+        int emitter = active_surface ? hit_emitter<INST>(sc, si) : -1;
         if (emitter >= 0) {
             Surf sf; sf.wi = -ray.d; sf.sh.n = f3s(0.f);
-            if (hit_valid(si)) complete_surface(sc, si, ray.d, sf);
+            if (hit_valid(si)) complete_surface<INST>(sc, si, ray.d, sf);
             DirSample ds;                                                                    // render/records.h:168-174
             ds.p = si.p; ds.n = sf.sh.n; ds.d = si.p - ref_p; ds.dist = norm(ds.d); ds.d = ds.d / ds.dist;
             if (!hit_valid(si)) ds.d = -sf.wi;
@@ -1467,19 +1602,19 @@ DEV Spec volpath_evaluate_direct_light(const DScene &sc, F3 ref_p, Pcg32 &rng, i
         }
         active_surface = active_surface && hit_valid(si) && !active_medium;
         if (active_surface) {
-            const DShape &s = sc.shapes[si.shape];
+            const DShape &s = sc.shapes[hit_shape<INST>(si)];
             transmittance = transmittance * null_transmission(sc, s);
             ray = spawn_ray(si.p, ray.d);
         }
         needs_intersection = needs_intersection || active_surface;
         active = active && (active_medium || active_surface) && any_nonzero(transmittance);
-        if (active_surface && sc.shapes[si.shape].is_medium_transition) medium = target_medium(sc.shapes[si.shape], hit_geo_normal(sc, si), ray.d);
+        if (active_surface && sc.shapes[hit_shape<INST>(si)].is_medium_transition) medium = target_medium(sc.shapes[hit_shape<INST>(si)], hit_geo_normal<INST>(sc, si), ray.d);
     }
     return transmittance * emitter_val;
 }
 
 // integrators/volpath.cpp:38-257
-template <bool COUNT, bool TEX = false>
+template <bool COUNT, int TEX = TEX_NONE>
 DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool &valid_out, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     const uint32_t max_depth = (uint32_t) sc.integrator.max_depth, rr_depth = (uint32_t) sc.integrator.rr_depth;
     const bool hide_emitters = sc.integrator.hide_emitters != 0;
@@ -1513,7 +1648,7 @@ DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool
             is_spectral = m.has_spectral_extinction != 0; not_spectral = !is_spectral;
             mi = medium_sample_interaction<COUNT>(sc, medium, ray, rng.next_1d(), channel, cnt, cx);
             if (m.is_homogeneous && ms_valid(mi)) ray.maxt = mi.t;
-            if (needs_intersection) si = ray_intersect(sc, ray);
+            if (needs_intersection) si = ray_intersect<false, TEX == TEX_INST>(sc, ray);
             needs_intersection = false;
             if (si.t < mi.t) mi.t = pm_inf();
             if (is_spectral) {
@@ -1545,7 +1680,7 @@ DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool
             F3 wi = -ray.d;
             if (sample_emitters) {
                 DirSample ds;
-                Spec emitted = volpath_sample_emitter<COUNT>(sc, mi.p, true, rng, medium, channel, ds, cnt, cx);
+                Spec emitted = volpath_sample_emitter<COUNT, TEX == TEX_INST>(sc, mi.p, true, rng, medium, channel, ds, cnt, cx);
                 float phase_val = phase_eval(sc, m.phase, wi, mi.p, ds.d, cx);
                 result = result + throughput * phase_val * emitted;
             }
@@ -1556,22 +1691,22 @@ DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool
         }
         active_surface = active_surface || escaped_medium;
         bool intersect = active_surface && needs_intersection;
-        if (intersect) si = ray_intersect(sc, ray);
+        if (intersect) si = ray_intersect<false, TEX == TEX_INST>(sc, ray);
         Surf sf; sf.wi = -ray.d;
-        if (active_surface && hit_valid(si)) complete_surface(sc, si, ray.d, sf);
+        if (active_surface && hit_valid(si)) complete_surface<TEX == TEX_INST>(sc, si, ray.d, sf);
         if (active_surface) {
-            int emitter = hit_emitter(sc, si);
+            int emitter = hit_emitter<TEX == TEX_INST>(sc, si);
             if (specular_chain && emitter >= 0) result = result + throughput * emitter_eval(sc, emitter, sf.wi.z, cx);
         }
         active_surface = active_surface && hit_valid(si);
         if (active_surface) {
-            const DShape &shape = sc.shapes[si.shape];
+            const DShape &shape = sc.shapes[hit_shape<TEX == TEX_INST>(si)];
             HitBsdf<TEX> hit_bsdf;
             const DBsdf &bsdf = hit_bsdf.at(sc, shape.bsdf, shape, si, sf.wi);
             bool active_e = (bsdf.flags & F_Smooth) != 0 && (depth + 1 < max_depth);
             if (active_e) {
                 DirSample ds;
-                Spec emitted = volpath_sample_emitter<COUNT>(sc, si.p, false, rng, medium, channel, ds, cnt, cx);
+                Spec emitted = volpath_sample_emitter<COUNT, TEX == TEX_INST>(sc, si.p, false, rng, medium, channel, ds, cnt, cx);
                 F3 wo = to_local(sf.sh, ds.d);
                 Spec bsdf_val; float bpdf;
                 hit_bsdf.eval_pdf(sc, bsdf, sf.wi, wo, bsdf_val, bpdf, cx, shape.bsdf);
@@ -1592,10 +1727,10 @@ DEV Spec volpath_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool
             bool add_emitter = !(bs.sampled_type & F_Delta) && any_nonzero(throughput) && (depth < max_depth);
             bool intersect2 = needs_intersection && add_emitter;
             Hit si_new = si;
-            if (intersect2) si_new = ray_intersect(sc, ray);
+            if (intersect2) si_new = ray_intersect<false, TEX == TEX_INST>(sc, ray);
             needs_intersection = needs_intersection && !intersect2;
             float emitter_pdf;
-            Spec emitted = volpath_evaluate_direct_light<COUNT>(sc, si.p, rng, medium, ray, si_new, channel, add_emitter, emitter_pdf, cnt, cx);
+            Spec emitted = volpath_evaluate_direct_light<COUNT, TEX == TEX_INST>(sc, si.p, rng, medium, ray, si_new, channel, add_emitter, emitter_pdf, cnt, cx);
             if (add_emitter && emitter_pdf != 0) result = result + mis_weight(bs.pdf, emitter_pdf) * throughput * emitted;
             if (shape.is_medium_transition) medium = target_medium(shape, sf.n, ray.d);
             if (intersect2) si = si_new;
@@ -1695,12 +1830,12 @@ DEV Spec mis_weight_w(const MisWeights<SPEC> &a, const MisWeights<SPEC> &b) {   
 }
 
 // volpathmis.cpp:330-445
-template <bool COUNT, bool SPEC>
+template <bool COUNT, bool SPEC, bool INST = false>
 DEV Spec volpathmis_sample_emitter(const DScene &sc, F3 ref_p, bool is_medium_interaction, Pcg32 &rng, int medium, const MisWeights<SPEC> &p_over_f,
                                           uint32_t channel, MisWeights<SPEC> &nee_out, MisWeights<SPEC> &uni_out, DirSample &ds, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     MisWeights<SPEC> p_over_f_nee = p_over_f, p_over_f_uni = p_over_f;
     Spec emitter_sample_weight;
-    ds = sample_emitter_direction(sc, ref_p, rng.next_2d(), false, emitter_sample_weight, cx);
+    ds = sample_emitter_direction<INST>(sc, ref_p, rng.next_2d(), false, emitter_sample_weight, cx);
     Spec emitter_val = emitter_sample_weight * ds.pdf;
     if (ds.pdf == 0.f) emitter_val = spec_s(0.f);
     bool active = ds.pdf != 0.f;
@@ -1722,7 +1857,7 @@ DEV Spec volpathmis_sample_emitter(const DScene &sc, F3 ref_p, bool is_medium_in
             const DMedium &m = sc.media[medium];
             MediumSample mi = medium_sample_interaction<COUNT>(sc, medium, ray, rng.next_1d(), channel, cnt, cx);
             if (m.is_homogeneous && ms_valid(mi)) ray.maxt = pm_min(mi.t, remaining_dist);
-            if (needs_intersection) si = ray_intersect(sc, ray);
+            if (needs_intersection) si = ray_intersect<false, INST>(sc, ray);
             if (si.t < mi.t) mi.t = pm_inf();
             needs_intersection = false;
             bool is_spectral = m.has_spectral_extinction != 0, not_spectral = !is_spectral;
@@ -1752,12 +1887,12 @@ DEV Spec volpathmis_sample_emitter(const DScene &sc, F3 ref_p, bool is_medium_in
             }
         }
         bool intersect = active_surface && needs_intersection;
-        if (intersect) si = ray_intersect(sc, ray);
+        if (intersect) si = ray_intersect<false, INST>(sc, ray);
         active_surface = active_surface || escaped_medium;
         if (active_surface) total_dist += si.t;
         active_surface = active_surface && hit_valid(si) && active && !active_medium;
         if (active_surface) {
-            Spec bsdf_val = null_transmission(sc, sc.shapes[si.shape]);
+            Spec bsdf_val = null_transmission(sc, sc.shapes[hit_shape<INST>(si)]);
             update_weights(p_over_f_nee, 1.0f, bsdf_val, channel, true);
             update_weights(p_over_f_uni, 1.0f, bsdf_val, channel, true);
         }
@@ -1766,14 +1901,14 @@ DEV Spec volpathmis_sample_emitter(const DScene &sc, F3 ref_p, bool is_medium_in
         needs_intersection = needs_intersection || active_surface;
         if (SPEC) active = active && (active_medium || active_surface) && any_nonzero(mis_weight_w(p_over_f_uni));
         else active = active && (active_medium || active_surface) && (any_nonzero(p_over_f_uni.r[0]) || any_nonzero(p_over_f_nee.r[0]));
-        if (active_surface && sc.shapes[si.shape].is_medium_transition) medium = target_medium(sc.shapes[si.shape], hit_geo_normal(sc, si), ray.d);
+        if (active_surface && sc.shapes[hit_shape<INST>(si)].is_medium_transition) medium = target_medium(sc.shapes[hit_shape<INST>(si)], hit_geo_normal<INST>(sc, si), ray.d);
     }
     nee_out = p_over_f_nee; uni_out = p_over_f_uni;
     return emitter_val;
 }
 
 // volpathmis.cpp:86-328
-template <bool COUNT, bool SPEC, bool TEX = false>
+template <bool COUNT, bool SPEC, int TEX = TEX_NONE>
 DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool &valid_out, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     const uint32_t max_depth = (uint32_t) sc.integrator.max_depth, rr_depth = (uint32_t) sc.integrator.rr_depth;
     const bool hide_emitters = sc.integrator.hide_emitters != 0;
@@ -1812,7 +1947,7 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
             const DMedium &m = sc.media[medium];
             mi = medium_sample_interaction<COUNT>(sc, medium, ray, rng.next_1d(), channel, cnt, cx);
             if (m.is_homogeneous && ms_valid(mi)) ray.maxt = mi.t;
-            if (needs_intersection) si = ray_intersect(sc, ray);
+            if (needs_intersection) si = ray_intersect<false, TEX == TEX_INST>(sc, ray);
             needs_intersection = false;
             if (si.t < mi.t) mi.t = pm_inf();
             if (is_spectral) {
@@ -1855,7 +1990,7 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
                 F3 wi = -ray.d;
                 if (sample_emitters) {
                     MisWeights<SPEC> nee_end, uni_end; DirSample ds;
-                    Spec emitted = volpathmis_sample_emitter<COUNT, SPEC>(sc, mi.p, true, rng, medium, p_over_f, channel, nee_end, uni_end, ds, cnt, cx);
+                    Spec emitted = volpathmis_sample_emitter<COUNT, SPEC, TEX == TEX_INST>(sc, mi.p, true, rng, medium, p_over_f, channel, nee_end, uni_end, ds, cnt, cx);
                     float phase_val = phase_eval(sc, m.phase, wi, mi.p, ds.d, cx);
                     update_weights(nee_end, 1.0f, phase_val, channel, true);
                     update_weights(uni_end, ds.delta ? 0.f : phase_val, phase_val, channel, true);
@@ -1873,13 +2008,13 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
         }
         active_surface = active_surface || escaped_medium;
         bool intersect = active_surface && needs_intersection;
-        if (intersect) si = ray_intersect(sc, ray);
+        if (intersect) si = ray_intersect<false, TEX == TEX_INST>(sc, ray);
         Surf sf; sf.wi = -ray.d; sf.sh.n = f3s(0.f);
-        if (active_surface && hit_valid(si)) complete_surface(sc, si, ray.d, sf);
+        if (active_surface && hit_valid(si)) complete_surface<TEX == TEX_INST>(sc, si, ray.d, sf);
         if (active_surface) {
             bool ray_from_camera = depth == 0;
             bool count_direct = ray_from_camera || specular_chain;
-            int emitter = hit_emitter(sc, si);
+            int emitter = hit_emitter<TEX == TEX_INST>(sc, si);
             bool active_e = emitter >= 0 && !(depth == 0 && hide_emitters);
             if (active_e) {
                 if (!count_direct) {
@@ -1897,13 +2032,13 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
         }
         active_surface = active_surface && hit_valid(si);
         if (active_surface) {
-            const DShape &shape = sc.shapes[si.shape];
+            const DShape &shape = sc.shapes[hit_shape<TEX == TEX_INST>(si)];
             HitBsdf<TEX> hit_bsdf;
             const DBsdf &bsdf = hit_bsdf.at(sc, shape.bsdf, shape, si, sf.wi);
             bool active_e = (bsdf.flags & F_Smooth) != 0 && (depth + 1 < max_depth);
             if (active_e) {
                 MisWeights<SPEC> nee_end, uni_end; DirSample ds;
-                Spec emitted = volpathmis_sample_emitter<COUNT, SPEC>(sc, si.p, false, rng, medium, p_over_f, channel, nee_end, uni_end, ds, cnt, cx);
+                Spec emitted = volpathmis_sample_emitter<COUNT, SPEC, TEX == TEX_INST>(sc, si.p, false, rng, medium, p_over_f, channel, nee_end, uni_end, ds, cnt, cx);
                 F3 wo_local = to_local(sf.sh, ds.d);
                 Spec bsdf_val; float bpdf;
                 hit_bsdf.eval_pdf(sc, bsdf, sf.wi, wo_local, bsdf_val, bpdf, cx, shape.bsdf);
@@ -1937,19 +2072,19 @@ DEV Spec volpathmis_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, b
 
 // ---------------------------------------------------------------- path
 // integrators/path.cpp:100-211
-template <bool COUNT, bool TEX = false>
+template <bool COUNT, int TEX = TEX_NONE>
 DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     const int max_depth = sc.integrator.max_depth, rr_depth = sc.integrator.rr_depth;
     float eta = 1.f, emission_weight = 1.f;
     Spec throughput = spec_s(1.f), result = spec_s(0.f);
     bool active = true;
-    Hit si = ray_intersect(sc, ray);
+    Hit si = ray_intersect<false, TEX == TEX_INST>(sc, ray);
     bool valid_ray = hit_valid(si);
-    int emitter = hit_emitter(sc, si);
+    int emitter = hit_emitter<TEX == TEX_INST>(sc, si);
     for (int depth = 1;; ++depth) {
         if (COUNT) cnt.n_iter++;
         Surf sf; sf.wi = -ray.d;
-        if (hit_valid(si)) complete_surface(sc, si, ray.d, sf);
+        if (hit_valid(si)) complete_surface<TEX == TEX_INST>(sc, si, ray.d, sf);
         if (emitter >= 0 && active) result = result + emission_weight * throughput * emitter_eval(sc, emitter, sf.wi.z, cx);
         active = active && hit_valid(si);
         if (depth > rr_depth) {
@@ -1958,13 +2093,13 @@ DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Co
             throughput = throughput * pm_rcp(q);
         }
         if ((uint32_t) depth >= (uint32_t) max_depth || !active) break;
-        const int bsdf_id = sc.shapes[si.shape].bsdf;
+        const int bsdf_id = sc.shapes[hit_shape<TEX == TEX_INST>(si)].bsdf;
         HitBsdf<TEX> hit_bsdf;
-        const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[si.shape], si, sf.wi);
+        const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[hit_shape<TEX == TEX_INST>(si)], si, sf.wi);
         bool active_e = (bsdf.flags & F_Smooth) != 0;
         if (active_e) {
             Spec emitter_val;
-            DirSample ds = sample_emitter_direction(sc, si.p, rng.next_2d(), true, emitter_val, cx);
+            DirSample ds = sample_emitter_direction<TEX == TEX_INST>(sc, si.p, rng.next_2d(), true, emitter_val, cx);
             active_e = active_e && ds.pdf != 0.f;
             F3 wo = to_local(sf.sh, ds.d);
             Spec bsdf_val; float bpdf;
@@ -1981,11 +2116,11 @@ DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Co
         eta *= bs.eta;
         F3 ref_p = si.p;
         ray = spawn_ray(si.p, to_world(sf.sh, bs.wo));
-        Hit si_bsdf = ray_intersect(sc, ray);
-        emitter = hit_emitter(sc, si_bsdf);
+        Hit si_bsdf = ray_intersect<false, TEX == TEX_INST>(sc, ray);
+        emitter = hit_emitter<TEX == TEX_INST>(sc, si_bsdf);
         if (emitter >= 0) {
             Surf sb; sb.wi = -ray.d; sb.sh.n = f3s(0.f);
-            if (hit_valid(si_bsdf)) complete_surface(sc, si_bsdf, ray.d, sb);
+            if (hit_valid(si_bsdf)) complete_surface<TEX == TEX_INST>(sc, si_bsdf, ray.d, sb);
             DirSample ds;                                                                    // render/records.h:168-174
             ds.p = si_bsdf.p; ds.n = sb.sh.n; ds.d = si_bsdf.p - ref_p; ds.dist = norm(ds.d); ds.d = ds.d / ds.dist;
             if (!hit_valid(si_bsdf)) ds.d = -sb.wi;
@@ -2004,7 +2139,7 @@ DEV Spec path_sample(const DScene &sc, Pcg32 &rng, DRay ray, bool &valid_out, Co
 // (NI_*: one render-kernel instantiation each, so that `path` does not carry the registers of the volumetric integrators)
 enum { NI_ANY = -1, NI_PATH = 0, NI_VOLPATH = 1, NI_VOLPATHMIS = 2, NI_VOLPATHMIS_NOSPEC = 3 };
 // TEX: the BSDF parameters of a hit go through their textures (HitBsdf)
-template <bool COUNT, int INTEG = NI_ANY, bool TEX = false>
+template <bool COUNT, int INTEG = NI_ANY, int TEX = TEX_NONE>
 DEV Spec integrator_sample(const DScene &sc, Pcg32 &rng, DRay ray, int medium, bool &valid, Counters &cnt, const SpecCtx &cx = SpecCtx()) {
     if (INTEG == NI_PATH) return path_sample<COUNT, TEX>(sc, rng, ray, valid, cnt, cx);
     if (INTEG == NI_VOLPATH) return volpath_sample<COUNT, TEX>(sc, rng, ray, medium, valid, cnt, cx);

@@ -37,7 +37,7 @@ DEV void flush_counters(unsigned long long *counters, const Counters &cnt) {
 // sample that falls on the left/top pixel edge (u == 0) goes to the neighbour through an atomic.
 // MOMENT (rgb / mono general unit): the `moment` wrapper's tail, eleven accumulators (splat_moment_t, volpath_flat.h)
 // TEX (rgb / mono general unit): BSDF parameters through their textures (integrator_dev.h: HitBsdf)
-template <bool COUNT, int INTEG, bool MOMENT = false, bool TEX = false>
+template <bool COUNT, int INTEG, bool MOMENT = false, int TEX = TEX_NONE>
 __device__ __forceinline__ void render_sample(const DScene &sc, Pcg32 &rng, const DBlock &blk, uint32_t lx, uint32_t ly,
                                               float *__restrict__ film, float acc[5], Counters &cnt) {
     const DSensor &se = sc.sensor;
@@ -90,7 +90,7 @@ __device__ __forceinline__ void render_sample(const DScene &sc, Pcg32 &rng, cons
 // same order, and sums its samples in the same order: bit-identical to the nested formulation and to the CPU restatement.
 // Written over the variant's spectrum type: in the spectral build a sample also draws its four wavelengths (from the sensor's response
 // function when there is one), carries the bins' AOV values and reaches the film through spectrum_to_xyz, as render_sample above.
-template <bool COUNT, bool MOMENT = false, bool TEX = false>
+template <bool COUNT, bool MOMENT = false, int TEX = TEX_NONE>
 __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, const DBlock &blk, uint32_t lx, uint32_t ly, uint32_t sample_count,
                                                 float *__restrict__ film, float acc[5], Counters &cnt, const uint32_t *stop_flag) {
     const DSensor &se = sc.sensor;
@@ -136,12 +136,12 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
     begin_sample();
     for (uint32_t it = 0;; ++it) {
         if ((it & 1023u) == 1023u && stop_requested(stop_flag)) break;      // should_stop(), integrator.h:143-146
-        const Hit si = ray_intersect(sc, ray);
-        const int emitter = hit_emitter(sc, si);
+        const Hit si = ray_intersect<false, TEX == TEX_INST>(sc, ray);
+        const int emitter = hit_emitter<TEX == TEX_INST>(sc, si);
         if (depth == 0) valid_ray = hit_valid(si);               // path.cpp:113-115
         else if (emitter >= 0) {                                 // :193-205: MIS weight of the emitter the BSDF sample found
             Surf sb; sb.wi = -ray.d; sb.sh.n = f3s(0.f);
-            if (hit_valid(si)) complete_surface(sc, si, ray.d, sb);
+            if (hit_valid(si)) complete_surface<TEX == TEX_INST>(sc, si, ray.d, sb);
             DirSample ds;                                        // render/records.h:168-174
             ds.p = si.p; ds.n = sb.sh.n; ds.d = si.p - ref_p; ds.dist = norm(ds.d); ds.d = ds.d / ds.dist;
             if (!hit_valid(si)) ds.d = -sb.wi;
@@ -153,7 +153,7 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
         // ---- one iteration of the loop of path.cpp:121-207
         if (COUNT) cnt.n_iter++;
         Surf sf; sf.wi = -ray.d;
-        if (hit_valid(si)) complete_surface(sc, si, ray.d, sf);
+        if (hit_valid(si)) complete_surface<TEX == TEX_INST>(sc, si, ray.d, sf);
         if (emitter >= 0) result = result + emission_weight * throughput * emitter_eval(sc, emitter, sf.wi.z MTS_CX);
         bool active = hit_valid(si);
         if (depth > rr_depth) {
@@ -163,13 +163,13 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
         }
         bool ended = (uint32_t) depth >= (uint32_t) max_depth || !active;
         if (!ended) {
-            const int bsdf_id = sc.shapes[si.shape].bsdf;
+            const int bsdf_id = sc.shapes[hit_shape<TEX == TEX_INST>(si)].bsdf;
             HitBsdf<TEX> hit_bsdf;
-            const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[si.shape], si, sf.wi);
+            const DBsdf &bsdf = hit_bsdf.at(sc, bsdf_id, sc.shapes[hit_shape<TEX == TEX_INST>(si)], si, sf.wi);
             bool active_e = (bsdf.flags & F_Smooth) != 0;
             if (active_e) {
                 Spec emitter_val;
-                DirSample ds = sample_emitter_direction(sc, si.p, rng.next_2d(), true, emitter_val MTS_CX);
+                DirSample ds = sample_emitter_direction<TEX == TEX_INST>(sc, si.p, rng.next_2d(), true, emitter_val MTS_CX);
                 active_e = active_e && ds.pdf != 0.f;
                 F3 wo = to_local(sf.sh, ds.d);
                 Spec bsdf_val; float bpdf;
@@ -442,6 +442,91 @@ __global__ void __launch_bounds__(256) intersect_kernel(DScene sc, int32_t n, co
     out_n[3 * i] = nn.x; out_n[3 * i + 1] = nn.y; out_n[3 * i + 2] = nn.z;
 }
 
+// ---- instanced scenes (MTS_SHAPE_INSTANCE; shapes/shapegroup.cpp, shapes/instance.cpp): the kernels of textured scenes above with TEX = TEX_INST -- the two-level
+// traversal (integrator_dev.h: inst_intersect), the instance of a hit in the upper bits of Hit::shape, a member's surface carried from group space to world space
+// (complete_surface) -- under names of their own: the plain, MOMENT and TEX instantiations stay what they are, and only these pay for the traversal's registers.
+// launch_render maps a row of the kernel table to them as to the TEX kernels (kv::textured_variant); mts_stats.textured reports 2.
+// The flat loop: two waves per SIMD is what inst_intersect's registers leave it.
+template <bool COUNT, bool FLAT>
+__global__ void __launch_bounds__(256, FLAT ? 2 : MTS_NESTED_WAVES) render_kernel_inst(DScene sc, const DBlock *__restrict__ blocks, uint32_t n_blocks, uint32_t block_size,
+                                                     uint32_t sample_count, float *__restrict__ film_base, unsigned long long *__restrict__ counters,
+                                                     const uint32_t *__restrict__ stop_flag) {
+    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];             // as render_kernel: the SCENE level's top nodes (bvh_node_count counts that level alone)
+    {
+        const int staged = min(sc.bvh_node_count, MTS_BVH_LDS_NODES);
+        for (int k = (int) threadIdx.x; k < staged * 8; k += (int) blockDim.x) bvh_top[k] = sc.bvh_nodes[k];
+        pm_tables_to_lds(threadIdx.x);
+        __syncthreads();
+        sc.bvh_lds = bvh_top; sc.bvh_lds_count = staged;
+    }
+    const uint32_t ppb = block_size * block_size;
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t b = gid / ppb, i = gid - b * ppb;
+    if (b >= n_blocks) return;
+    const DBlock blk = blocks[b];
+    float *__restrict__ film = film_base + (((size_t) blk.film_off_hi << 32) | blk.film_off_lo);
+    const uint32_t lx = compact_bits(i), ly = compact_bits(i >> 1);
+    if (lx >= (uint32_t) blk.sx || ly >= (uint32_t) blk.sy) return;
+    Pcg32 rng;
+    rng.seed(sc.sensor.seed + (uint64_t) blk.id * ppb + i, PCG32_DEFAULT_STREAM);
+    Counters cnt = {};
+    float acc[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };
+    if (FLAT) path_pixel_flat<COUNT, false, TEX_INST>(sc, rng, blk, lx, ly, sample_count, film, acc, cnt, stop_flag);
+    else
+    for (uint32_t j = 0; j < sample_count; ++j) {
+        if ((j & 63u) == 63u && stop_requested(stop_flag)) break;
+        if (sc.sensor.wavefront) seed_wavefront_sample(rng, sc.sensor, blk, lx, ly, j);
+        render_sample<COUNT, NI_ANY, false, TEX_INST>(sc, rng, blk, lx, ly, film, acc, cnt);
+    }
+    float *dst = film_entry(sc, blk, lx, ly, as_global(film));
+    for (int k = 0; k < 5; ++k) atomicAdd(dst + k, acc[k]);
+    if (COUNT) flush_counters(counters, cnt);
+}
+// `volpath` of an instanced scene on the 1024-path rings: the INTERSECT block runs the two-level traversal, the SURFACE and BSDF blocks resolve
+// the instance per lane ahead of their waterfalls over shapes; scalar streams, no counters.
+template <int WG, int NT, int WPE>
+__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_inst(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
+                                                                uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
+                                                                unsigned long long *counters, const uint32_t *stop_flag,
+                                                                const uint32_t *tiles, uint32_t n_tiles) {
+    Counters cnt = {};
+    ring_workgroup_async<VolpathRing<false, WG, false, false, TEX_INST>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+}
+// sample_kernel / intersect_kernel of an instanced scene (a hit reports the member's index in mts_scene_desc.shapes)
+__global__ void __launch_bounds__(256) sample_kernel_inst(DScene sc, int32_t n, uint64_t seed_offset, const float *__restrict__ rays /* 6 SoA rows */,
+                                                          float *__restrict__ out_rgb, uint8_t *__restrict__ out_valid) {
+    pm_tables_to_lds(threadIdx.x);
+    __syncthreads();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Pcg32 rng; rng.seed(sc.sensor.seed + seed_offset + (uint64_t) i, PCG32_DEFAULT_STREAM);
+    DRay ray = make_ray(f3(rays[i], rays[n + i], rays[2 * n + i]), f3(rays[3 * n + i], rays[4 * n + i], rays[5 * n + i]), MTS_RAY_EPSILON, pm_inf());
+    bool valid; Counters cnt;
+    F3 L = integrator_sample<false, NI_ANY, TEX_INST>(sc, rng, ray, sc.sensor.medium, valid, cnt);
+    out_rgb[3 * i] = L.x; out_rgb[3 * i + 1] = L.y; out_rgb[3 * i + 2] = L.z; out_valid[i] = valid ? 1 : 0;
+}
+__global__ void __launch_bounds__(256) intersect_kernel_inst(DScene sc, int32_t n, const float *__restrict__ o, const float *__restrict__ d,
+                                                             const float *__restrict__ mint, const float *__restrict__ maxt,
+                                                             float *__restrict__ out_t, int32_t *__restrict__ out_shape, int32_t *__restrict__ out_prim,
+                                                             float *__restrict__ out_p, float *__restrict__ out_n) {
+    pm_tables_to_lds(threadIdx.x);
+    __syncthreads();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    DRay ray = make_ray(f3(o + 3 * i), f3(d + 3 * i), mint[i], maxt[i]);
+    Hit h = ray_intersect<false, true>(sc, ray);
+    F3 nn = f3s(0.f);
+    int prim = -1, shape = -1;
+    if (hit_valid(h)) {
+        Surf sf; complete_surface<true>(sc, h, ray.d, sf); nn = sf.n;
+        shape = hit_shape<true>(h);
+        prim = sc.shapes[shape].type == MTS_SHAPE_SPHERE ? 0 : h.prim;
+    }
+    out_t[i] = h.t; out_shape[i] = shape; out_prim[i] = prim;
+    out_p[3 * i] = h.p.x; out_p[3 * i + 1] = h.p.y; out_p[3 * i + 2] = h.p.z;
+    out_n[3 * i] = nn.x; out_n[3 * i + 1] = nn.y; out_n[3 * i + 2] = nn.z;
+}
+
 // sample_tea_32 / sample_tea_64 / sample_tea_float32 for n (v0, v1) pairs (core/random.h:75-140)
 __global__ void __launch_bounds__(256) tea_kernel(int32_t n, const uint32_t *__restrict__ v0, const uint32_t *__restrict__ v1, int rounds,
                                                   uint32_t *__restrict__ out32, uint64_t *__restrict__ out64, float *__restrict__ outf) {
@@ -586,7 +671,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     const int integ = a.sc->integrator.type;
     const bool volpath = integ == MTS_INTEGRATOR_VOLPATH, mis = integ == MTS_INTEGRATOR_VOLPATHMIS, spec_mis = a.sc->integrator.use_spectral_mis != 0;
 #if defined(MTS_LEAN)
-    if (a.moment || a.textured) return hipErrorInvalidConfiguration;      // a moment or textured scene presents no traits: the general unit renders it
+    if (a.moment || a.textured || a.instanced) return hipErrorInvalidConfiguration;      // a moment, textured or instanced scene presents no traits: the general unit renders it
 #endif
 #if defined(MTS_LEAN_PATH)    // kernels_lean_p.hip / _ps.hip: `path` as the flat loop with regeneration, nothing else
     (void) volpath; (void) mis; (void) spec_mis;
@@ -613,6 +698,13 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
         if (a.variant == kv::FLAT) return launch_lane(a, threads, render_kernel_moment<false, true>);
         return launch_lane(a, threads, a.count ? render_kernel_moment<true, false> : render_kernel_moment<false, false>);
     }
+    if (a.instanced) {                                         // an instanced scene: mapped from the table's row as a textured scene is, to the INST kernels
+        if (a.moment || !a.textured || a.sc->instances == nullptr) return hipErrorInvalidConfiguration;
+        if (a.variant != kv::textured_variant(a.variant, integ, a.sc->sensor.wavefront != 0, a.count)) return hipErrorInvalidConfiguration;
+        if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, render_kernel_wga_inst<1024, 1024, 4>);
+        if (a.variant == kv::FLAT) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel_inst, true));
+        return launch_lane(a, threads, MTS_BY_COUNT(render_kernel_inst, false));
+    }
     if (a.textured) {                                          // a textured scene: a.variant is kv::textured_variant() of the table's row (capi.cpp)
         if (a.variant != kv::textured_variant(a.variant, integ, a.sc->sensor.wavefront != 0, a.count)) return hipErrorInvalidConfiguration;
         if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, render_kernel_wga_tex<1024, 1024, 4>);
@@ -635,7 +727,7 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     }
     if (a.variant != kv::NESTED && volpath) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel, true, NI_VOLPATH));     // the flat state machine per lane
 #else
-    if (a.moment || a.textured) return hipErrorInvalidConfiguration;      // rgb / mono only (scene_host.cpp refuses the description)
+    if (a.moment || a.textured || a.instanced) return hipErrorInvalidConfiguration;      // rgb / mono only (scene_host.cpp refuses the description)
     // four-wide state: `volpath` 42 hot dwords per path; `volpathmis` 69 with spectral MIS (round 4: the path's matrices are parked during
     // walks), 53 without -- 256 paths per workgroup, two or three workgroups per CU
     if (kv::is_ring(a.variant) && volpath)
@@ -656,6 +748,11 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
 
 hipError_t launch_sample(const DScene &sc, int32_t n, uint64_t seed_offset, const float *d_rays, float *d_rgb, uint8_t *d_valid, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
+    if (sc.instances != nullptr) {                             // an instanced scene
+        if (sc.bsdf_tex == nullptr) return hipErrorInvalidConfiguration;
+        hipLaunchKernelGGL(sample_kernel_inst, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(sc.bsdf_tex != nullptr ? sample_kernel<true> : sample_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
     return hipGetLastError();
 }
@@ -663,6 +760,10 @@ hipError_t launch_sample(const DScene &sc, int32_t n, uint64_t seed_offset, cons
 hipError_t launch_intersect(const DScene &sc, int32_t n, const float *o, const float *d, const float *mint, const float *maxt,
                             float *t, int32_t *shape, int32_t *prim, float *p, float *nn, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
+    if (sc.instances != nullptr) {                             // an instanced scene
+        hipLaunchKernelGGL(intersect_kernel_inst, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, o, d, mint, maxt, t, shape, prim, p, nn);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, o, d, mint, maxt, t, shape, prim, p, nn);
     return hipGetLastError();
 }

@@ -193,6 +193,7 @@ static DXf xf_perspective(float fov, float near_, float far_) {
 // Which promises of integrator_dev.h's scene traits (MT_*: what the lean translation units were compiled without) this scene keeps.
 // mts_render launches the leanest kernel whose promises are all kept; a scene that keeps none runs on the general kernels.
 static int scene_traits(const HostScene &hs, bool spectral) {
+    if (!hs.instances.empty()) return 0;                                // an instanced scene promises nothing either: the INST kernels are the general rgb / mono unit's
     if (!hs.bsdf_tex.empty()) return 0;                                 // a scene with textures, a blendbsdf or a twosided promises nothing: the general rgb / mono unit holds the TEX kernels
     int tr = 0;
     bool media = !hs.media.empty();
@@ -632,6 +633,9 @@ static void build_textures(const mts_scene_desc &d, bool spectral, HostScene &hs
         // a blend or a twosided renders in the TEX instantiations, which read the index table: all -1 under a constant weight and plain children
         for (int i = 0; i < d.bsdf_count; ++i)
             if (d.bsdfs[i].type == MTS_BSDF_BLEND || d.bsdfs[i].type == MTS_BSDF_TWOSIDED) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
+        // so does an instanced scene: the INST kernels are TEX instantiations
+        for (int i = 0; i < d.shape_count; ++i)
+            if (d.shapes[i].type == MTS_SHAPE_INSTANCE) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
         return;
     }
     // rgb texels need the sRGB upsampling model (bitmap.cpp:169-178), whose data this backend has not got -- as for three-channel grids
@@ -646,7 +650,8 @@ static void build_textures(const mts_scene_desc &d, bool spectral, HostScene &hs
     hs.scene.texture_count = d.texture_count;
 }
 // one shape of the description: its record, its primitives and their rows in the per-primitive tables; the scene's bounding box grows (scene.cpp:31-40)
-static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaults, HostScene &hs) {
+// `bbox`: the box that grows -- the scene's, or the group's of a shapegroup's member (group space)
+static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaults, HostScene &hs, DBBox &bbox) {
     const mts_shape &s = d.shapes[i];
     check_index(s.bsdf, d.bsdf_count, "shape bsdf", true); check_index(s.interior_medium, d.medium_count, "shape interior", true);
     check_index(s.exterior_medium, d.medium_count, "shape exterior", true); check_index(s.emitter, d.emitter_count, "shape emitter", true);
@@ -655,8 +660,9 @@ static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaul
     if (ds.bsdf < 0) ds.bsdf = ds.emitter >= 0 ? defaults.emitter : defaults.plain;
     ds.bsdf_type = hs.bsdfs[(size_t) ds.bsdf].type; ds.bsdf_flags = hs.bsdfs[(size_t) ds.bsdf].flags;
     ds.prim_offset = (int32_t) hs.prims.size();
-    hs.shapes.push_back(ds); bbox_expand(hs.scene.bbox, sb);
-    if (i < 64 && ds.bsdf_type == MTS_BSDF_NULL && (ds.bsdf_flags & F_Smooth) == 0 && ds.emitter < 0) hs.scene.cross_mask |= 1ull << i;     // DScene::cross_mask
+    hs.shapes[(size_t) i] = ds; bbox_expand(bbox, sb);
+    // DScene::cross_mask: the scene's own shapes only -- a hit on a group's member carries its instance above the shape index (Hit::shape), so no bit could serve it
+    if (&bbox == &hs.scene.bbox && i < 64 && ds.bsdf_type == MTS_BSDF_NULL && (ds.bsdf_flags & F_Smooth) == 0 && ds.emitter < 0) hs.scene.cross_mask |= 1ull << i;
     const bool triangles = ds.type == MTS_SHAPE_CUBE || ds.type == MTS_SHAPE_MESH;
     for (int k = 0; k < prim_count; ++k) {
         DPrim p; p.shape = i; p.index = k; hs.prims.push_back(p);
@@ -682,7 +688,7 @@ static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaul
     }
     if (triangles) {
         // Mesh::build_pmf (mesh.cpp:285-312) + DiscreteDistribution::update (distr_1d.h:49-83): running sum in double precision
-        DShape &sh = hs.shapes.back();
+        DShape &sh = hs.shapes[(size_t) i];
         double sum = 0.0; sh.area_lo = sh.area_hi = -1;
         for (int k = 0; k < prim_count; ++k) {
             float a = hs.area_pmf[(size_t) sh.prim_offset + k];
@@ -691,6 +697,114 @@ static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaul
         }
         sh.surface_area = (float) sum; sh.inv_surface_area = (float) (1.0 / sum);         // mesh.cpp:346-350,373
     } else for (int k = 0; k < prim_count; ++k) hs.area_cdf.push_back(0.f);
+}
+// ---- instanced geometry (mtsamd.h: MTS_SHAPE_SHAPEGROUP / MTS_SHAPE_INSTANCE; shapegroup.cpp, instance.cpp)
+static bool shape_is_instancing(int type) { return type == MTS_SHAPE_SHAPEGROUP || type == MTS_SHAPE_INSTANCE; }
+// Everything the description can get wrong about groups and instances, before any record is built.  member_of[i]: the index of the
+// group record shape i is a member of, -1 for the scene's own shapes (groups and instances included).
+static std::vector<int32_t> validate_instancing(const mts_scene_desc &d, bool spectral) {
+    std::vector<int32_t> member_of((size_t) std::max(d.shape_count, 0), -1);
+    bool any = false; int64_t instances = 0;
+    for (int i = 0; i < d.shape_count; ++i) any = any || shape_is_instancing(d.shapes[i].type);
+    if (!any) return member_of;
+    const auto name = [](int i) { return "shape " + std::to_string(i) + ": "; };
+    if (spectral) throw std::runtime_error("shapegroup / instance shapes are not supported in the spectral variant");
+    if (d.integrator.moment != 0) throw std::runtime_error("shapegroup / instance shapes are not supported inside a moment integrator's scene");
+    for (int i = 0; i < d.shape_count; ++i) {
+        const mts_shape &s = d.shapes[i];
+        if (s.type != MTS_SHAPE_SHAPEGROUP) continue;
+        if (member_of[(size_t) i] >= 0) throw std::runtime_error(name(i) + "a shapegroup among the members of shapegroup " + std::to_string(member_of[(size_t) i]) + " (Nested ShapeGroup is not permitted)");
+        if (s.face_count < 0 || (int64_t) i + 1 + s.face_count > (int64_t) d.shape_count)
+            throw std::runtime_error(name(i) + "shapegroup: its " + std::to_string(s.face_count) + " members (face_count) run past the end of the shape array");
+        for (int m = i + 1; m <= i + s.face_count; ++m) {
+            const mts_shape &mem = d.shapes[m];
+            if (mem.type == MTS_SHAPE_SHAPEGROUP) throw std::runtime_error(name(m) + "a shapegroup among the members of shapegroup " + std::to_string(i) + " (Nested ShapeGroup is not permitted)");
+            if (mem.type == MTS_SHAPE_INSTANCE) throw std::runtime_error(name(m) + "an instance among the members of shapegroup " + std::to_string(i) + " (Nested instancing is not permitted)");
+            if (mem.emitter != -1) throw std::runtime_error(name(m) + "a member of shapegroup " + std::to_string(i) + " carries an emitter (Instancing of emitters is not supported)");
+            if (mem.interior_medium != -1) throw std::runtime_error(name(m) + "a member of shapegroup " + std::to_string(i) + " has an \"interior\" medium: media on instanced shapes are not supported on this backend");
+            if (mem.exterior_medium != -1) throw std::runtime_error(name(m) + "a member of shapegroup " + std::to_string(i) + " has an \"exterior\" medium: media on instanced shapes are not supported on this backend");
+            member_of[(size_t) m] = i;
+        }
+    }
+    for (int i = 0; i < d.shape_count; ++i) {
+        const mts_shape &s = d.shapes[i];
+        if (s.type != MTS_SHAPE_INSTANCE) continue;
+        ++instances;
+        if (s.vertex_count < 0 || s.vertex_count >= d.shape_count) throw std::runtime_error(name(i) + "instance: its group index (vertex_count) " + std::to_string(s.vertex_count) + " is out of range");
+        if (d.shapes[s.vertex_count].type != MTS_SHAPE_SHAPEGROUP) throw std::runtime_error(name(i) + "instance: shape " + std::to_string(s.vertex_count) + " is not a shapegroup (Only a shapegroup can be specified in an instance.)");
+        if (s.bsdf != -1 || s.interior_medium != -1 || s.exterior_medium != -1 || s.emitter != -1)
+            throw std::runtime_error(name(i) + "instance: bsdf, interior, exterior and emitter must be -1 (the members of its shapegroup carry the material)");
+    }
+    for (int i = 0; i < d.emitter_count; ++i)
+        if (d.emitters[i].type == MTS_EMITTER_AREA && d.emitters[i].shape >= 0 && d.emitters[i].shape < d.shape_count &&
+            (shape_is_instancing(d.shapes[d.emitters[i].shape].type) || member_of[(size_t) d.emitters[i].shape] >= 0))
+            throw std::runtime_error("emitter " + std::to_string(i) + ": its shape " + std::to_string(d.emitters[i].shape) + " is a shapegroup, one of its members or an instance (Instancing of emitters is not supported)");
+    if (instances > 0 && d.shape_count > MTS_INST_MAX_SHAPES)
+        throw std::runtime_error("an instanced scene holds at most " + std::to_string(MTS_INST_MAX_SHAPES) + " shape records (shape_count = " + std::to_string(d.shape_count) + "): the hit encoding keeps the shape in " + std::to_string(MTS_INST_SHAPE_BITS) + " bits");
+    if (instances > MTS_INST_MAX_INSTANCES)
+        throw std::runtime_error("at most " + std::to_string(MTS_INST_MAX_INSTANCES) + " instances per scene (the hit encoding), this one has " + std::to_string(instances));
+    return member_of;
+}
+// A group's bounding box: that of its acceleration structure, the union of its members' (shapegroup.cpp; group space)
+static DBBox group_bbox(const mts_scene_desc &d, int g) {
+    DBBox b; bbox_reset(b);
+    for (int m = g + 1; m <= g + d.shapes[g].face_count; ++m) { HostScene scratch; DBBox sb; int pc; (void) build_shape(d.shapes[m], scratch, sb, pc); bbox_expand(b, sb); }
+    return b;
+}
+// One instance: a shape record that holds its transform, ONE primitive of the scene (instance.cpp:94) whose walk record carries rows
+// 0..2 of to_object, and its device record.  `group`: the index of its group in hs.groups, `gb` that group's box.
+static void add_instance(const mts_scene_desc &d, int i, int group, const DBBox &gb, const DefaultBsdfs &defaults, HostScene &hs) {
+    DShape ds; memset(&ds, 0, sizeof(ds));
+    ds.type = MTS_SHAPE_INSTANCE;
+    ds.to_world = xf_from_abi(d.shapes[i].to_world); ds.to_object = xf_inverse(ds.to_world);       // instance.cpp:63-64
+    ds.bsdf = defaults.plain; ds.interior = ds.exterior = ds.emitter = -1;                          // never read: a hit names a member
+    ds.bsdf_type = hs.bsdfs[(size_t) ds.bsdf].type; ds.bsdf_flags = hs.bsdfs[(size_t) ds.bsdf].flags;
+    ds.prim_offset = (int32_t) hs.prims.size(); ds.area_lo = ds.area_hi = -1;
+    ds.vertex_offset = group;
+    hs.shapes[(size_t) i] = ds;
+    DBBox ib; bbox_reset(ib);                                                                       // instance.cpp:81-92: the eight transformed corners
+    if (gb.min[0] <= gb.max[0] && gb.min[1] <= gb.max[1] && gb.min[2] <= gb.max[2])
+        for (int k = 0; k < 8; ++k)
+            bbox_expand(ib, mat_point_affine(ds.to_world.m, f3((k & 1) ? gb.max[0] : gb.min[0], (k & 2) ? gb.max[1] : gb.min[1], (k & 4) ? gb.max[2] : gb.min[2])));
+    bbox_expand(hs.scene.bbox, ib);
+    DPrim p; p.shape = i; p.index = 0; hs.prims.push_back(p);
+    const float zero[24] = { 0 };
+    hs.tri.insert(hs.tri.end(), zero, zero + 9); hs.tri_attr.insert(hs.tri_attr.end(), zero, zero + 24);
+    DWalkPrim w; memset(&w, 0, sizeof(w)); w.type = MTS_SHAPE_INSTANCE; w.shape = (int32_t) hs.instances.size(); w.index = group;
+    memcpy(w.f, ds.to_object.m, 48);
+    hs.walk.push_back(w); hs.area_pmf.push_back(0.f); hs.area_cdf.push_back(0.f);
+    DInstance rec; memset(&rec, 0, sizeof(rec)); rec.to_world = ds.to_world; rec.to_object = ds.to_object; rec.group = group; rec.shape = i;
+    hs.instances.push_back(rec); hs.instance_boxes.push_back(ib);
+}
+// The shapes of a description: the scene's own (instances among them) first, in declaration order -- they are the scene level's
+// primitives [0, DScene::prim_count) -- then group by group the members' primitives, in group space.  A scene without groups gets
+// exactly the records it always got.
+static void build_shapes(const mts_scene_desc &d, const std::vector<int32_t> &member_of, const DefaultBsdfs &defaults, HostScene &hs) {
+    DShape none; memset(&none, 0, sizeof(none));
+    hs.shapes.assign((size_t) std::max(d.shape_count, 0), none);
+    std::vector<int32_t> group_index((size_t) std::max(d.shape_count, 0), -1);
+    for (int i = 0; i < d.shape_count; ++i)
+        if (d.shapes[i].type == MTS_SHAPE_SHAPEGROUP) {
+            DGroup g; memset(&g, 0, sizeof(g)); g.bbox = group_bbox(d, i); g.shape = i;
+            group_index[(size_t) i] = (int32_t) hs.groups.size(); hs.groups.push_back(g);
+            DShape &ds = hs.shapes[(size_t) i]; ds.type = MTS_SHAPE_SHAPEGROUP; ds.to_world = ds.to_object = xf_identity();
+            ds.bsdf = defaults.plain; ds.interior = ds.exterior = ds.emitter = -1; ds.area_lo = ds.area_hi = -1;
+            ds.bsdf_type = hs.bsdfs[(size_t) ds.bsdf].type; ds.bsdf_flags = hs.bsdfs[(size_t) ds.bsdf].flags;
+        }
+    for (int i = 0; i < d.shape_count; ++i) {
+        if (member_of[(size_t) i] >= 0 || d.shapes[i].type == MTS_SHAPE_SHAPEGROUP) continue;
+        if (d.shapes[i].type == MTS_SHAPE_INSTANCE) { const int g = group_index[(size_t) d.shapes[i].vertex_count]; add_instance(d, i, g, hs.groups[(size_t) g].bbox, defaults, hs); }
+        else add_shape(d, i, defaults, hs, hs.scene.bbox);
+    }
+    hs.scene.prim_count = (int32_t) hs.prims.size();
+    for (DGroup &g : hs.groups) {
+        g.prim_first = (int32_t) hs.prims.size();
+        DBBox gb; bbox_reset(gb);
+        for (int m = g.shape + 1; m <= g.shape + d.shapes[g.shape].face_count; ++m) add_shape(d, m, defaults, hs, gb);
+        g.prim_count = (int32_t) hs.prims.size() - g.prim_first;
+        hs.shapes[(size_t) g.shape].prim_offset = g.prim_first;
+    }
+    hs.scene.instance_count = (int32_t) hs.instances.size(); hs.scene.group_count = (int32_t) hs.groups.size();
 }
 // the scene's bounding sphere, which set_scene hands to the emitters and the distant sensors (scene.cpp:95-97, bbox.h:329-332)
 struct BSphere { float center[3], radius; };
@@ -841,6 +955,8 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     std::unique_ptr<HostScene> hsp(new HostScene());
     HostScene &hs = *hsp; DScene &sc = hs.scene; memset(&sc, 0, sizeof(sc));
     const bool spectral = d->integrator.spectral != 0;
+    if (d->shape_count < 0 || (d->shape_count > 0 && !d->shapes)) throw std::runtime_error("shapes: a negative count, or records missing");
+    const std::vector<int32_t> member_of = validate_instancing(*d, spectral);      // groups and instances, ahead of every record
     if (spectral) build_spectra(*d, hs);
     build_volumes(*d, spectral, hs);
     build_phases(*d, hs);
@@ -848,14 +964,14 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     const DefaultBsdfs defaults = build_bsdfs(*d, spectral, hs);
     build_textures(*d, spectral, hs);
     bbox_reset(sc.bbox);
-    for (int i = 0; i < d->shape_count; ++i) add_shape(*d, i, defaults, hs);
+    build_shapes(*d, member_of, defaults, hs);
     build_bvh(hs);
     const BSphere bsphere = scene_bsphere(sc.bbox);
     build_emitters(*d, spectral, bsphere, hs);
     sc.sensor = build_sensor(*d, bsphere, hs);
     build_integrator(*d, spectral, hs);
     sc.volume_count = (int) hs.volumes.size(); sc.phase_count = (int) hs.phases.size(); sc.medium_count = (int) hs.media.size();
-    sc.bsdf_count = (int) hs.bsdfs.size(); sc.shape_count = (int) hs.shapes.size(); sc.prim_count = (int) hs.prims.size();
+    sc.bsdf_count = (int) hs.bsdfs.size(); sc.shape_count = (int) hs.shapes.size();      // (prim_count: the scene level's primitives, build_shapes)
     sc.emitter_count = (int) hs.emitters.size();
     hs.traits = scene_traits(hs, spectral);
     return hsp.release();
@@ -936,39 +1052,65 @@ struct BvhLayout {
 };
 }
 
-void build_bvh(HostScene &hs) {
-    hs.bvh_nodes.clear(); hs.bvh_prims.clear(); hs.scene.bvh_node_count = 0;
-    int threshold = 40;                                                    // at or below this the scalar walk over the list is faster (measured: 31 primitives 584 vs 562 Msamples/s)
-    if (const char *e = getenv("MTSAMD_BVH_THRESHOLD")) threshold = atoi(e);
-    const int n = (int) hs.prims.size();
-    if (n <= threshold) return;
+// The BVH of one level: primitives [first, first + n) of prim order, appended to bvh_nodes / bvh_prims with absolute node and leaf
+// indices.  `diag`: the diagonal of the level's bounding box, which scales the margin.  Returns the number of nodes (0: the list is walked).
+static int32_t build_bvh_level(HostScene &hs, int first, int n, F3 diag, int threshold) {
+    if (n <= threshold) return 0;
     std::vector<PrimBox> pb((size_t) n);
     for (int i = 0; i < n; ++i) {
-        const DPrim &pr = hs.prims[(size_t) i]; const DShape &s = hs.shapes[(size_t) pr.shape];
-        PrimBox b; b.prim = i;
+        const DPrim &pr = hs.prims[(size_t) (first + i)]; const DShape &s = hs.shapes[(size_t) pr.shape];
+        PrimBox b; b.prim = first + i;
         for (int a = 0; a < 3; ++a) { b.lo[a] = INFINITY; b.hi[a] = -INFINITY; }
         auto add = [&b](F3 p) { const float v[3] = { p.x, p.y, p.z }; for (int a = 0; a < 3; ++a) { b.lo[a] = std::min(b.lo[a], v[a]); b.hi[a] = std::max(b.hi[a], v[a]); } };
         if (s.type == MTS_SHAPE_RECTANGLE || s.type == MTS_SHAPE_DISK) {
             for (int k = 0; k < 4; ++k) add(mat_point_affine(s.to_world.m, f3((k & 1) ? 1.f : -1.f, (k & 2) ? 1.f : -1.f, 0.f)));
         } else if (s.type == MTS_SHAPE_SPHERE) {
             add(f3(s.center) - f3s(s.radius)); add(f3(s.center) + f3s(s.radius));
+        } else if (s.type == MTS_SHAPE_INSTANCE) {                             // the instance's own box (instance.cpp:81-92)
+            const DBBox &ib = hs.instance_boxes[(size_t) hs.walk[(size_t) (first + i)].shape];
+            // an instance of an empty group has no box (instance.cpp:84-86): it gets the point of its translation, finite, so that
+            // no NaN centroid reaches the builder; the traversal finds nothing inside it
+            if (ib.min[0] <= ib.max[0] && ib.min[1] <= ib.max[1] && ib.min[2] <= ib.max[2]) { add(f3(ib.min)); add(f3(ib.max)); }
+            else add(f3(s.to_world.m[3], s.to_world.m[7], s.to_world.m[11]));
         } else {
-            const float *t = &hs.tri[9 * (size_t) i];
+            const float *t = &hs.tri[9 * (size_t) (first + i)];
             F3 p0 = f3(t), e1 = f3(t + 3), e2 = f3(t + 6);
             add(p0); add(p0 + e1); add(p0 + e2);
         }
         for (int a = 0; a < 3; ++a) b.c[a] = .5f * (b.lo[a] + b.hi[a]);
         pb[(size_t) i] = b;
     }
-    const F3 diag = f3(hs.scene.bbox.max) - f3(hs.scene.bbox.min);
     std::vector<TmpNode> tmp;
-    BvhBuilder bb{ pb, tmp, hs.bvh_prims };
+    std::vector<int32_t> leaves;
+    BvhBuilder bb{ pb, tmp, leaves };
     const int root = bb.build(0, n, 0);
     BvhLayout layout{ tmp };
     layout.assign(root, MTS_BVH_TOP_DEPTH);
-    hs.bvh_nodes.assign(8 * tmp.size(), 0.f);
-    layout.emit(root, (int) tmp.size(), 1e-5f * norm(diag) + 1e-7f, hs.bvh_nodes);
-    hs.scene.bvh_node_count = (int32_t) tmp.size();
+    std::vector<float> nodes(8 * tmp.size(), 0.f);
+    layout.emit(root, (int) tmp.size(), 1e-5f * norm(diag) + 1e-7f, nodes);
+    const int32_t node_base = (int32_t) (hs.bvh_nodes.size() / 8), leaf_base = (int32_t) hs.bvh_prims.size();
+    if (node_base != 0 || leaf_base != 0)                                      // behind another level: the indices become absolute
+        for (size_t k = 0; k < tmp.size(); ++k) {
+            int32_t skip, link; memcpy(&skip, &nodes[8 * k + 6], 4); memcpy(&link, &nodes[8 * k + 7], 4);
+            skip += node_base;
+            link = link < 0 ? link - node_base : (int32_t) (((uint32_t) ((link >> 3) + leaf_base) << 3) | (uint32_t) (link & 7));
+            memcpy(&nodes[8 * k + 6], &skip, 4); memcpy(&nodes[8 * k + 7], &link, 4);
+        }
+    hs.bvh_nodes.insert(hs.bvh_nodes.end(), nodes.begin(), nodes.end());
+    hs.bvh_prims.insert(hs.bvh_prims.end(), leaves.begin(), leaves.end());
+    return (int32_t) tmp.size();
+}
+
+void build_bvh(HostScene &hs) {
+    hs.bvh_nodes.clear(); hs.bvh_prims.clear(); hs.scene.bvh_node_count = 0;
+    int threshold = 40;                                                    // at or below this the scalar walk over the list is faster (measured: 31 primitives 584 vs 562 Msamples/s)
+    if (const char *e = getenv("MTSAMD_BVH_THRESHOLD")) threshold = atoi(e);
+    // the scene level first: its top levels are what the kernels stage in LDS; then every group's, by the same rule on its own count
+    hs.scene.bvh_node_count = build_bvh_level(hs, 0, hs.scene.prim_count, f3(hs.scene.bbox.max) - f3(hs.scene.bbox.min), threshold);
+    for (DGroup &g : hs.groups) {
+        g.node_first = (int32_t) (hs.bvh_nodes.size() / 8);
+        g.node_count = build_bvh_level(hs, g.prim_first, g.prim_count, f3(g.bbox.max) - f3(g.bbox.min), threshold);
+    }
 }
 
 // ---------------------------------------------------------------- upload
@@ -1002,7 +1144,7 @@ void upload_host_scene(HostScene &hs, int device) {
     sc.tri_attr = upload(hs, hs.tri_attr);
     sc.area_pmf = upload(hs, hs.area_pmf); sc.area_cdf = upload(hs, hs.area_cdf);
     sc.bvh_nodes = nullptr; sc.bvh_prims = nullptr; sc.bvh_lds = nullptr; sc.bvh_lds_count = 0;
-    if (sc.bvh_node_count > 0) { sc.bvh_nodes = upload(hs, hs.bvh_nodes); sc.bvh_prims = upload(hs, hs.bvh_prims); }
+    if (!hs.bvh_nodes.empty()) { sc.bvh_nodes = upload(hs, hs.bvh_nodes); sc.bvh_prims = upload(hs, hs.bvh_prims); }
     sc.sensor.rfilter.values = upload(hs, hs.rfilter_values);
     sc.sensor.multi = upload(hs, hs.multi_transforms);
     sc.textures = nullptr; sc.bsdf_tex = nullptr;
@@ -1011,6 +1153,8 @@ void upload_host_scene(HostScene &hs, int device) {
             if (hs.textures[i].type == MTS_TEXTURE_BITMAP) hs.textures[i].data = upload(hs, hs.texels[i]);
         sc.textures = upload(hs, hs.textures); sc.bsdf_tex = upload(hs, hs.bsdf_tex);
     }
+    sc.instances = nullptr; sc.groups = nullptr;
+    if (!hs.instances.empty()) { sc.instances = upload(hs, hs.instances); sc.groups = upload(hs, hs.groups); }
     sc.spectra = nullptr; sc.bsdf_sp = nullptr; sc.emitter_sp = nullptr; sc.volume_sp = nullptr; sc.cie = nullptr;
     if (hs.integrator.spectral) {
         for (size_t i = 0; i < hs.spectra.size(); ++i)
@@ -1399,6 +1543,10 @@ void digest_host_scene(HostScene &hs, bool device, uint64_t out[8]) {
     geom.add(from(sc.faces, hs.faces)); geom.add(from(sc.tri, hs.tri)); geom.add(from(sc.tri_attr, hs.tri_attr));
     geom.add(from(sc.area_pmf, hs.area_pmf)); geom.add(from(sc.area_cdf, hs.area_cdf));
     geom.add(from(sc.bvh_nodes, hs.bvh_nodes)); geom.add(from(sc.bvh_prims, hs.bvh_prims));
+    if (!hs.instances.empty()) {                           // instanced scenes: the records behind the tail's pointers and the two counts; nothing for any other scene
+        geom.add(from(sc.instances, hs.instances)); geom.add(from(sc.groups, hs.groups));
+        const int32_t counts[2] = { sc.instance_count, sc.group_count }; geom.add(counts, sizeof(counts));
+    }
     sens.add(from(sc.sensor.rfilter.values, hs.rfilter_values)); sens.add(from(sc.sensor.multi, hs.multi_transforms));
     sens.add(from(sc.bin_lo, hs.bin_lo)); sens.add(from(sc.bin_hi, hs.bin_hi));
     out[0] = rec.h; out[1] = grid.h; out[2] = pair.h; out[3] = tab.h; out[4] = spec.h; out[5] = head.h; out[6] = geom.h; out[7] = sens.h;

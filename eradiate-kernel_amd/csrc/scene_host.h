@@ -43,6 +43,10 @@ struct HostScene {
     // to four floats), and the per-BSDF index table; all three empty in a scene without textures -- but for the table of a scene that
     // holds a blendbsdf or a twosided: a non-empty table is what sends a scene to the TEX instantiations
     std::vector<DTexture> textures; std::vector<std::vector<float>> texels; std::vector<int32_t> bsdf_tex;
+    // instanced scenes (DScene::instances / groups): one record per MTS_SHAPE_INSTANCE / MTS_SHAPE_SHAPEGROUP, in the order of their
+    // shape records; instance_boxes: the world-space box of each instance (instance.cpp:81-92), by its index in `instances` -- what
+    // build_bvh puts around the instance's primitive (DWalkPrim::shape of that primitive is the index)
+    std::vector<DInstance> instances; std::vector<DGroup> groups; std::vector<DBBox> instance_boxes;
     std::vector<void *> device_allocs;
     // mts_scene_update: two words per volume the grid pass reduces into (launch.h: GridUpdateJob::stats), allocated by the first update
     // that rewrites a grid.  After an update of an uploaded scene, grid_data / pair_data above keep their sizes, not the device's contents.
@@ -54,7 +58,7 @@ struct HostScene {
 };
 
 HostScene *build_host_scene(const mts_scene_desc *desc);   // throws std::runtime_error
-void build_bvh(HostScene &hs);                 // fills bvh_nodes / bvh_prims when the scene has many primitives
+void build_bvh(HostScene &hs);                 // fills bvh_nodes / bvh_prims: the scene level's BVH when it has many primitives, then each group's by the same rule
 void upload_host_scene(HostScene &hs, int device);          // throws std::runtime_error
 void free_host_scene(HostScene *hs);
 // mts_scene_update: re-runs build_host_scene's per-record work for the dirty records of `desc` and the records derived from them, and
@@ -63,7 +67,8 @@ void free_host_scene(HostScene *hs);
 void update_host_scene(HostScene &hs, const mts_scene_desc *desc, const mts_dirty *dirty, int32_t n, hipStream_t stream);
 // FNV-1a over the scene's contents, pointer fields zeroed: [0] record arrays (texture records and the BSDFs' texture indices behind
 // them), [1] grid data, [2] pair grids, [3] phase tables (bitmap texels behind them),
-// [4] spectra, [5] traits and the scalar header of DScene, [6] geometry (prims, walk, vertex and triangle tables, area tables, BVH),
+// [4] spectra, [5] traits and the scalar header of DScene, [6] geometry (prims, walk, vertex and triangle tables, area tables, BVH; instance
+// and group records behind them),
 // [7] the sensor's and the bins' arrays (filter table, sub-sensor matrices, bin bounds).  One walk, two sources: `device` reads the
 // uploaded copy back (throws for a scene that is not in device memory), otherwise the walk reads HostScene's own vectors -- no
 // device is touched, and a fresh scene gives the same eight words either way.

@@ -502,7 +502,7 @@ struct RingMachine {
     // ================================================================= INTERSECT, the core (volpath.cpp:109,182,241,298,339,395,425)
     DEV bool intersect(P &p) const {
         if (!wants_int(p)) return false;
-        p.si = ray_intersect<M::GEOM_TABLE>(sc, p.ray);      // ring kernels of the lean units a, h: hit points from the LDS table
+        p.si = ray_intersect<M::GEOM_TABLE, M::INST>(sc, p.ray);      // ring kernels of the lean units a, h: hit points from the LDS table
         p.flags &= ~FL_NEEDS_INT;
         return true;
     }
@@ -549,11 +549,12 @@ struct RingMachine {
 
 // GEOM_: the machine runs under the ring driver of a unit with the geometry table in LDS (integrator_dev.h: MTS_GEOM_LDS)
 // TEX_: the BSDF record of a hit goes through its textures (integrator_dev.h: bsdf_apply_textures; general rgb / mono unit only)
-template <bool COUNT, bool MOMENT_ = false, bool GEOM_ = false, bool TEX_ = false>
+template <bool COUNT, bool MOMENT_ = false, bool GEOM_ = false, int TEX_ = TEX_NONE>
 struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>, PathState, true> {
     typedef RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>, PathState, true> Base;
     static constexpr bool MOMENT = MOMENT_;                    // RingMachine::blk_new: the `moment` wrapper's eleven-channel tail
-    static constexpr bool TEX = TEX_;
+    static constexpr int TEX = TEX_;
+    static constexpr bool INST = TEX_ == TEX_INST;      // an instanced scene: two-level traversal, the instance resolved per lane (integrator_dev.h)
     static constexpr bool GEOM_TABLE = GEOM_;
     using Base::sc; using Base::cnt; using Base::ctx; using Base::queue_intersection; using Base::wants_int;
     DEV VolpathMachine(const DScene &sc_, Counters &cnt_) : Base(sc_, cnt_) {}
@@ -888,7 +889,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         p.st = S_PHASE;
         Spec emitter_val;
         const SpecCtx cx = ctx(p); (void) cx;
-        DirSample ds = sample_emitter_direction(sc, p.ray.o, p.rng.next_2d(), false, emitter_val MTS_CX);
+        DirSample ds = sample_emitter_direction<INST>(sc, p.ray.o, p.rng.next_2d(), false, emitter_val MTS_CX);
         if (ds.pdf == 0.f) return;
         float phase_val = 0.f;
         WATERFALL_BEGIN(p.medium, mu)
@@ -912,13 +913,13 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         Surf sf; sf.wi = -p.ray.d; sf.sh.n = f3s(0.f); sf.n = f3s(0.f);
         Spec nt = spec_s(0.f); int is_tr = 0, ext = -1, inte = -1;
         if (hit) {
-            WATERFALL_BEGIN(p.si.shape, su)
+            WATERFALL_BEGIN(hit_shape<INST>(p.si), su)
                 const DShape s = cload(sc.shapes + su);
                 if (!is_nee) emitter = s.emitter;
                 nt = s.bsdf_type == MTS_BSDF_NULL ? spec_s(1.f) : spec_s(0.f);                // null.cpp:70-73, bsdf.cpp:11-14
                 is_tr = s.is_medium_transition; ext = s.exterior; inte = s.interior;
-                if (emitter >= 0) complete_surface<GEOM_TABLE>(sc, s, p.si, p.ray.d, sf);
-                else if (is_tr) sf.n = hit_geo_normal<GEOM_TABLE>(sc, s, p.si);
+                if (emitter >= 0) complete_surface<GEOM_TABLE, INST>(sc, s, p.si, p.ray.d, sf);
+                else if (is_tr) sf.n = hit_geo_normal<GEOM_TABLE, INST>(sc, s, p.si);
             WATERFALL_END
         }
         if (emitter >= 0) {                                    // direct-light walk reached an emitter, volpath.cpp:430-440
@@ -952,12 +953,12 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         int emitter = CROSSING ? -1 : sc.environment, bsdf_id = 0;
         F2 tex_uv; tex_uv.x = tex_uv.y = 0.f;                  // TEX: si.uv of the hit
         if (!CROSSING && hit) {
-            WATERFALL_BEGIN(p.si.shape, su)
+            WATERFALL_BEGIN(hit_shape<INST>(p.si), su)
                 const DShape s = cload(sc.shapes + su);
                 emitter = s.emitter; bsdf_id = s.bsdf;
-                if constexpr (TEX) tex_uv = surface_uv(sc, s, p.si);
+                if constexpr (TEX != 0) tex_uv = surface_uv<INST>(sc, s, p.si);
                 // the shading frame is only read by emitter evaluation and by the NEE of a smooth BSDF: a null boundary needs neither
-                if (s.emitter >= 0 || (s.bsdf_flags & F_Smooth) != 0) complete_surface<GEOM_TABLE>(sc, s, p.si, p.ray.d, sf);
+                if (s.emitter >= 0 || (s.bsdf_flags & F_Smooth) != 0) complete_surface<GEOM_TABLE, INST>(sc, s, p.si, p.ray.d, sf);
             WATERFALL_END
         }
         const SpecCtx cx = ctx(p); (void) cx;
@@ -972,7 +973,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         }
         if (!active_e) return;
         Spec emitter_val;                                      // volpath.cpp:200-212 -> sample_emitter :261-281
-        DirSample ds = sample_emitter_direction(sc, p.si.p, p.rng.next_2d(), false, emitter_val MTS_CX);
+        DirSample ds = sample_emitter_direction<INST>(sc, p.si.p, p.rng.next_2d(), false, emitter_val MTS_CX);
         if (ds.pdf == 0.f) return;
         F3 wo = to_local(sf.sh, ds.d), wi = sf.wi;
         Spec bsdf_val; float bpdf;
@@ -980,7 +981,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         // dword loads of the hit's own record, BEFORE the waterfall; that then runs over the resolved id and its record loads stay
         // wave-uniform (scalar loads into SGPRs).  The flips are per lane too; emitter_eval above read the unflipped sf.wi.z.
         // active_e above read the flags of the hit's own record, the union of both sides' (twosided.cpp:78-88).
-        if constexpr (TEX) {
+        if constexpr (TEX != 0) {
             const BsdfSide side = twosided_side(sc, bsdf_id, wi);
             bsdf_id = side.id;
             if (side.back) { wi.z = -wi.z; wo.z = -wo.z; }
@@ -988,7 +989,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         WATERFALL_BEGIN(bsdf_id, bu)
             DBsdf bsdf = cload(sc.bsdfs + bu);
             float blend_w = 0.f;                               // TEX: a blendbsdf's weight at the hit (the BSDF block evaluates the same again)
-            if constexpr (TEX) { if (bsdf.type == MTS_BSDF_BLEND) blend_w = blend_weight(sc, bu, bsdf, tex_uv); else bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; }); }
+            if constexpr (TEX != 0) { if (bsdf.type == MTS_BSDF_BLEND) blend_w = blend_weight(sc, bu, bsdf, tex_uv); else bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; }); }
             hit_bsdf_eval_pdf<TEX, true>(sc, bsdf, blend_w, tex_uv, wi, wo, bsdf_val, bpdf MTS_CXI(bu));
         WATERFALL_END
         e.cold.put_spec(C_CW, p.thr * bsdf_val * mis_weight(ds.pdf, ds.delta ? 0.f : bpdf)); e.cold.put_spec(C_EMIT, emitter_val);
@@ -1006,10 +1007,10 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         const uint32_t max_depth = (uint32_t) sc.integrator.max_depth;
         Surf sf; int bsdf_id = 0, is_tr = 0, ext = -1, inte = -1;
         F2 tex_uv; tex_uv.x = tex_uv.y = 0.f;                  // TEX: si.uv of the hit
-        WATERFALL_BEGIN(p.si.shape, su)
+        WATERFALL_BEGIN(hit_shape<INST>(p.si), su)
             const DShape s = cload(sc.shapes + su);
-            complete_surface<GEOM_TABLE>(sc, s, p.si, p.ray.d, sf);
-            if constexpr (TEX) tex_uv = surface_uv(sc, s, p.si);
+            complete_surface<GEOM_TABLE, INST>(sc, s, p.si, p.ray.d, sf);
+            if constexpr (TEX != 0) tex_uv = surface_uv<INST>(sc, s, p.si);
             bsdf_id = s.bsdf; is_tr = s.is_medium_transition; ext = s.exterior; inte = s.interior;
         WATERFALL_END
         const float s1 = p.rng.next_1d(); const F2 s2 = p.rng.next_2d();
@@ -1021,17 +1022,17 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         } else {
             F3 wi = sf.wi;
             BsdfSide side; side.id = bsdf_id; side.back = side.none = false;
-            if constexpr (TEX) {                               // a twosided's child, per lane and before the waterfall, as in blk_surf
+            if constexpr (TEX != 0) {                               // a twosided's child, per lane and before the waterfall, as in blk_surf
                 side = twosided_side(sc, bsdf_id, wi);
                 if (side.back) wi.z = -wi.z;
             }
             WATERFALL_BEGIN(side.id, bu)
                 DBsdf bsdf = cload(sc.bsdfs + bu);
                 float blend_w = 0.f;                           // TEX: a blendbsdf's weight at the hit
-                if constexpr (TEX) { if (bsdf.type == MTS_BSDF_BLEND) blend_w = blend_weight(sc, bu, bsdf, tex_uv); else bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; }); }
+                if constexpr (TEX != 0) { if (bsdf.type == MTS_BSDF_BLEND) blend_w = blend_weight(sc, bu, bsdf, tex_uv); else bsdf_apply_textures(sc, bu, bsdf, [&]() { return tex_uv; }); }
                 bsdf_val = hit_bsdf_sample<TEX, true>(sc, bsdf, blend_w, tex_uv, wi, s1, s2, bs MTS_CXI(bu));
             WATERFALL_END
-            if constexpr (TEX) {
+            if constexpr (TEX != 0) {
                 if (side.back) bs.wo.z = -bs.wo.z;             // twosided.cpp:121
                 if (side.none) { zero_bsdf_sample(bs); bsdf_val = spec_s(0.f); }     // wi.z == 0: neither side (:109)
             }
@@ -1340,6 +1341,9 @@ struct MaskWords { uint32_t lo, hi; };
 template <bool HAVE_SHAPE, int WG>
 DEV int cross_class(int cls, const PathState &p, const HotStore<WG> &hs, const MTS_CONST_AS void *kernarg) {
     if (cls == B_SURF && p.st == S_SURF && hit_valid(p.si)) {
+        // the word as it is stored: in an INST instantiation a member's hit carries 1 + its instance above MTS_INST_SHAPE_BITS bits, so it
+        // is >= 64 and stays in B_SURF, and the mask holds bits of the scene's own shapes alone (scene_host.cpp: add_shape)
+        static_assert(MTS_INST_SHAPE_BITS >= 6, "a packed member hit must lie beyond the 64 shapes of DScene::cross_mask");
         const uint32_t shape = HAVE_SHAPE ? (uint32_t) p.si.shape : hs.u(H_SIX + 5);
         const MaskWords m = cload_k<MaskWords>((const MTS_CONST_AS char *) kernarg + offsetof(WgArgs, sc) + offsetof(DScene, cross_mask));
         if (shape < 64u && (((shape < 32u ? m.lo : m.hi) >> (shape & 31u)) & 1u) != 0u) cls = B_CROSS;
@@ -1353,7 +1357,7 @@ DEV int cross_class(int cls, const PathState &p, const HotStore<WG> &hs, const M
 // from (pixel, sample index) on every load: a 64-bit TEA of four rounds, ~60 instructions, and one dword of the cold record -- in an
 // instantiation of its own, so that the kernels of the scalar streams do not change by an instruction.
 // __forceinline__: a real call costs 48 callee-saved VGPR spills + reloads per block visit (measured: 5 TB of scratch writes per render)
-template <bool COUNT, int WG, int C, bool WF = false, bool MOMENT = false, bool TEX = false>
+template <bool COUNT, int WG, int C, bool WF = false, bool MOMENT = false, int TEX = TEX_NONE>
 static __device__ __forceinline__ int wg_block(const MTS_CONST_AS void *kernarg_, uint32_t *hot_lds, uint32_t wg_base_, uint32_t pid, Counters *cnt) {
     uint32_t wg_base;
     const MTS_CONST_AS void *kernarg = block_uniforms(kernarg_, wg_base_, wg_base);
@@ -1375,7 +1379,7 @@ static __device__ __forceinline__ int wg_block(const MTS_CONST_AS void *kernarg_
 #if defined(MTSAMD_BLOCKSTATS)
     if (COUNT && C == B_SURF) {                               // [9]: the lane-visits of this class that are null-boundary crossings (tools/cross_class_stats.py)
         bool cross = p.st == S_SURF && hit_valid(p.si);
-        if (cross) { const DShape &s = a.sc.shapes[p.si.shape]; cross = s.bsdf_type == MTS_BSDF_NULL && (s.bsdf_flags & F_Smooth) == 0 && s.emitter < 0; }     // DScene::cross_mask's condition
+        if (cross) { const DShape &s = a.sc.shapes[hit_shape<TEX == TEX_INST>(p.si)]; cross = s.bsdf_type == MTS_BSDF_NULL && (s.bsdf_flags & F_Smooth) == 0 && s.emitter < 0; }     // DScene::cross_mask's condition
         const unsigned long long m = __ballot(cross);
         if (__builtin_amdgcn_readfirstlane((int) (threadIdx.x & 63)) == (int) (threadIdx.x & 63)) atomicAdd(&g_blockstats[9], (unsigned long long) __popcll(m));
     }
@@ -1425,7 +1429,7 @@ static __device__ __forceinline__ int wg_block(const MTS_CONST_AS void *kernarg_
 
 // Driver 2, the asynchronous regrouping of a workgroup's paths through LDS rings, is ring_driver.h; this is what it needs to know of
 // `volpath`.  WF: wavefront streams (wg_block).
-template <bool COUNT_, int WG_, bool WF, bool MOMENT = false, bool TEX = false>
+template <bool COUNT_, int WG_, bool WF, bool MOMENT = false, int TEX = TEX_NONE>
 struct VolpathRing {
     static constexpr bool COUNT = COUNT_;
     static constexpr int WG = WG_, HOT_DWORDS = H_COUNT, PACKED = H_PACKED;

@@ -47,6 +47,7 @@ template <bool COUNT, bool SPEC, bool MOMENT_ = false>
 struct VolpathMisMachine : RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, MisPathState<SPEC>, false> {
     static constexpr bool MOMENT = MOMENT_;                    // RingMachine::blk_new: the `moment` wrapper's eleven-channel tail
     static constexpr bool GEOM_TABLE = false;                  // RingMachine::intersect: the primitive list is walked from the scene records
+    static constexpr bool INST = false;                        // instanced scenes render `volpathmis` in the nested kernel
     typedef MisPathState<SPEC> P;
     typedef MisWeights<SPEC> W;
     typedef RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, P, false> Base;
@@ -295,7 +296,7 @@ struct VolpathMisMachine : RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, 
         p.wa += p.si.t;
         if (!hit) { end_nee(p, e); return; }
         Spec nt = spec_s(0.f); F3 n = f3s(0.f); int is_tr = 0, ext = -1, inte = -1;
-        WATERFALL_BEGIN(p.si.shape, su)
+        WATERFALL_BEGIN(hit_shape(p.si), su)
             const DShape s = cload(sc.shapes + su);
             nt = s.bsdf_type == MTS_BSDF_NULL ? spec_s(1.f) : spec_s(0.f);
             is_tr = s.is_medium_transition; ext = s.exterior; inte = s.interior;
@@ -318,7 +319,7 @@ struct VolpathMisMachine : RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, 
         Surf sf; sf.wi = -p.ray.d; sf.n = f3s(0.f); sf.sh.s = sf.sh.t = sf.sh.n = f3s(0.f);
         int emitter = sc.environment, bsdf_id = 0;
         if (hit) {
-            WATERFALL_BEGIN(p.si.shape, su)
+            WATERFALL_BEGIN(hit_shape(p.si), su)
                 const DShape s = cload(sc.shapes + su);
                 emitter = s.emitter; bsdf_id = s.bsdf;
                 complete_surface(sc, s, p.si, p.ray.d, sf);
@@ -360,7 +361,7 @@ struct VolpathMisMachine : RingMachine<VolpathMisMachine<COUNT, SPEC, MOMENT_>, 
     template <class E> DEV void blk_bsdf(P &p, const E &) const {
         if (p.st != S_BSDF) return;
         Surf sf; int bsdf_id = 0, is_tr = 0, ext = -1, inte = -1;
-        WATERFALL_BEGIN(p.si.shape, su)
+        WATERFALL_BEGIN(hit_shape(p.si), su)
             const DShape s = cload(sc.shapes + su);
             complete_surface(sc, s, p.si, p.ray.d, sf);
             bsdf_id = s.bsdf; is_tr = s.is_medium_transition; ext = s.exterior; inte = s.interior;

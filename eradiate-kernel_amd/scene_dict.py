@@ -511,6 +511,7 @@ class SceneBuilder:
         self.textures, self.bsdf_textures, self.bitmaps = [], [], {}
         self.blends = []         # where each blendbsdf sits (what a refusal of the whole scene names)
         self.twosided = []       # and each twosided
+        self.groups, self.instanced = [], []     # where each shapegroup / instance sits
 
     def _colour_node(self, kind, index, field, where, spectrum=-1, emitter=False):
         return ("spectrum", spectrum) if _SPECTRAL is not None else ("colour", kind, index, field, where, emitter)
@@ -1011,6 +1012,94 @@ class SceneBuilder:
         self._register(d, "shape", idx)
         return idx
 
+    # ------------------------------------------------------------ instanced geometry (src/shapes/shapegroup.cpp, instance.cpp; librender/shapegroup.cpp)
+    def add_shapegroup(self, d, where):
+        """A shapegroup: its record (mtsamd.h: MTS_SHAPE_SHAPEGROUP, face_count = the number of members) and, directly behind it, its
+        members' records -- shapes that are NOT part of the scene's geometry (scene.cpp:36-41).  The reference's ShapeGroup does not
+        traverse into its members, so the node lists nothing; what members reference by id is listed where it was declared."""
+        p = Props(d, where)
+        grp = A.Shape()
+        grp.type = A.SHAPE_SHAPEGROUP
+        grp.bsdf = grp.interior_medium = grp.exterior_medium = grp.emitter = -1
+        grp.to_world = _xf(None)
+        self.shapes.append(grp)
+        gidx = len(self.shapes) - 1
+        members = 0
+        for k, v in sorted_items(d):                                     # librender/shapegroup.cpp:15-40, in props.objects() order
+            if k in p.queried or not isinstance(v, dict):
+                continue
+            p.queried.add(k)
+            t = v.get("type")
+            kind = self.instances.get(v.get("id"), ("",))[0] if t == "ref" else None
+            if t == "instance" or kind == "instance":
+                if t == "instance":
+                    self._instance_group(v, where + "." + k)             # the child is constructed first: its own errors come first
+                raise RuntimeError("Nested instancing is not permitted")
+            if t == "shapegroup" or kind == "shapegroup":
+                raise RuntimeError("Nested ShapeGroup is not permitted")
+            if kind == "shape":
+                raise RuntimeError("\"%s\": a shapegroup member given by reference is not supported by this backend (declare the shape inside the group)" % (where + "." + k))
+            if t not in SHAPE_PLUGINS:
+                raise RuntimeError("Tried to add an unsupported object of type \"%s\" (key \"%s\" of shapegroup \"%s\")" % (t, k, where))
+            rec, emitter_dict = self.make_shape(v, where + "." + k)
+            if emitter_dict is not None:
+                raise RuntimeError("Instancing of emitters is not supported")
+            for key, medium in (("interior", rec.interior_medium), ("exterior", rec.exterior_medium)):
+                if medium >= 0:
+                    raise RuntimeError("\"%s\": an \"%s\" medium on a shapegroup member is not supported by this backend" % (where + "." + k, key))
+            self.shapes.append(rec)
+            members += 1
+        p.finish()
+        self.shapes[gidx].face_count = members
+        self.nodes[("shape", gidx)] = []
+        if isinstance(d, dict) and "id" in d:
+            self.instances[d["id"]] = ("shapegroup", gidx)
+        self.groups.append(where)
+        return gidx
+
+    def _instance_group(self, d, where):
+        """The one shapegroup of an instance (instance.cpp:66-78): inline, or a reference to one declared before."""
+        group = None
+        for k, v in sorted_items(d):
+            if k in ("type", "id", "to_world") or not isinstance(v, dict):
+                continue
+            t = v.get("type")
+            kind = self.instances.get(v.get("id"), ("",))[0] if t == "ref" else None
+            if t == "ref" and v.get("id") not in self.instances:
+                raise RuntimeError("Referenced id \"%s\" not found" % v.get("id"))
+            if t == "shapegroup" or kind == "shapegroup":
+                if group is not None:
+                    raise RuntimeError("Only a single shapegroup can be specified per instance.")
+                group = self.add_shapegroup(v, where + "." + k) if t == "shapegroup" else self.instances[v["id"]][1]
+            else:
+                if t == "instance":                                      # a child is constructed before its parent: its own errors come first
+                    self._instance_group(v, where + "." + k)
+                raise RuntimeError("Only a shapegroup can be specified in an instance.")
+        if group is None:
+            raise RuntimeError("A reference to a 'shapegroup' must be specified!")
+        return group
+
+    def add_instance(self, d, where):
+        """An instance (mtsamd.h: MTS_SHAPE_INSTANCE): to_world and, in vertex_count, the index of its group's record."""
+        p = Props(d, where)
+        rec = A.Shape()
+        rec.type = A.SHAPE_INSTANCE
+        rec.bsdf = rec.interior_medium = rec.exterior_medium = rec.emitter = -1
+        rec.to_world = _xf(p.get("to_world"))
+        for k, v in d.items():
+            if isinstance(v, dict) and k != "to_world":
+                p.queried.add(k)
+        group = self._instance_group(d, where)
+        p.finish()
+        rec.vertex_count = group
+        self.shapes.append(rec)
+        idx = len(self.shapes) - 1
+        self.nodes[("shape", idx)] = [("param", "to_world", "geometry", "to_world")]
+        if isinstance(d, dict) and "id" in d:
+            self.instances[d["id"]] = ("instance", idx)
+        self.instanced.append(where)
+        return idx
+
     # ------------------------------------------------------------ emitters
     @staticmethod
     def _emitter_colour(e, v, where):
@@ -1401,6 +1490,10 @@ class SceneBuilder:
             name = v.get("id", k)                                       # scene.cpp:237-244: a child goes by its id; here a key is one
             if t in SHAPE_PLUGINS:
                 self.children.append((name, ("shape", self.add_shape(v, k))))
+            elif t == "shapegroup":
+                self.children.append((name, ("shape", self.add_shapegroup(v, k))))
+            elif t == "instance":
+                self.children.append((name, ("shape", self.add_instance(v, k))))
             elif t in ("directional", "constant", "area", "point"):
                 self.children.append((name, ("emitter", self.add_emitter(v, k))))
             elif t in SENSOR_PLUGINS:
@@ -1431,6 +1524,10 @@ class SceneBuilder:
             raise RuntimeError("Textures inside a moment integrator's scene are not supported by this backend")
         if self.blends and self.integrator.moment:
             raise RuntimeError("\"blendbsdf\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.blends))
+        if (self.groups or self.instanced) and self.integrator.moment:
+            raise RuntimeError("\"shapegroup\" / \"instance\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.groups + self.instanced))
+        if (self.groups or self.instanced) and self.spectral:
+            raise RuntimeError("\"shapegroup\" / \"instance\" (%s) is not supported in the gpu_spectral variant" % ", ".join(self.groups + self.instanced))
         if self.twosided and self.integrator.moment:
             raise RuntimeError("\"twosided\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.twosided))
         return self.finish()

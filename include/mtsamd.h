@@ -160,8 +160,26 @@ typedef struct mts_texture {
     float color0[3], color1[3];
 } mts_texture;
 
-/* ---- Shapes (src/shapes/{rectangle,cube,sphere,disk}.cpp, src/librender/mesh.cpp) ---- */
-enum { MTS_SHAPE_RECTANGLE = 0, MTS_SHAPE_CUBE = 1, MTS_SHAPE_SPHERE = 2, MTS_SHAPE_MESH = 3, MTS_SHAPE_DISK = 4 /* src/shapes/disk.cpp */ };
+/* ---- Shapes (src/shapes/{rectangle,cube,sphere,disk,shapegroup,instance}.cpp, src/librender/{mesh,shapegroup}.cpp) ----
+ *      Instanced geometry (rgb / mono variants; not with mts_integrator.moment) adds no field: two more values of `type` on the
+ *      existing record (a library from before them refuses both as "unknown shape type"):
+ *      MTS_SHAPE_SHAPEGROUP   shapegroup.cpp: a group of shapes that are NOT part of the scene's own geometry (scene.cpp:36-41).
+ *        face_count           the number M >= 0 of its members: the M records that follow it directly in mts_scene_desc.shapes.  A
+ *                             member is a rectangle, cube, sphere, mesh or disk with its own to_world (group space = the members'
+ *                             to_world and nothing else) and its own bsdf; it carries no emitter ("Instancing of emitters is not
+ *                             supported") and, a limit of this backend, no interior_medium / exterior_medium; it is neither a
+ *                             shapegroup ("Nested ShapeGroup is not permitted") nor an instance ("Nested instancing is not
+ *                             permitted").  Nothing else of the group's record is read.
+ *      MTS_SHAPE_INSTANCE     instance.cpp: ONE primitive of the scene that places a group.
+ *        to_world             the instance's transform (any invertible affine matrix; its inverse transpose travels with it)
+ *        vertex_count         the index in mts_scene_desc.shapes of its MTS_SHAPE_SHAPEGROUP record, which may stand before or
+ *                             behind it; K instances of one record share one group on the device.
+ *                             bsdf, interior_medium, exterior_medium and emitter must be -1: material and media are the members'.
+ *      An area emitter's `shape` names neither a group, a member nor an instance.  Hits report a member's index in `shapes`.
+ *      Limits: at most 1024 shape records in an instanced scene and 2^21 - 2 instances (what a hit's packed shape word holds).
+ *      The value 7 is the first unassigned one and stays refused as "unknown shape type". */
+enum { MTS_SHAPE_RECTANGLE = 0, MTS_SHAPE_CUBE = 1, MTS_SHAPE_SPHERE = 2, MTS_SHAPE_MESH = 3, MTS_SHAPE_DISK = 4 /* src/shapes/disk.cpp */,
+       MTS_SHAPE_SHAPEGROUP = 5, MTS_SHAPE_INSTANCE = 6 };
 typedef struct mts_shape {
     int32_t type;
     mts_transform to_world;
@@ -327,6 +345,8 @@ typedef struct mts_stats {
     double calibration_ms;    /* device time of that launch                                      */
     int32_t textured;         /* 1 when the scene was rendered by the TEX instantiations (a scene with mts_scene_desc.textures or a blendbsdf): kernel_variant still names
                                  the row of the kernel table the scene gets; kernel_names.h: kv::textured_variant maps it to the kernel that ran */
+                              /* 2 when it was rendered by the INST kernels (a scene with an MTS_SHAPE_INSTANCE: the TEX instantiations over the two-level
+                                 traversal, mapped from the row in the same way) */
     int32_t reserved2_;
 } mts_stats;
 

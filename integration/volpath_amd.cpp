@@ -300,7 +300,14 @@ private:
                 indices.emplace_back(fc.data(), fc.data() + 3 * r.face_count); r.faces = indices.back().data();
                 r.to_world = xf(ScalarTransform4f());                               // the buffers are in world space already
             }
-        } else
+        } else if (cls == "instance" || cls == "shapegroup")
+            // mtsamd.h has records for both (MTS_SHAPE_INSTANCE / MTS_SHAPE_SHAPEGROUP: a group's members follow its record), but
+            // Scene::shapes() hands an Instance over without its group -- ShapeGroup does not traverse into its members, and
+            // Instance keeps m_shapegroup private -- so the visitor cannot write the member records: load such a scene through
+            // the backend's own loaders (load_dict / load_file), which build them
+            Throw("volpath_amd: shape plugin \"%s\": instanced geometry is not visited by this plugin (the reference exposes no "
+                  "access to a group's members); load the scene with the backend's load_dict / load_file", cls);
+        else
             Throw("volpath_amd: shape plugin \"%s\"", cls);
         return r;
     }
