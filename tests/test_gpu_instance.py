@@ -6,8 +6,9 @@ scaled and translated instance under a directional emitter, `path` with max_dept
 normal restated in float64 through the inverse transpose; (3) the kernels the table's rows map to and the four list / BVH combinations
 of the two levels agree bit for bit; (4) K references to one group render what K inline copies render; (5) full transport between
 five placed instances agrees with the independent float64 estimator, and wrong placements are rejected; (6) an update in place is a
-fresh load; (7) 256 instances of a 4 096-face mesh cost the device the records of one.  Nothing compares a render under a
-non-identity transform with the oracle bit for bit: it knows no instances."""
+fresh load; (7) 256 instances of a 4 096-face mesh cost the device the records of one.  The oracle knows no instances, so no RENDER
+under a non-identity transform is compared with it bit for bit; intersection is, per ray: on dyadic placements the device's t,
+member and primitive are the oracle's on the expanded plain scene (tests/test_gpu_instance_rays.py)."""
 import copy
 import ctypes as C
 import importlib
