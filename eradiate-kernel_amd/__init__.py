@@ -18,6 +18,7 @@ Only the `gpu_rgb` variant exists: there is no CPU fallback in the product path.
 import ctypes as C
 import threading
 import types
+import weakref
 
 import os
 import numpy as np
@@ -197,8 +198,18 @@ class Integrator:
     """SamplingIntegrator (include/mitsuba/render/integrator.h:42-51,114-119)."""
 
     def __init__(self, scene):
-        self._scene = scene
+        # The scene owns its integrator (scene.cpp:88-92), not the other way round: a weak reference, so that Scene <-> Integrator is no
+        # reference cycle and a dropped scene frees its device memory with its last reference -- not in some later pass of the cyclic
+        # collector, whose hipFree calls synchronise the device and would stall whatever thread triggers them behind a running render.
+        self._scene_ref = weakref.ref(scene)
         self.last_stats = None
+
+    @property
+    def _scene(self):
+        scene = self._scene_ref()
+        if scene is None:
+            raise RuntimeError("Integrator: the scene this integrator belongs to no longer exists")
+        return scene
 
     def render(self, scene, sensor, shard_index=0, shard_count=1, device_film=None, stream=None,
                collect_counters=False, device_film_floats=None):
@@ -216,7 +227,17 @@ class Integrator:
         """
         if scene is not self._scene:
             raise RuntimeError("Integrator.render(): the integrator belongs to another scene")
-        rec = scene._desc.sensor
+        # `sensor`: one of scene.sensors(), or its index (the reference's render() takes either, integrator_v.cpp:124-127).  The film is
+        # sized from THAT sensor's crop window and stored on THAT sensor's Film; the others keep their last film.
+        sensors = scene.sensors()
+        if isinstance(sensor, (int, np.integer)) and not isinstance(sensor, bool):
+            if not 0 <= int(sensor) < len(sensors):
+                raise RuntimeError("Integrator.render(): sensor index %d is out of range (the scene has %d)" % (int(sensor), len(sensors)))
+            sensor = sensors[int(sensor)]
+        index = next((i for i, s in enumerate(sensors) if s is sensor), None)
+        if index is None:
+            raise RuntimeError("Integrator.render(): the sensor belongs to another scene (pass one of scene.sensors(), or its index)")
+        rec = sensor._rec
         h, w = rec.crop_size[1], rec.crop_size[0]
         opts = A.RenderOpts()
         opts.shard_index, opts.shard_count = shard_index, shard_count
@@ -234,14 +255,14 @@ class Integrator:
                 opts.film_on_device = 1
                 opts.film_capacity = int(device_film_floats) if device_film_floats is not None else h * w * 5
                 sensor._film._storage = None
-                A.check(A.lib().mts_render(scene._handle, C.byref(opts), C.c_void_p(int(device_film)), C.byref(stats)))
+                A.check(A.lib().mts_render_sensor(scene._handle, index, C.byref(opts), C.c_void_p(int(device_film)), C.byref(stats)))
             else:
                 it = scene._desc.integrator
                 out = np.zeros((h, w, 11 if it.moment else 5 + 2 * it.bin_count), dtype=np.float32)    # X, Y, Z, A, W + aov_names()
                 opts.film_on_device = 0
                 opts.film_capacity = out.size
                 sensor._film._storage = out
-                A.check(A.lib().mts_render(scene._handle, C.byref(opts), out.ctypes.data_as(C.c_void_p), C.byref(stats)))
+                A.check(A.lib().mts_render_sensor(scene._handle, index, C.byref(opts), out.ctypes.data_as(C.c_void_p), C.byref(stats)))
         finally:
             # stats first: a KeyboardInterrupt re-raised by the handler surfaces at the next bytecode
             self.last_stats = {k: getattr(stats, k) for k, _ in A.Stats._fields_ if not k.startswith("reserved")}
@@ -285,11 +306,20 @@ class Scene:
         h = C.c_void_p()
         A.check(A.lib().mts_scene_create(C.byref(desc), device, C.byref(h)))
         self._handle = h
-        self._sensor = Sensor(desc.sensor, getattr(keep, "film_pixel_format", "rgba"))
+        # desc.sensor is sensor 0; the loader's other sensors (keep.extra_sensors, in the order it visited them) are added to the
+        # uploaded scene one by one.  A refused one raises; the handle goes with the object.
+        extras = list(getattr(keep, "extra_sensors", []))
+        formats = list(getattr(keep, "sensor_pixel_formats", [])) or [getattr(keep, "film_pixel_format", "rgba")]
+        formats += ["rgba"] * (1 + len(extras) - len(formats))
+        for rec in extras:
+            A.check(A.lib().mts_scene_add_sensor(h, C.byref(rec), None))
+        self._sensors = [Sensor(rec, fmt) for rec, fmt in zip([desc.sensor] + extras, formats)]
+        self._sensor = self._sensors[0]
         self._integrator = Integrator(self)
 
     def sensors(self):
-        return [self._sensor]
+        """Scene::sensors() (scene.h:95-98): one Sensor per record, in the order load_dict visited them (props.objects() order)."""
+        return list(self._sensors)
 
     def integrator(self):
         return self._integrator

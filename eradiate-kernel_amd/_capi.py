@@ -146,7 +146,8 @@ ABI_STRUCTS = {"mts_spectrum": Spectrum, "mts_transform": Transform, "mts_volume
 
 # every symbol include/mtsamd.h declares
 ABI_SYMBOLS = ["mts_abi_version", "mts_build_id", "mts_last_error", "mts_device_count", "mts_scene_create", "mts_scene_destroy",
-               "mts_render", "mts_cancel", "mts_sigint_scope_enter", "mts_sigint_scope_exit", "mts_sample", "mts_sample_spectral", "mts_ray_intersect", "mts_abi_sizeof", "mts_sample_tea", "mts_wavefront_sampler", "mts_scene_update"]
+               "mts_render", "mts_cancel", "mts_sigint_scope_enter", "mts_sigint_scope_exit", "mts_sample", "mts_sample_spectral", "mts_ray_intersect", "mts_abi_sizeof", "mts_sample_tea", "mts_wavefront_sampler", "mts_scene_update",
+               "mts_scene_add_sensor", "mts_scene_sensor_count", "mts_render_sensor"]
 
 _lib = None
 
@@ -171,6 +172,9 @@ def lib():
     L.mts_scene_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_void_p)]
     L.mts_scene_destroy.argtypes = [C.c_void_p]
     L.mts_render.argtypes = [C.c_void_p, C.POINTER(RenderOpts), C.c_void_p, C.POINTER(Stats)]
+    L.mts_scene_add_sensor.argtypes = [C.c_void_p, C.POINTER(Sensor), C.POINTER(i32)]
+    L.mts_scene_sensor_count.argtypes = [C.c_void_p, C.POINTER(i32)]
+    L.mts_render_sensor.argtypes = [C.c_void_p, i32, C.POINTER(RenderOpts), C.c_void_p, C.POINTER(Stats)]
     L.mts_cancel.argtypes = [C.c_void_p]
     L.mts_sigint_scope_enter.argtypes = [C.c_void_p]
     L.mts_sigint_scope_exit.argtypes = []
@@ -180,10 +184,12 @@ def lib():
     L.mts_sample_tea.argtypes = [C.c_int, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), fp]
     L.mts_wavefront_sampler.argtypes = [C.c_int, i32, C.c_uint64, i32, fp]
     L.mts_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Dirty), i32, C.c_void_p]
-    # debug entries (not in the header): the host half of an update, a hash of the device scene, and the same hash of a description's host scene
+    # debug entries (not in the header): the host half of an update, a hash of the device scene, the same hash of a description's host scene,
+    # and what one sensor of a scene with added sensors would render on
     L.mts_debug_update_plan.argtypes = [C.POINTER(SceneDesc), C.POINTER(SceneDesc), C.POINTER(Dirty), i32, C.POINTER(i32), C.POINTER(i32)]
     L.mts_debug_scene_digest.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mts_debug_desc_digest.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint64)]
+    L.mts_debug_sensor_choice.argtypes = [C.POINTER(SceneDesc), C.POINTER(Sensor), i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mts_debug_scene_geometry.argtypes = [C.POINTER(SceneDesc), C.POINTER(i32), C.POINTER(C.c_float)]
     L.mts_abi_sizeof.argtypes = [C.c_char_p]
     L.mts_abi_sizeof.restype = C.c_int

@@ -211,12 +211,13 @@ int mts_sigint_scope_exit(void) {
 
 // What choose_kernel (render_plan.cpp; DESIGN.md section 4, "kernel table") reads of a scene
 // (a `moment` scene presents no traits: its kernels are in the general unit)
-static KernelFacts facts_of(const HostScene &hs) { return { hs.integrator.type, hs.integrator.spectral != 0, hs.integrator.use_spectral_mis != 0, !hs.media.empty(), hs.scene.bin_count > 0, hs.scene.srf >= 0, hs.srf_lookup_by_wavelength, hs.scene.sensor.wavefront != 0, hs.integrator.moment ? 0 : hs.traits }; }
+// Facts, traits and the choice are those of a (scene, sensor) pair: `sv` is the sensor that renders (scene_host.h: host_sensor)
+static KernelFacts facts_of(const HostScene &hs, const SensorView &sv) { return { hs.integrator.type, hs.integrator.spectral != 0, hs.integrator.use_spectral_mis != 0, !hs.media.empty(), hs.scene.bin_count > 0, sv.srf >= 0, sv.srf_lookup_by_wavelength, sv.sensor->wavefront != 0, hs.integrator.moment ? 0 : sv.traits }; }
 // The kernel that renders a scene: the table's choice, which the `moment` wrapper maps to its own instantiation of that row or to the
 // nested moment kernel (kernel_names.h: kv::moment_variant)
-static KernelChoice kernel_of(const HostScene &hs, uint32_t block_size, const RenderSwitches &sw, bool counters) {
-    KernelChoice kc = choose_kernel(facts_of(hs), block_size, sw);
-    if (hs.integrator.moment) kc.variant = kv::moment_variant(kc.variant, hs.integrator.type, hs.scene.sensor.wavefront != 0, counters);
+static KernelChoice kernel_of(const HostScene &hs, const SensorView &sv, uint32_t block_size, const RenderSwitches &sw, bool counters) {
+    KernelChoice kc = choose_kernel(facts_of(hs, sv), block_size, sw);
+    if (hs.integrator.moment) kc.variant = kv::moment_variant(kc.variant, hs.integrator.type, sv.sensor->wavefront != 0, counters);
     return kc;
 }
 
@@ -227,10 +228,48 @@ int mts_debug_kernel_choice(const mts_scene_desc *desc, int32_t *kernel_variant)
     if (!kernel_variant) throw std::runtime_error("mts_debug_kernel_choice: kernel_variant is NULL");
     HostScene *hs = build_host_scene(desc);
     try {
-        const KernelChoice kc = kernel_of(*hs, plan_block_size(hs->integrator.block_size), read_render_switches(), false);
+        const KernelChoice kc = kernel_of(*hs, host_sensor(*hs, 0), plan_block_size(hs->integrator.block_size), read_render_switches(), false);
         *kernel_variant = kv::stat(kc.variant, kc.unit);
     } catch (...) { free_host_scene(hs); throw; }
     free_host_scene(hs);
+    API_CATCH
+}
+
+// Not part of the ABI either: what sensor `sensor` of a scene would render on -- the scene of `desc` with the `n_extra` sensors of
+// `extra` added in order (mts_scene_add_sensor's host half): the traits of that (scene, sensor) pair and mts_stats.kernel_variant
+// as mts_render_sensor would report it.  Host only (tests/test_sensors.py compares with the single-sensor description's
+// mts_debug_scene_traits / mts_debug_kernel_choice).
+int mts_debug_sensor_choice(const mts_scene_desc *desc, const mts_sensor *extra, int32_t n_extra, int32_t sensor, int32_t *traits, int32_t *kernel_variant) {
+    API_TRY
+    if (!traits || !kernel_variant) throw std::runtime_error("mts_debug_sensor_choice: NULL output");
+    if (n_extra < 0 || (n_extra > 0 && !extra)) throw std::runtime_error("mts_debug_sensor_choice: a negative count, or sensors missing");
+    HostScene *hs = build_host_scene(desc);
+    try {
+        for (int32_t k = 0; k < n_extra; ++k) (void) add_host_sensor(*hs, extra + k);
+        const SensorView sv = host_sensor(*hs, sensor);
+        const KernelChoice kc = kernel_of(*hs, sv, plan_block_size(hs->integrator.block_size), read_render_switches(), false);
+        *traits = sv.traits; *kernel_variant = kv::stat(kc.variant, kc.unit);
+    } catch (...) { free_host_scene(hs); throw; }
+    free_host_scene(hs);
+    API_CATCH
+}
+
+// Further sensors of a scene: sensor 0's constructor against the scene as created (scene_host.cpp: add_host_sensor).  Like an update
+// it is refused, not made to wait, while a render or another call holds the handle.
+int mts_scene_add_sensor(mts_scene *scene, const mts_sensor *sensor, int32_t *index) {
+    API_TRY
+    if (!scene) throw std::runtime_error("mts_scene_add_sensor: scene is NULL");
+    std::unique_lock<std::mutex> guard(scene->render_mutex, std::try_to_lock);
+    if (!guard.owns_lock()) throw std::runtime_error("mts_scene_add_sensor: a render of this scene is in flight (or another call on this handle: a sample / intersection query, an update)");
+    const int32_t i = add_host_sensor(*scene->hs, sensor);
+    if (index) *index = i;
+    API_CATCH
+}
+
+int mts_scene_sensor_count(mts_scene *scene, int32_t *count) {
+    API_TRY
+    if (!scene || !count) throw std::runtime_error("mts_scene_sensor_count: NULL argument");
+    *count = scene->hs->sensor_count.load();
     API_CATCH
 }
 
@@ -256,7 +295,7 @@ int mts_debug_update_plan(const mts_scene_desc *before, const mts_scene_desc *af
     HostScene *hs = build_host_scene(before);
     try {
         update_host_scene(*hs, after, dirty, n, nullptr);
-        const KernelChoice kc = kernel_of(*hs, plan_block_size(hs->integrator.block_size), read_render_switches(), false);
+        const KernelChoice kc = kernel_of(*hs, host_sensor(*hs, 0), plan_block_size(hs->integrator.block_size), read_render_switches(), false);
         *traits = hs->traits; *kernel_variant = kv::stat(kc.variant, kc.unit);
     } catch (...) { free_host_scene(hs); throw; }
     free_host_scene(hs);
@@ -268,7 +307,11 @@ int mts_debug_scene_digest(mts_scene *scene, uint64_t *out8) {
     API_TRY
     if (!scene || !out8) throw std::runtime_error("mts_debug_scene_digest: NULL argument");
     std::lock_guard<std::mutex> guard(scene->render_mutex);
+#if defined(MTSAMD_HOST_ONLY)
+    digest_host_scene(*scene->hs, false, out8);           // a host-only handle has no device copy: the walk over the host's own arrays
+#else
     digest_host_scene(*scene->hs, true, out8);
+#endif
     API_CATCH
 }
 
@@ -308,11 +351,18 @@ static_assert(sizeof(RENDER_LAUNCHERS) / sizeof(RENDER_LAUNCHERS[0]) == UNIT_COU
 #endif
 #endif
 
-int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_stats *stats) {
+// Sensor `sensor` of the scene renders: plan, film size, kernel facts, traits and the kernel choice are that sensor's.  The kernels get
+// a COPY of the scene's DScene with the sensor's record and srf in it (RenderArgs::sc): hs.scene, which mts_sample, mts_ray_intersect,
+// the digest and mts_scene_update read, is never written -- whatever a render throws, nothing is left swapped.
+int mts_render_sensor(mts_scene *scene, int32_t sensor, const mts_render_opts *opts_, float *film, mts_stats *stats) {
     API_TRY
     if (!scene || !film) throw std::runtime_error("mts_render: NULL argument");
     std::lock_guard<std::mutex> guard(scene->render_mutex);         // one render per handle at a time
     HostScene &hs = *scene->hs;
+    SensorView sv;
+    try { sv = host_sensor(hs, sensor); } catch (const std::runtime_error &e) { throw std::runtime_error(std::string("mts_render_sensor: ") + e.what()); }
+    DScene sc = hs.scene;
+    sc.sensor = *sv.sensor; sc.srf = sv.srf;
     mts_render_opts opts; memset(&opts, 0, sizeof(opts)); opts.shard_count = 1;
     if (opts_) opts = *opts_;
     if (opts.shard_count < 1 || opts.shard_index < 0 || opts.shard_index >= opts.shard_count) throw std::runtime_error("mts_render: invalid shard specification");
@@ -325,20 +375,20 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, hs.device));
 #endif
     hipStream_t stream = (hipStream_t) opts.stream;
-    const DSensor &se = hs.scene.sensor;
+    const DSensor &se = sc.sensor;
     RenderPlan plan = plan_render(se, hs.integrator.samples_per_pass, hs.integrator.block_size, hs.scene.film_channels, opts.shard_index, opts.shard_count, cus, sw);
     const uint32_t block_size = plan.block_size; const size_t film_floats = plan.film_floats;
     if (opts.film_capacity > 0 && (uint64_t) opts.film_capacity < (uint64_t) film_floats)
         throw std::runtime_error("mts_render: the film buffer holds " + std::to_string(opts.film_capacity) + " floats, this scene writes " + std::to_string(film_floats) +
                                  " (crop_width x crop_height x " + std::to_string(hs.scene.film_channels) + " channels: " +
                                  (hs.integrator.moment ? "X, Y, Z, A, W + the moment integrator's m1.X, m1.Y, m1.Z, m2.X, m2.Y, m2.Z)" : "X, Y, Z, A, W + two per spectral bin)"));
-    const KernelChoice kc = kernel_of(hs, block_size, sw, opts.collect_counters != 0);
+    const KernelChoice kc = kernel_of(hs, sv, block_size, sw, opts.collect_counters != 0);
     // a textured scene: the TEX instantiation that renders the table's row (kernel_names.h); mts_stats.kernel_variant keeps naming the row
     const bool textured = !hs.bsdf_tex.empty();            // texture records, a blendbsdf or a twosided (scene_host.cpp: build_textures); an instanced scene has the table too
     const bool instanced = !hs.instances.empty();          // the INST kernels (kernels.hip): the TEX instantiations over the two-level traversal, mapped from the row alike
-    const int variant = textured ? kv::textured_variant(kc.variant, hs.integrator.type, hs.scene.sensor.wavefront != 0, opts.collect_counters != 0) : kc.variant;
+    const int variant = textured ? kv::textured_variant(kc.variant, hs.integrator.type, se.wavefront != 0, opts.collect_counters != 0) : kc.variant;
 #if defined(MTSAMD_HOST_ONLY)
-    (void) stream; (void) t0; (void) stats; (void) variant; (void) instanced;
+    (void) stream; (void) t0; (void) stats; (void) variant; (void) instanced; (void) sc;
     HOST_ONLY_STOP("mts_render");
 #else
     RenderCache &rc = scene->cache;
@@ -394,7 +444,7 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
             // one 128-byte cold record per path in flight; volpathmis parks the path's two weight matrices in a second one (volpathmis_flat.h)
             const size_t ws_records = hs.integrator.type == MTS_INTEGRATOR_VOLPATHMIS ? 2 : 1;
             float *d_ws = (float *) rc.get(BUF_WORKSPACE, render_workspace_floats(paths, variant) * ws_records * sizeof(float));
-            const RenderArgs args = { &hs.scene, d_blocks, (uint32_t) blocks.size(), block_size, spp, d_target, d_counters, opts.collect_counters != 0, variant,
+            const RenderArgs args = { &sc, d_blocks, (uint32_t) blocks.size(), block_size, spp, d_target, d_counters, opts.collect_counters != 0, variant,
                                       d_ws, (const uint32_t *) scene->stop_word, d_tiles, (uint32_t) tiles.size(), stream, hs.integrator.moment != 0, textured, instanced };
             HIP_CHECK(launcher(args));
             HIP_CHECK(hipEventRecord(rc.ev1, stream));
@@ -462,6 +512,9 @@ int mts_render(mts_scene *scene, const mts_render_opts *opts_, float *film, mts_
     API_CATCH
 }
 
+int mts_render(mts_scene *scene, const mts_render_opts *opts, float *film, mts_stats *stats) { return mts_render_sensor(scene, 0, opts, film, stats); }
+
+// mts_sample, mts_sample_spectral and mts_ray_intersect read hs.scene as it is: sensor 0's seed and medium, whatever sensors were added
 int mts_sample(mts_scene *scene, int32_t n, uint64_t seed_offset, const float *ox, const float *oy, const float *oz,
                const float *dx, const float *dy, const float *dz, float *out_rgb, uint8_t *out_valid) {
     API_TRY

@@ -192,7 +192,9 @@ static DXf xf_perspective(float fov, float near_, float far_) {
 
 // Which promises of integrator_dev.h's scene traits (MT_*: what the lean translation units were compiled without) this scene keeps.
 // mts_render launches the leanest kernel whose promises are all kept; a scene that keeps none runs on the general kernels.
-static int scene_traits(const HostScene &hs, bool spectral) {
+// `se`: the sensor that renders -- a distant sensor's own target / origin shape counts as the scene's shapes do, so the traits are
+// those of a (scene, sensor) pair: HostScene::traits for sensor 0, host_sensor() for any of them.
+static int scene_traits(const HostScene &hs, bool spectral, const DSensor &se) {
     if (!hs.instances.empty()) return 0;                                // an instanced scene promises nothing either: the INST kernels are the general rgb / mono unit's
     if (!hs.bsdf_tex.empty()) return 0;                                 // a scene with textures, a blendbsdf or a twosided promises nothing: the general rgb / mono unit holds the TEX kernels
     int tr = 0;
@@ -209,7 +211,7 @@ static int scene_traits(const HostScene &hs, bool spectral) {
     if (hs.bvh_nodes.empty()) tr |= MT_NO_BVH;
     bool sphere = false, rpv = false, shape_emitter = false, tree = false, grid_eval = false;
     for (const DShape &sh : hs.shapes) sphere = sphere || sh.type == MTS_SHAPE_SPHERE;
-    sphere = sphere || hs.scene.sensor.target_shape.type == MTS_SHAPE_SPHERE || hs.scene.sensor.origin_shape.type == MTS_SHAPE_SPHERE;   // the distant sensors' own shapes
+    sphere = sphere || se.target_shape.type == MTS_SHAPE_SPHERE || se.origin_shape.type == MTS_SHAPE_SPHERE;   // the distant sensors' own shapes
     for (const DBsdf &b : hs.bsdfs) rpv = rpv || b.type == MTS_BSDF_RPV;
     for (const DEmitter &e : hs.emitters) shape_emitter = shape_emitter || e.shape >= 0;
     if (!media)                                                         // a medium that is not on a pair grid reads its grids through volume_eval()
@@ -532,9 +534,10 @@ static DEmitter build_emitter(const mts_emitter &e, const float center[3], float
     return de;
 }
 // the response function's weights can be recovered from the sampled wavelengths (srf_weights_of, integrator_dev.h, looks a weight up by its wavelength)
-static bool srf_lookup_by_wavelength(const HostScene &hs) {
-    if (hs.scene.srf < 0 || hs.spectra[(size_t) hs.scene.srf].type != MTS_SPECTRUM_DISCRETE) return true;
-    const std::vector<float> &w = hs.spectrum_wavelengths[(size_t) hs.scene.srf];
+// `srf`: a sensor's response function, an index into hs.spectra or -1
+static bool srf_lookup_by_wavelength(const HostScene &hs, int32_t srf) {
+    if (srf < 0 || hs.spectra[(size_t) srf].type != MTS_SPECTRUM_DISCRETE) return true;
+    const std::vector<float> &w = hs.spectrum_wavelengths[(size_t) srf];
     for (size_t k = 1; k < w.size(); ++k) if (!(w[k] > w[k - 1])) return false;
     return true;
 }
@@ -846,24 +849,27 @@ static void build_ray_target(const mts_sensor &s, const std::string &name, const
     } else if (se.target_type != MTS_DISTANT_TARGET_NONE && se.target_type != MTS_DISTANT_TARGET_POINT)
         throw std::runtime_error(name + " sensor: unknown " + key + " type");
 }
-// sensor, film, sampler.  Fills hs.rfilter_values and hs.multi_transforms next to the record it returns
-static DSensor build_sensor(const mts_scene_desc &d, const BSphere &bsphere, HostScene &hs) {
-    const mts_sensor &s = d.sensor;
+// What a sensor is built against -- the scene as created: its bounding sphere, the number of its media and the integrator's
+// samples_per_pass.  mts_scene_create (sensor 0) and mts_scene_add_sensor (the others) run the same constructor.
+struct SensorContext { BSphere bsphere; int32_t medium_count, samples_per_pass; };
+// sensor, film, sampler.  Fills the filter table and the sub-sensor matrices next to the record it returns
+static DSensor build_sensor(const mts_sensor &s, const SensorContext &cx, std::vector<float> &rfilter_values, std::vector<float> &multi_transforms) {
+    const BSphere &bsphere = cx.bsphere;
     DSensor se; memset(&se, 0, sizeof(se));
     se.type = s.type; se.to_world = xf_from_abi(s.to_world);
     se.width = s.film_width; se.height = s.film_height;
     se.crop_x = s.crop_offset[0]; se.crop_y = s.crop_offset[1]; se.crop_w = s.crop_size[0]; se.crop_h = s.crop_size[1];
     if (se.width <= 0 || se.height <= 0 || se.crop_w <= 0 || se.crop_h <= 0 || se.crop_x < 0 || se.crop_y < 0 ||
         se.crop_x + se.crop_w > se.width || se.crop_y + se.crop_h > se.height) throw std::runtime_error("film: invalid size / crop window");
-    se.rfilter = build_rfilter(s.rfilter_type, s.rfilter_radius, s.rfilter_stddev, hs.rfilter_values);
+    se.rfilter = build_rfilter(s.rfilter_type, s.rfilter_radius, s.rfilter_stddev, rfilter_values);
     if (se.rfilter.radius > 16.f) throw std::runtime_error("reconstruction filter radius too large");
     if (s.sample_count <= 0) throw std::runtime_error("sampler: sample_count must be positive");
     se.sample_count = s.sample_count; se.seed = s.sampler_seed; se.medium = s.medium; se.shutter_open_time = s.shutter_open_time;
     se.wavefront = s.sampler_wavefront != 0;
     // (mts_render clamps samples_per_pass to sample_count as integrator.cpp:58-65 does: a larger value is one pass as well)
-    if (se.wavefront && d.integrator.samples_per_pass >= 0 && d.integrator.samples_per_pass < s.sample_count)
+    if (se.wavefront && cx.samples_per_pass >= 0 && cx.samples_per_pass < s.sample_count)
         throw std::runtime_error("wavefront streams (mts_sensor.sampler_wavefront): samples_per_pass must cover the whole sample_count (one pass)");
-    check_index(s.medium, d.medium_count, "sensor medium", true);
+    check_index(s.medium, cx.medium_count, "sensor medium", true);
     if (s.type == MTS_SENSOR_PERSPECTIVE) {
         se.near_clip = s.near_clip; se.far_clip = s.far_clip;
         float fsx = (float) se.width, fsy = (float) se.height;
@@ -891,7 +897,7 @@ static DSensor build_sensor(const mts_scene_desc &d, const BSphere &bsphere, Hos
     } else if (s.type == MTS_SENSOR_MRADIANCEMETER || s.type == MTS_SENSOR_MDISTANT) {        // mradiancemeter.cpp:72-132, mdistant.cpp:147-203
         if (s.multi_count <= 0 || s.multi_transforms == nullptr) throw std::runtime_error("multi-sensor: no sub-sensors given");
         if (se.width != s.multi_count || se.height != 1) throw std::runtime_error("Film size must be [sensor_count, 1].");
-        hs.multi_transforms.assign(s.multi_transforms, s.multi_transforms + 16 * (size_t) s.multi_count);
+        multi_transforms.assign(s.multi_transforms, s.multi_transforms + 16 * (size_t) s.multi_count);
         se.multi_count = s.multi_count;
         se.needs_aperture_sample = s.type == MTS_SENSOR_MDISTANT ? 1 : 0;                        // m_needs_sample_3
         se.target_type = MTS_DISTANT_TARGET_NONE;
@@ -901,6 +907,17 @@ static DSensor build_sensor(const mts_scene_desc &d, const BSphere &bsphere, Hos
         }
     } else throw std::runtime_error("unknown sensor type");
     return se;
+}
+// A sensor's srf (perspective.cpp:113-121, radiancemeter.cpp:62-68): its index into hs.spectra, -1 for none.  spectrum_count: the
+// description's own (two default spectra follow them in hs.spectra)
+static int32_t build_sensor_srf(const mts_sensor &s, bool spectral, int32_t spectrum_count, const HostScene &hs) {
+    if (!spectral || s.srf == 0) return -1;
+    if (s.srf < 0 || s.srf > spectrum_count) throw std::runtime_error("index out of range: sensor srf");
+    if (s.type != MTS_SENSOR_PERSPECTIVE && !(s.type == MTS_SENSOR_MRADIANCEMETER && s.multi_count == 1))
+        throw std::runtime_error("srf: only perspective and radiancemeter sensors sample their wavelengths from a response function");
+    const int t = hs.spectra[(size_t) s.srf - 1].type;
+    if (t != MTS_SPECTRUM_UNIFORM && t != MTS_SPECTRUM_DISCRETE) throw std::runtime_error("srf: sample_spectrum is available for uniform and discrete spectra");
+    return s.srf - 1;
 }
 // integrator (integrator.cpp:23-39,302-315), the wrappers around it, the film's channels and the sensor's response function
 static void build_integrator(const mts_scene_desc &d, bool spectral, HostScene &hs) {
@@ -938,15 +955,8 @@ static void build_integrator(const mts_scene_desc &d, bool spectral, HostScene &
         sc.bin_mode = it.bin_mode; sc.bin_count = it.bin_count; sc.film_channels = 5 + 2 * it.bin_count;
     } else hs.integrator.bin_count = 0;
     if (it.moment != 0) sc.film_channels = 11;             // X, Y, Z, A, W, then the nested integrator's XYZ and its square (validated above)
-    if (spectral && d.sensor.srf != 0) {
-        if (d.sensor.srf < 0 || d.sensor.srf > d.spectrum_count) throw std::runtime_error("index out of range: sensor srf");
-        if (d.sensor.type != MTS_SENSOR_PERSPECTIVE && !(d.sensor.type == MTS_SENSOR_MRADIANCEMETER && d.sensor.multi_count == 1))
-            throw std::runtime_error("srf: only perspective and radiancemeter sensors sample their wavelengths from a response function");
-        const int t = hs.spectra[(size_t) d.sensor.srf - 1].type;
-        if (t != MTS_SPECTRUM_UNIFORM && t != MTS_SPECTRUM_DISCRETE) throw std::runtime_error("srf: sample_spectrum is available for uniform and discrete spectra");
-        sc.srf = d.sensor.srf - 1;
-        hs.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs);
-    }
+    sc.srf = build_sensor_srf(d.sensor, spectral, d.spectrum_count, hs);
+    hs.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs, sc.srf);
 }
 
 HostScene *build_host_scene(const mts_scene_desc *d) {
@@ -968,12 +978,12 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     build_bvh(hs);
     const BSphere bsphere = scene_bsphere(sc.bbox);
     build_emitters(*d, spectral, bsphere, hs);
-    sc.sensor = build_sensor(*d, bsphere, hs);
+    sc.sensor = build_sensor(d->sensor, SensorContext{ bsphere, d->medium_count, d->integrator.samples_per_pass }, hs.rfilter_values, hs.multi_transforms);
     build_integrator(*d, spectral, hs);
     sc.volume_count = (int) hs.volumes.size(); sc.phase_count = (int) hs.phases.size(); sc.medium_count = (int) hs.media.size();
     sc.bsdf_count = (int) hs.bsdfs.size(); sc.shape_count = (int) hs.shapes.size();      // (prim_count: the scene level's primitives, build_shapes)
     sc.emitter_count = (int) hs.emitters.size();
-    hs.traits = scene_traits(hs, spectral);
+    hs.traits = scene_traits(hs, spectral, sc.sensor);
     return hsp.release();
 }
 
@@ -1176,6 +1186,38 @@ void free_host_scene(HostScene *hs) {
     if (!hs) return;
     if (hs->uploaded) { (void) hipSetDevice(hs->device); for (void *p : hs->device_allocs) (void) hipFree(p); }
     delete hs;
+}
+
+// ---------------------------------------------------------------- further sensors (mts_scene_add_sensor)
+// Sensor 0's constructor against the scene as created; everything is validated and built before the scene is touched.  The device
+// tables of an uploaded scene join device_allocs: they keep their addresses until free_host_scene.
+int32_t add_host_sensor(HostScene &hs, const mts_sensor *s) {
+    if (!s) throw std::runtime_error("mts_scene_add_sensor: sensor is NULL");
+    const bool spectral = hs.integrator.spectral != 0;
+    HostSensor rec;
+    try {
+        const SensorContext cx = { scene_bsphere(hs.scene.bbox), (int32_t) hs.media.size(), hs.integrator.samples_per_pass };
+        rec.sensor = build_sensor(*s, cx, rec.rfilter_values, rec.multi_transforms);
+        rec.srf = build_sensor_srf(*s, spectral, spectral ? (int32_t) hs.spectra.size() - 2 : 0, hs);
+        rec.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs, rec.srf);
+    } catch (const std::runtime_error &e) { throw std::runtime_error(std::string("mts_scene_add_sensor: ") + e.what()); }
+    if (hs.uploaded) {
+        HIP_CHECK(hipSetDevice(hs.device));
+        rec.sensor.rfilter.values = upload(hs, rec.rfilter_values);
+        rec.sensor.multi = upload(hs, rec.multi_transforms);
+    }
+    hs.extra_sensors.push_back(std::move(rec));
+    hs.sensor_count.store(1 + (int) hs.extra_sensors.size());
+    return (int32_t) hs.extra_sensors.size();
+}
+
+SensorView host_sensor(const HostScene &hs, int32_t index) {
+    const int32_t n = 1 + (int32_t) hs.extra_sensors.size();
+    if (index < 0 || index >= n) throw std::runtime_error("sensor index " + std::to_string(index) + " is out of range (the scene has " + std::to_string(n) + (n == 1 ? " sensor)" : " sensors)"));
+    const bool spectral = hs.integrator.spectral != 0;
+    if (index == 0) return { &hs.scene.sensor, hs.scene.srf, hs.srf_lookup_by_wavelength, scene_traits(hs, spectral, hs.scene.sensor) };
+    const HostSensor &x = hs.extra_sensors[(size_t) index - 1];
+    return { &x.sensor, x.srf, x.srf_lookup_by_wavelength, scene_traits(hs, spectral, x.sensor) };
 }
 
 // ---------------------------------------------------------------- update (mts_scene_update)
@@ -1421,8 +1463,9 @@ void update_host_scene(HostScene &hs, const mts_scene_desc *d, const mts_dirty *
         hs.spectra[i] = ds;
         hs.spectrum_values[i].swap(kv.second.arrays.values); hs.spectrum_wavelengths[i].swap(kv.second.arrays.wavelengths); hs.spectrum_cdf[i].swap(kv.second.arrays.cdf);
     }
-    hs.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs);
-    hs.traits = scene_traits(hs, spectral);                // the next render picks the kernel a fresh scene would
+    hs.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs, hs.scene.srf);
+    for (HostSensor &x : hs.extra_sensors) x.srf_lookup_by_wavelength = srf_lookup_by_wavelength(hs, x.srf);      // a dirty spectrum may be any sensor's srf
+    hs.traits = scene_traits(hs, spectral, hs.scene.sensor);       // the next render picks the kernel a fresh scene would (the other sensors': host_sensor)
 
     // ---- 4. the device's copies of what changed
 #if !defined(MTSAMD_HOST_ONLY)
@@ -1549,6 +1592,12 @@ void digest_host_scene(HostScene &hs, bool device, uint64_t out[8]) {
     }
     sens.add(from(sc.sensor.rfilter.values, hs.rfilter_values)); sens.add(from(sc.sensor.multi, hs.multi_transforms));
     sens.add(from(sc.bin_lo, hs.bin_lo)); sens.add(from(sc.bin_hi, hs.bin_hi));
+    for (const HostSensor &x : hs.extra_sensors) {         // added sensors: nothing for a scene without them, so it hashes as it always did
+        DSensor r = x.sensor; r.rfilter.values = nullptr; r.multi = nullptr;
+        const int32_t of_sensor[2] = { x.srf, x.srf_lookup_by_wavelength ? 1 : 0 };
+        head.add(&r, sizeof(r)); head.add(of_sensor, sizeof(of_sensor));
+        sens.add(from(x.sensor.rfilter.values, x.rfilter_values)); sens.add(from(x.sensor.multi, x.multi_transforms));
+    }
     out[0] = rec.h; out[1] = grid.h; out[2] = pair.h; out[3] = tab.h; out[4] = spec.h; out[5] = head.h; out[6] = geom.h; out[7] = sens.h;
 }
 

@@ -490,7 +490,10 @@ class SceneBuilder:
 
     def __init__(self):
         self.volumes, self.phases, self.media, self.bsdfs, self.shapes, self.emitters = [], [], [], [], [], []
+        # the sensors in the order load() visits them: `sensor` is the first (mts_scene_desc.sensor, sensor 0), `extra_sensors` the others
+        # (Scene hands them to mts_scene_add_sensor in this order); sensor_pixel_formats: each one's film "pixel_format", in that order
         self.sensor = None
+        self.extra_sensors, self.sensor_pixel_formats = [], []
         self.sensor_dict = None
         self.integrator = None
         self.keep = []
@@ -1167,7 +1170,12 @@ class SceneBuilder:
             raise RuntimeError("Unknown / unsupported sensor plugin \"%s\"" % p.type)
         SENSOR_PLUGINS[p.type](self, p, s, where)
         p.finish()
-        self.sensor = s
+        self.sensor_pixel_formats.append(self._pixel_format)
+        if self.sensor is None:
+            self.sensor = s
+            self.film_pixel_format = self._pixel_format                   # sensor 0's, as ever
+        else:
+            self.extra_sensors.append(s)
 
     def _film(self, p, s, where):
         """film (src/librender/film.cpp:14-50, src/films/hdrfilm.cpp) and its reconstruction filter"""
@@ -1194,7 +1202,7 @@ class SceneBuilder:
                                "Found %s instead." % cf)
         if ff in ("rgbe", "pfm") and not (ff == "pfm" and pf == "luminance"):
             pf = "rgb"                                                     # hdrfilm.cpp:153-176
-        self.film_pixel_format = "luminance" if _MONO else pf             # hdrfilm.cpp:122-128
+        self._pixel_format = "luminance" if _MONO else pf                 # hdrfilm.cpp:122-128 (set_sensor files it under its sensor)
         fp_.get("high_quality_edges"); fp_.get("filename")
         rp = Props(fp_.get("rfilter", {"type": "gaussian"}), where + ".film.rfilter")
         s.rfilter_radius, s.rfilter_stddev = 0.5, 0.5
@@ -1497,9 +1505,7 @@ class SceneBuilder:
             elif t in ("directional", "constant", "area", "point"):
                 self.children.append((name, ("emitter", self.add_emitter(v, k))))
             elif t in SENSOR_PLUGINS:
-                if self.sensor is not None:
-                    raise RuntimeError("this backend supports a single sensor per scene")
-                self.set_sensor(v, k)
+                self.set_sensor(v, k)                                    # scene.cpp:41-60: any number; the first one visited is sensor 0
             elif t in INTEGRATOR_PLUGINS:
                 if self.integrator is not None:
                     raise RuntimeError("Only one integrator can be specified per scene.")

@@ -406,6 +406,25 @@ int  mts_scene_update(mts_scene *scene, const mts_scene_desc *desc, const mts_di
  * (stats->cancelled = 1, like render() returning false). */
 int  mts_render(mts_scene *scene, const mts_render_opts *opts, float *film, mts_stats *stats);
 
+/* Several sensors on one uploaded scene (scene.cpp:41-60: a scene holds any number of sensors; an Eradiate experiment renders its
+ * measures one after another: `for sensor in scene.sensors(): scene.integrator().render(scene, sensor)`).  mts_scene_desc.sensor is
+ * sensor 0.  mts_scene_add_sensor appends one more and returns its index (1, 2, ...) in *index (may be NULL); it runs the
+ * validation and the constructor-time work mts_scene_create runs for sensor 0, against the scene as created: its bounding sphere,
+ * its media (`medium`), its spectra (`srf`, spectral variant) and its integrator (a wavefront sensor needs samples_per_pass to
+ * cover its sample_count).  The record references nothing but records of the scene, and everything it points to (multi_transforms)
+ * is copied: the caller's arrays may go away after the call.  Everything is validated before anything is written: a refused call
+ * (a NULL sensor, an index out of range, a film or sensor the constructor refuses; the message names the field) leaves the scene as
+ * it was.  Like mts_scene_update it is refused, not made to wait, while a render or another call holds the handle.  Sensors cannot be
+ * changed or removed afterwards; they are outside mts_scene_update, which still refreshes what a sensor derives from a dirty `srf`.
+ *
+ * mts_render_sensor renders through sensor `sensor` of [0, count): the film is that sensor's crop_height x crop_width x channels
+ * (channels are the integrator's: 5, 5 + 2 x bins, 11), the render plan, the kernel (mts_stats.kernel_variant, .textured) and the
+ * statistics are that sensor's -- exactly those of a scene created with that sensor alone.  mts_render(s, o, f, st) is
+ * mts_render_sensor(s, 0, o, f, st).  mts_sample, mts_sample_spectral and mts_ray_intersect keep reading sensor 0 (seed, medium). */
+int  mts_scene_add_sensor(mts_scene *scene, const mts_sensor *sensor, int32_t *index);
+int  mts_scene_sensor_count(mts_scene *scene, int32_t *count);
+int  mts_render_sensor(mts_scene *scene, int32_t sensor, const mts_render_opts *opts, float *film, mts_stats *stats);
+
 /* Integrator::cancel */
 int  mts_cancel(mts_scene *scene);
 
