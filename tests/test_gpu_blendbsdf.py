@@ -19,6 +19,7 @@ import tests.kernel_rows as kr
 import tests.oracle_binding as ob
 import tests.test_gpu_textures as gt
 from tests.independent import problems_surface, problems_textured
+from tests.sheet_shared import WEIGHTS
 from tests.test_gpu_textures import ATOL, CONSTANT_SCENES, IRRADIANCE, MARGIN, N_RAYS, SUN, assert_is_fresh, bits, measured_rho, render
 from tests.test_independent_surface_pin import assert_agrees, fixture_for, load_surf_pin, rejected, rgb_estimate
 from tests.test_independent_textured_pin import hip_render, load_pin
@@ -94,14 +95,6 @@ def test_identities_equal_the_oracle(gpu_rgb, name, integrator, identity):
 # ================================================================ 2. closed form
 RHO_0, RHO_1 = np.array([0.15, 0.55, 0.35]), np.array([0.85, 0.25, 0.6])
 LUMINANCE = np.array([0.212671, 0.715160, 0.072169])                      # core/spectrum.h:246-248
-CLAMPED = np.array([[-0.5, 1.5, 0.25, 1.5], [1.5, 0.75, -0.5, -0.5], [-0.5, 1.5, 1.5, 0.5], [0.25, -0.5, 1.5, -0.5]], np.float32)
-WEIGHTS = {
-    "constant": 0.3,
-    "bilinear_1ch": dict(gt.TEXTURES["b44_bilinear_repeat"]),
-    "bilinear_3ch": dict(gt.TEXTURES["b44rgb_bilinear_clamp"]),
-    "checkerboard": {"type": "checkerboard", "color0": 0.8, "color1": 0.1, "to_uv": T.scale([4.0, 4.0, 1.0])},
-    "nearest_clamped": {"type": "bitmap", "data": CLAMPED, "filter_type": "nearest", "wrap_mode": "mirror", "to_uv": gt.UV23},
-}
 
 
 def weight_eval(weight, uv):

@@ -20,6 +20,7 @@ import tests.kernel_rows as kr
 import tests.oracle_binding as ob
 import tests.test_gpu_textures as tt
 from tests.independent import problems_instance
+from tests.sheet_shared import PLACE, place_matrix
 from tests.test_gpu_textures import ATOL, CONSTANT_SCENES, bits, digest, render
 from tests.test_independent_surface_pin import assert_agrees, rejected, rgb_estimate
 from tests.test_independent_textured_pin import hip_render
@@ -69,22 +70,6 @@ def test_identity_instance_equals_the_oracle(gpu_rgb, name, integrator):
 
 
 # ================================================================ 2. a closed form under a rotation, an uneven scale and a translation
-AXIS, ANGLE, SCALE, SHIFT = np.array([0.3, -0.5, 0.8]), 37.0, np.array([1.0, 0.6, 0.8]), np.array([0.2, -0.15, 0.1])
-PLACE = T.rotate(AXIS.tolist(), ANGLE) @ T.scale(SCALE.tolist()) @ T.translate(SHIFT.tolist())
-
-
-def place_matrix():
-    """the same transform from the definitions, float64: Rodrigues' rotation matrix times diag(scale) times the translation"""
-    k = AXIS / np.linalg.norm(AXIS)
-    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    a = np.radians(ANGLE)
-    R = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
-    M = np.eye(4)
-    M[:3, :3] = R @ np.diag(SCALE)
-    M[:3, 3] = M[:3, :3] @ SHIFT
-    return M
-
-
 def instanced_closed_form(surface, texture, integrator="path"):
     """tests/test_gpu_textures.closed_form_case with the surface inside a group instanced under PLACE: the group-space points and
     normals of that construction carried to world space here -- points by M, normals by the inverse transpose of M -- and the rays

@@ -113,16 +113,17 @@ def mat(t):
     return np.asarray(t.matrix, np.float64).reshape(4, 4)
 
 
-def rectangle(n):
-    s = RNG.random((n, 2))
+def rectangle(n, rng=None):
+    s = (rng or RNG).random((n, 2))
     m = mat(RECT_XF)
     p = (np.c_[2 * s - 1, np.zeros(n), np.ones(n)] @ m.T)[:, :3]
     normal = m[:3, 2] / np.linalg.norm(m[:3, 2])
     return {"type": "rectangle", "to_world": RECT_XF}, p, s, np.tile(normal, (n, 1)), np.full(n, 1.0)          # rectangle.cpp:205: uv = prim_uv / 2 + 1 / 2
 
 
-def disk(n):
-    r, phi = 0.1 + 0.85 * RNG.random(n), 2 * np.pi * RNG.random(n)
+def disk(n, rng=None):
+    rng = rng or RNG
+    r, phi = 0.1 + 0.85 * rng.random(n), 2 * np.pi * rng.random(n)
     m = mat(RECT_XF)
     p = (np.c_[r * np.cos(phi), r * np.sin(phi), np.zeros(n), np.ones(n)] @ m.T)[:, :3]
     normal = m[:3, 2] / np.linalg.norm(m[:3, 2])
@@ -131,8 +132,9 @@ def disk(n):
     return {"type": "disk", "to_world": RECT_XF}, p, uv, np.tile(normal, (n, 1)), seam
 
 
-def sphere(n):
-    theta, phi = np.pi * (0.08 + 0.84 * RNG.random(n)), 2 * np.pi * RNG.random(n)
+def sphere(n, rng=None):
+    rng = rng or RNG
+    theta, phi = np.pi * (0.08 + 0.84 * rng.random(n)), 2 * np.pi * rng.random(n)
     local = np.c_[np.sin(theta) * np.cos(phi), np.sin(theta) * np.sin(phi), np.cos(theta)]
     m = mat(SPHERE_XF)
     p = (np.c_[local, np.ones(n)] @ m.T)[:, :3]
@@ -142,9 +144,10 @@ def sphere(n):
     return {"type": "sphere", "to_world": SPHERE_XF}, p, uv, normal, seam
 
 
-def quad(n, texcoords):
-    face = RNG.integers(0, 2, n)
-    b = 0.05 + 0.9 * RNG.random((n, 2))
+def quad(n, texcoords, rng=None):
+    rng = rng or RNG
+    face = rng.integers(0, 2, n)
+    b = 0.05 + 0.9 * rng.random((n, 2))
     flip = b.sum(axis=1) > 1.0
     b[flip] = 1.0 - b[flip]
     b = np.clip(b, 0.03, None)                                         # strictly inside the triangle
@@ -163,7 +166,7 @@ def quad(n, texcoords):
     return shape, p, uv, normal, np.minimum(np.minimum(b[:, 0], b[:, 1]), b0)      # the margin: away from the triangle's edges
 
 
-SURFACES = {"rectangle": rectangle, "disk": disk, "sphere": sphere, "quad_uv": lambda n: quad(n, True), "quad_bary": lambda n: quad(n, False)}
+SURFACES = {"rectangle": rectangle, "disk": disk, "sphere": sphere, "quad_uv": lambda n, rng=None: quad(n, True, rng), "quad_bary": lambda n, rng=None: quad(n, False, rng)}
 B44 = np.random.default_rng(44).random((4, 4), dtype=np.float32)
 B53 = np.random.default_rng(53).random((3, 5, 3), dtype=np.float32)                  # 5 x 3 texels, rgb
 B44C = np.random.default_rng(45).random((4, 4, 3), dtype=np.float32)
