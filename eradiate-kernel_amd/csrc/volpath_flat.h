@@ -118,13 +118,29 @@ DEV float grid_fetch1(const MTS_GLOBAL_AS float *__restrict__ D, const GridCell 
 // x-neighbours of sigma_t and albedo.  Clamp mode only: x1 is x0 + 1 except on the last column, where both are nx - 1.
 // `nx` here is the stored row length: a one-column grid (the 1-D atmospheres: nz x 1 x 1) is stored two voxels wide.
 typedef float mts_float4 __attribute__((ext_vector_type(4)));
-typedef mts_float4 __attribute__((aligned(8))) mts_float4_a8;
-// columns_equal (wave-uniform): a profile in z only -- the two rows of a z-level hold the same voxels, one gather serves both.
+// columns_equal (wave-uniform): a profile in z only -- the two rows of a z-level hold the same voxels, two gathers serve the lookup.
+// The order of the gathers and of the one wait is PINNED in assembly: all loads of a lookup go out before the first wait on any of
+// them.  Left to the compiler, `q10 = q00; if (!columns_equal) q10 = load` becomes a move ahead of the branch, which waits for q00 and
+// q01 before the other two are issued -- two dependent round trips on every grid whose columns differ -- and every rewording of it
+// in C++ (a select behind the join, the conditional pair first, a diamond) came back to that order in at least one of the repeat
+// loops (tools/step_loop_stats.py --trips, tests/test_step_round_trips.py).  The compiler does not count these
+// loads in vmcnt, which only makes its own waits stricter (loads return in order); the values may be read only behind grid_gather_wait,
+// which every one of them passes through.
+DEV mts_float4 grid_gather_issue(const MTS_GLOBAL_AS float *p) {
+    mts_float4 q;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(q) : "v"(p) : "memory");
+    return q;
+}
+DEV void grid_gather_wait(mts_float4 &a, mts_float4 &b, mts_float4 &c, mts_float4 &d) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
 DEV void grid_fetch_pair(const MTS_GLOBAL_AS float *__restrict__ P, const GridCell &c, int nx, bool columns_equal, float &sigma_t, float &albedo) {
     const int xb = min(c.x0, nx - 2);
     const bool hi0 = c.x0 != xb, hi1 = c.x1 != xb;           // take the second voxel of the pair
-    mts_float4 q00 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * (c.r00 + xb)), q01 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * (c.r01 + xb)), q10 = q00, q11 = q01;
-    if (!columns_equal) { q10 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * (c.r10 + xb)); q11 = *(const MTS_GLOBAL_AS mts_float4_a8 *) (P + 2 * (c.r11 + xb)); }
+    mts_float4 q00 = grid_gather_issue(P + 2 * (c.r00 + xb)), q01 = grid_gather_issue(P + 2 * (c.r01 + xb)), q10 = {0.f, 0.f, 0.f, 0.f}, q11 = {0.f, 0.f, 0.f, 0.f};
+    if (!columns_equal) { q10 = grid_gather_issue(P + 2 * (c.r10 + xb)); q11 = grid_gather_issue(P + 2 * (c.r11 + xb)); }
+    grid_gather_wait(q00, q01, q10, q11);
+    if (columns_equal) { q10 = q00; q11 = q01; }
     sigma_t = trilerp(hi0 ? q00.z : q00.x, hi1 ? q00.z : q00.x, hi0 ? q10.z : q10.x, hi1 ? q10.z : q10.x,
                       hi0 ? q01.z : q01.x, hi1 ? q01.z : q01.x, hi0 ? q11.z : q11.x, hi1 ? q11.z : q11.x, c.w0, c.w1);
     albedo = trilerp(hi0 ? q00.w : q00.y, hi1 ? q00.w : q00.y, hi0 ? q10.w : q10.y, hi1 ? q10.w : q10.y,
@@ -750,9 +766,9 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
     // The arithmetic, its order and the draws are blk_med's and top's; what changes is the control structure: no early return, every lane
     // runs the same instructions, the grid lookup of a lane without a collision reads the voxels around its ray origin and drops them,
     // the outcome (escaped / null collision / real collision) picks the new state with selects, and the class follows from the outcome.
-    // What blk_med meets on its uncommon paths makes a lane RARE: a medium whose majorant has no invariant reciprocal (a scalar branch
-    // around the whole form), an argument outside the common range of pm_log / pm_exp / pm_div_by_invariant (their *_flag forms), the
-    // depth limit at a real collision, a walk whose transmittance became zero.  A rare lane commits nothing -- p still holds the state
+    // What blk_med meets on its uncommon paths makes a lane RARE: a medium whose majorant has no invariant reciprocal (rd == 0, found by
+    // value: a branch on it would split the record's scalar loads into two round trips), an argument outside the common range of pm_log /
+    // pm_exp / pm_div_by_invariant (their *_flag forms), the depth limit at a real collision, a walk whose transmittance became zero.  A rare lane commits nothing -- p still holds the state
     // it came with -- and one wave-uniform branch at the end runs blk_med, top and classify themselves for the rare lanes.  So a lane
     // either runs the general code, or instructions that are the general code's common path.
     template <int MODEK, class E> DEV int step_fast(PathState &p, const E &e) const {
@@ -766,8 +782,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         F3 mi_p = f3s(0.f);
         WATERFALL_BEGIN(p.medium, mu)
             const DMedium m = cload(sc.media + mu);            // medium_step, pair-grid arm
-            if (m.inv_max_density == 0.f) rare = true;         // wave-uniform: the plain division of div_by_invariant
-            else {
+            {                                                  // a majorant without an invariant reciprocal (rd == 0) makes the lane rare by value: no branch splits the record's loads
                 float bmint, bmaxt;
                 bool active = bbox_ray_intersect(m.aabb, p.ray, bmint, bmaxt);
                 active = active && (pm_isfinite(bmint) || pm_isfinite(bmaxt));
@@ -777,7 +792,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
                 mext = m.max_density; rd = m.inv_max_density;
                 bool ok_log, ok_div;
                 const float sampled_t = mint + pm_div_by_invariant_flag(-pm_log_flag(1.f - u, &ok_log), mext, rd, &ok_div);
-                rare = !(ok_log && ok_div);
+                rare = !(ok_log && ok_div) || rd == 0.f;
                 valid_mi = active && (sampled_t <= maxt);
                 mi_t = valid_mi ? sampled_t : pm_inf();
                 mi_p = ray_at(p.ray, sampled_t);

@@ -1,6 +1,6 @@
 """Static figures of the tracking step: the two in-place repeat loops of wg_block (volpath_flat.h) in one device unit's assembly.
 
-    python tools/step_loop_stats.py [unit.hip] [--kernel SUBSTRING] [--source DIR] [--asm FILE] [--keep FILE] [--histogram]
+    python tools/step_loop_stats.py [unit.hip] [--kernel SUBSTRING] [--source DIR] [--asm FILE] [--keep FILE] [--histogram] [--trips]
 
 Compiles the unit (default kernels_lean_a.hip) for the device only, to assembly, with the product flags of _buildid.py plus line
 tables (about 30 s; the added flags do not change the code), and finds the loops of the chosen kernel (default: the flagship,
@@ -18,9 +18,14 @@ Instructions are COUNTED by mnemonic prefix / substring only (s_, v_, ds_, globa
 needs more than a class: a mnemonic with `branch` in it ends a block and names a successor, and two are known by name -- `s_branch`
 (no fall-through) and `s_endpgm` (no successor).
 
-The anchors are literal texts of source lines of volpath_flat.h (comments at those lines say so): a reworded line makes the tool stop
-with a message that names the anchor.
+--trips adds, for the common path of each loop, the memory instructions (global_load*, s_load*, ds_read*) and the s_waitcnt between them
+in control-flow order from the loop head, and says whether (a) the grid gathers, (b) the medium record's scalar loads go out in one
+round trip each, and (c) the logarithm's table read is issued ahead of the record (trips(), tests/test_step_round_trips.py).
+
+The anchors are literal texts of source lines of volpath_flat.h (comments at those lines say so) and, for --trips, of cload's copy
+loop in integrator_dev.h: a reworded line makes the tool stop with a message that names the anchor.
 """
+import contextlib
 import os
 import re
 import subprocess
@@ -205,8 +210,8 @@ def stats(insts, blocks, body_blocks):
     return s, hist
 
 
-def step_loops(asm_path, kernel=DEFAULT_KERNEL):
-    """-> {"B_MED": (stats, histogram), "B_MEDW": (...)} of the kernel in an assembly file"""
+def find_loops(asm_path, kernel=DEFAULT_KERNEL):
+    """-> (insts, blocks, succ, dominates, {"B_MED": (blocks of the loop, blocks of its common path), "B_MEDW": (...)})"""
     insts, labels = parse_kernel(asm_path, kernel)
     repeat, main, walk = anchor_lines(REPEAT_ANCHOR), anchor_lines(MAIN_ANCHOR), anchor_lines(WALK_ANCHOR)
     for name, text, lines in (("REPEAT_ANCHOR", REPEAT_ANCHOR, repeat), ("MAIN_ANCHOR", MAIN_ANCHOR, main), ("WALK_ANCHOR", WALK_ANCHOR, walk)):
@@ -240,14 +245,120 @@ def step_loops(asm_path, kernel=DEFAULT_KERNEL):
                     side = {x for x in body if dominates(s_, x)}
                     if not has(side, repeat):
                         common -= side
-        res[name] = stats(insts, blocks, body) + stats(insts, blocks, common)
+        res[name] = (body, common)
+    return insts, blocks, succ, dominates, res
+
+
+def step_loops(asm_path, kernel=DEFAULT_KERNEL):
+    """-> {"B_MED": (stats, histogram, stats of the common path, its histogram), "B_MEDW": (...)} of the kernel in an assembly file"""
+    insts, blocks, _, _, found = find_loops(asm_path, kernel)
+    return {name: stats(insts, blocks, body) + stats(insts, blocks, common) for name, (body, common) in found.items()}
+
+
+# --trips: the memory round trips of the common path.  A round trip is a load and the s_waitcnt that waits for it; two loads of one kind
+# with such a wait between them on some path are two DEPENDENT trips -- the second is issued only when the first has come back.
+RECORD_FILE, RECORD_ANCHOR = "integrator_dev.h", "tmp[k] = src[k];"     # cload: the scalar loads of a scene record (the step's: its medium)
+MEMORY = ("global_load", "s_load", "ds_read")
+
+
+def trips(asm_path, kernel=DEFAULT_KERNEL):
+    """-> {"B_MED": {"listing": [text lines], "a": [...], "b": [...], "c": [...]}, "B_MEDW": {...}}: the memory instructions and waits
+    of each repeat loop's common path in control-flow order from the loop head, and the instructions that break each rule (empty: kept)
+
+      a  no path leads from one global_load_dwordx4 to another through an s_waitcnt that names vmcnt
+      b  no path leads from one s_load of the medium record to another through an s_waitcnt that names lgkmcnt
+      c  every path from the loop head meets a ds_read_b128 (the logarithm's table) before the first s_load of the medium record
+
+    Paths run inside the common path and stop at a back edge -- the repeat loop's own and the waterfall's, whose second trip is another
+    medium's lookup."""
+    insts, blocks, succ, dominates, found = find_loops(asm_path, kernel)
+    with open(os.path.join(SOURCE_DIR, RECORD_FILE)) as f:
+        record_lines = {n for n, line in enumerate(f, 1) if RECORD_ANCHOR in line and not line.lstrip().startswith("//")}
+    if not record_lines:
+        raise SystemExit("no code line of %s holds RECORD_ANCHOR = %r any more: give tools/step_loop_stats.py its new text" % (RECORD_FILE, RECORD_ANCHOR))
+    def is_record(k):
+        mn, _, loc = insts[k]
+        return mn.startswith("s_load") and loc is not None and loc[0] == RECORD_FILE and loc[1] in record_lines
+    def is_gather(k):
+        return insts[k][0] == "global_load_dwordx4"
+    def waits(k, counter):
+        return insts[k][0] == "s_waitcnt" and counter in insts[k][1]
+    res = {}
+    for name, (body, common) in found.items():
+        head = next(b for b in common if all(dominates(b, x) for x in common))
+        fwd = {b: [s for s in succ[b] if s in common and not dominates(s, b)] for b in common}      # no back edges: acyclic
+        order, seen = [], set()
+        def visit(b):
+            seen.add(b)
+            for s in sorted(fwd[b], reverse=True):
+                if s not in seen:
+                    visit(s)
+            order.append(b)
+        visit(head)
+        order.reverse()                                      # reverse postorder: every block after all its predecessors
+        listing = []
+        for b in order:
+            for k in range(blocks[b][0], blocks[b][1] + 1):
+                mn, ops, loc = insts[k]
+                if mn.startswith(MEMORY) or mn.startswith("s_waitcnt"):
+                    listing.append("  block %-4d %-22s %-26s %s%s" % (b, "%s:%d" % loc if loc else "-", mn, ops, "   <- medium record" if is_record(k) else ""))
+        # one forward pass of a small state machine per rule; a block's entry states are the union of its predecessors' exit states
+        def run(start, step):
+            state, broken = {b: set() for b in order}, []
+            state[head] = {start}
+            for b in order:
+                cur = set(state[b])
+                for k in range(blocks[b][0], blocks[b][1] + 1):
+                    cur = step(k, cur, broken)
+                for s in fwd[b]:
+                    state[s] |= cur
+            return ["%s:%d %s %s" % ((insts[k][2] or ("-", 0)) + insts[k][:2]) for k in broken]
+        def two_trips(is_load, counter):                     # states: 0 no load yet, 1 a load in flight, 2 a load, then a wait for it
+            def step(k, cur, broken):
+                if is_load(k):
+                    if 2 in cur:
+                        broken.append(k)
+                    return {1}
+                if waits(k, counter):
+                    return {2 if s == 1 else s for s in cur}
+                return cur
+            return step
+        def log_first(k, cur, broken):                       # states: 0 no ds_read_b128 yet, 1 seen
+            if insts[k][0] == "ds_read_b128":
+                return {1}
+            if is_record(k) and 0 in cur:
+                broken.append(k)
+                return {1}                                   # named once: the record's first load
+            return cur
+        res[name] = {"listing": listing, "a": run(0, two_trips(is_gather, "vmcnt")), "b": run(0, two_trips(is_record, "lgkmcnt")),
+                     "c": run(0, log_first)}
     return res
 
 
-def measure(unit="kernels_lean_a.hip", kernel=DEFAULT_KERNEL, keep=None):
+def render_trips(res):
+    rows = []
+    for name in ("B_MED", "B_MEDW"):
+        r = res[name]
+        rows.append("%s, common path: memory instructions and waits in control-flow order from the loop head" % name)
+        rows += r["listing"]
+        for rule, text in (("a", "the gathers (global_load_dwordx4) go out in one round trip: no vmcnt wait between two of them"),
+                           ("b", "the medium record's s_load go out in one round trip: no lgkmcnt wait between two of them"),
+                           ("c", "the logarithm's table read (ds_read_b128) is issued before the medium record's first s_load")):
+            rows.append("  (%s) %s: %s" % (rule, text, "yes" if not r[rule] else "NO -- " + "; ".join(r[rule])))
+    return "\n".join(rows)
+
+
+@contextlib.contextmanager
+def compiled(unit="kernels_lean_a.hip", keep=None):
+    """the unit's assembly, compiled now: at `keep`, or in a temporary directory that lives as long as the block"""
     with tempfile.TemporaryDirectory(prefix="step_loop_") as tmp:
         asm = keep or os.path.join(tmp, "unit.s")
         compile_asm(unit, asm)
+        yield asm
+
+
+def measure(unit="kernels_lean_a.hip", kernel=DEFAULT_KERNEL, keep=None):
+    with compiled(unit, keep) as asm:
         return step_loops(asm, kernel)
 
 
@@ -274,8 +385,10 @@ if __name__ == "__main__":
         return None
     kernel, asm, keep = opt("--kernel") or DEFAULT_KERNEL, opt("--asm"), opt("--keep")
     SOURCE_DIR = opt("--source") or SOURCE_DIR
-    histogram = "--histogram" in argv
-    argv = [a for a in argv if a != "--histogram"]
+    histogram, want_trips = "--histogram" in argv, "--trips" in argv
+    argv = [a for a in argv if a not in ("--histogram", "--trips")]
     unit = argv[0] if argv else "kernels_lean_a.hip"
-    res = step_loops(asm, kernel) if asm else measure(unit, kernel, keep)
-    print(render(res, unit, kernel, histogram))
+    with (contextlib.nullcontext(asm) if asm else compiled(unit, keep)) as asm:
+        print(render(step_loops(asm, kernel), unit, kernel, histogram))
+        if want_trips:
+            print(render_trips(trips(asm, kernel)))
