@@ -29,6 +29,7 @@ SHAPE_RECTANGLE, SHAPE_CUBE, SHAPE_SPHERE, SHAPE_MESH, SHAPE_DISK = 0, 1, 2, 3, 
 # instanced geometry on the existing record (mtsamd.h): a group's face_count = its member count, the members follow it; an instance's
 # vertex_count = the index of its group's record
 SHAPE_SHAPEGROUP, SHAPE_INSTANCE = 5, 6
+SHAPE_CONE = 8                   # 7 stays unassigned (mtsamd.h); the cone reads to_world and flip_normals
 EMITTER_DIRECTIONAL, EMITTER_AREA, EMITTER_CONSTANT, EMITTER_POINT = 0, 1, 2, 3
 SENSOR_PERSPECTIVE, SENSOR_DISTANT, SENSOR_MRADIANCEMETER, SENSOR_MDISTANT, SENSOR_DISTANTFLUX = 0, 1, 2, 3, 4
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1

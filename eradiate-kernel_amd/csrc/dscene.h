@@ -84,7 +84,8 @@ struct DShape {
     float frame_s[3], frame_t[3], frame_n[3];     // rectangle.cpp:66-74
     float inv_surface_area;
     float surface_area;                           // disk (disk.cpp:108-111)
-    float center[3], radius;                      // sphere
+    float center[3], radius;                      // sphere; cone (cone.cpp:98-108): center = the tip in object space (0, 0, length), radius = that of the
+                                                  // base circle; to_world / to_object of a cone are rigid (rotation + translation)
     int32_t flip_normals;
     int32_t vertex_offset, face_offset;           // into the scene-wide mesh arrays
     int32_t has_normals, has_texcoords;
@@ -97,6 +98,7 @@ struct DShape {
 struct DPrim { int32_t shape, index; };
 // Everything the primitive-list walk needs about one primitive in ONE 64-byte record (one scalar load per primitive instead of a
 // chain prim -> shape -> geometry): triangle: p0, e1, e2; rectangle: rows 0..2 of to_object; sphere: center, radius.
+// cone (read by the INST kernels only): rows 0..2 of its rigid to_object, and the bits of radius / length in index / pad (its one primitive is primitive 0).
 struct DWalkPrim { int32_t type, shape, index, pad; float f[12]; };
 
 // Instanced geometry (shapes/shapegroup.cpp, shapes/instance.cpp, librender/shapegroup.cpp; read by the INST kernels only, kernels.hip: render_kernel_inst).

@@ -226,6 +226,48 @@ DEV_NOINLINE float sphere_intersect_v(float cx, float cy, float cz, float radius
     bool active = found && !out_bounds && !in_bounds;
     return active ? (x0 < mint ? (float) x1 : (float) x0) : pm_inf();
 }
+// shapes/cone.cpp:245-294 (== ray_test, :296-338) in double precision + core/math.h:371-411: the cone with its base circle of radius r in
+// z = 0 and its tip at (0, 0, l) of object space.  The ray goes to object space in fp32 through the record's rigid to_object (direction not
+// renormalised), then widens.  A real function, reachable from the INST kernels alone (prim_intersect_lane<true>): no other kernel holds it.
+// It fetches the walk record itself (DWalkPrim: rows 0..2 of the rigid to_object in f, the bits of radius / length in index / pad) and takes
+// the ray as origin, direction and window: ten argument registers, so that the call costs its callers -- which test far more triangles
+// than cones -- as little as the sphere's.
+DEV_NOINLINE float cone_intersect_v(const DWalkPrim *rec, F3 ro, F3 rd, float rmint, float rmaxt) {
+    typedef int mts_int4 __attribute__((ext_vector_type(4)));
+    const MTS_GLOBAL_AS mts_int4 *q = (const MTS_GLOBAL_AS mts_int4 *) as_global(rec);
+    const mts_int4 hd = q[0], g0 = q[1], g1 = q[2], g2 = q[3];
+    const float to_object[12] = { __int_as_float(g0.x), __int_as_float(g0.y), __int_as_float(g0.z), __int_as_float(g0.w),
+                                  __int_as_float(g1.x), __int_as_float(g1.y), __int_as_float(g1.z), __int_as_float(g1.w),
+                                  __int_as_float(g2.x), __int_as_float(g2.y), __int_as_float(g2.z), __int_as_float(g2.w) };
+    const float radius = __int_as_float(hd.z), length_f = __int_as_float(hd.w);
+    const F3 o = mat_point_affine(to_object, ro), d = mat_vector(to_object, rd);
+    double mint = rmint, maxt = rmaxt;
+    double ox = o.x, oy = o.y, oz = o.z, dx = d.x, dy = d.y, dz = d.z;
+    const double length = (double) length_f;
+    double k = (double) radius / length;
+    k *= k;
+    double A = dx * dx + dy * dy - k * (dz * dz);
+    double B = 2.0 * (dx * ox + dy * oy - k * dz * (oz - length));
+    double Cc = ox * ox + oy * oy - k * ((oz - length) * (oz - length));
+    bool linear_case = A == 0.0, valid_linear = linear_case && B != 0.0;
+    double x0 = -Cc / B, x1 = x0;
+    double discrim = pm_fma_d(B, B, -(4.0 * A * Cc));
+    bool valid_quadratic = !linear_case && discrim >= 0.0;
+    if (valid_quadratic) {
+        double sqrt_discrim = __builtin_sqrt(discrim);
+        double temp = -0.5 * (B + __builtin_copysign(sqrt_discrim, B));
+        double x0p = temp / A, x1p = Cc / temp;
+        x0 = x1p < x0p ? x1p : x0p; x1 = x0p < x1p ? x1p : x0p;
+    }
+    bool found = valid_linear || valid_quadratic;
+    bool out_bounds = !(x0 <= maxt && x1 >= mint);            // the cone does not meet the segment (NaN-aware)
+    bool in_bounds = x0 < mint && x1 > maxt;                  // "the cone fully contains the segment"
+    double z_near = oz + dz * x0, z_far = oz + dz * x1;
+    bool shadow_near = length - z_near <= 0.0, shadow_far = length - z_far <= 0.0;     // a root on the mirror nappe beyond the tip
+    bool near_ok = z_near >= 0.0 && x0 >= mint && !shadow_near;
+    bool active = found && !out_bounds && !in_bounds && (near_ok || (z_far >= 0.0 && x1 <= maxt && !shadow_far));
+    return active ? (near_ok ? (float) x0 : (!shadow_far ? (float) x1 : pm_inf())) : pm_inf();
+}
 
 // ---------------------------------------------------------------- scene traversal
 // Closest hit with the semantics of ShapeKDTree::ray_intersect_scalar (render/kdtree.h:2078-2171):
@@ -238,6 +280,9 @@ struct BvhArgs { const float *nodes; const int32_t *leaf_prims; int32_t node_cou
                  const float *lds_nodes; int32_t lds_count; };
 // One primitive addressed per lane (BVH leaves): the same tests as the scalar walk on the same 64-byte record, fetched with
 // four 16-byte vector loads (no prim -> shape -> geometry chain of dependent loads).
+// CONE: the caller may meet cones (inst_intersect alone: a scene with a cone renders in the INST kernels); their record keeps the bits
+// of radius / length where the others keep index / pad, and the one primitive of a cone is primitive 0.
+template <bool CONE = false>
 DEV float prim_intersect_lane(const BvhArgs &a, int pi, const DRay &ray, F2 &uv, int &shape, int &index) {
     typedef int mts_int4 __attribute__((ext_vector_type(4)));
     const MTS_GLOBAL_AS mts_int4 *rec = (const MTS_GLOBAL_AS mts_int4 *) as_global(a.walk + pi);
@@ -250,6 +295,7 @@ DEV float prim_intersect_lane(const BvhArgs &a, int pi, const DRay &ray, F2 &uv,
     if (hd.x == MTS_SHAPE_RECTANGLE) return rectangle_intersect(f, ray, uv);
     if (hd.x == MTS_SHAPE_DISK) return disk_intersect(f, ray, uv);
     if (hd.x == MTS_SHAPE_SPHERE) return sphere_intersect(f, f[3], ray);
+    if constexpr (CONE) if (hd.x == MTS_SHAPE_CONE) { index = 0; return cone_intersect_v(a.walk + pi, ray.o, ray.d, ray.mint, ray.maxt); }
     TriRec T;
     for (int k = 0; k < 9; ++k) T.v[k] = f[k];
     return triangle_intersect(T, ray, uv);
@@ -348,7 +394,7 @@ DEV_NOINLINE Hit inst_intersect(const InstArgs a, DRay wray) {
                 continue;
             }
             F2 uv; int shape, index;
-            const float t = prim_intersect_lane(pa, pi, ray, uv, shape, index);
+            const float t = prim_intersect_lane<true>(pa, pi, ray, uv, shape, index);
             const int tp = inst >= 0 ? top_pi : pi, bp = inst >= 0 ? pi : -1;
             // the tests accept t <= ray.maxt == h.t: equal t goes to the later primitive, scene level first
             if (t != pm_inf() && (t < h.t || tp > best_top || (tp == best_top && bp > best_bot))) {
@@ -447,9 +493,31 @@ DEV void tri_attr_load(const DScene &sc, const DShape &s, const Hit &h, bool tab
     }
 }
 
-// Hit point: rectangle.cpp:181-185, mesh.cpp:470-483, sphere.cpp:325-327
-template <bool TAB = false>
+// cone.cpp:370-379 from the object-space point `local`: dp_du = 2 pi (-y, x, 0) and dp_dv = (-x / (1 - v), -y / (1 - v), l), v = z / l,
+// through the cone's rigid to_world; n = normalize(dp_du x dp_dv), turned by flip_normals.  (INST kernels only.)
+DEV F3 cone_normal(const DShape &s, F3 local, F3 &dp_du) {
+    const float length = s.center[2], v = local.z / length, inv = 1.f - v;
+    const F3 du = f3(-local.y, local.x, 0.f) * (2.f * MTS_PI), dv = f3(-local.x / inv, -local.y / inv, length);
+    dp_du = mat_vector(s.to_world.m, du);
+    F3 n = normalize(cross(dp_du, mat_vector(s.to_world.m, dv)));
+    if (s.flip_normals) n = -n;
+    return n;
+}
+
+// Hit point: rectangle.cpp:181-185, mesh.cpp:470-483, sphere.cpp:325-327, cone.cpp:361-383 (INST instantiations only)
+template <bool TAB = false, bool INST = false>
 DEV void hit_point(const DScene &sc, const DShape &s, const DRay &ray, Hit &h, bool tab = false) {
+    if constexpr (INST) if (s.type == MTS_SHAPE_CONE) {
+        // local = to_object * ray(t), from the unshifted point; n from local; THEN the point moves along n onto the cone.  The reference
+        // shifts along the normal after flip_normals has turned it, so a flipped cone moves its point AWAY from the surface by the
+        // distance an unflipped one moves it towards it (cone.cpp:378-383): restated as it is, quirk included.
+        const F3 p = ray_at(ray, h.t), local = mat_point_affine(s.to_object.m, p);
+        F3 dp_du; const F3 n = cone_normal(s, local, dp_du);
+        const float length = s.center[2];
+        h.p = p + n * (s.radius * (length - local.z) / length - pm_sqrt(pm_fma(local.y, local.y, local.x * local.x)));
+        h.uv.x = local.x; h.uv.y = local.y; h.prim = (int32_t) pm_bits(local.z);   // keep the object-space point for complete_surface() / surface_uv()
+        return;
+    }
     if (s.type == MTS_SHAPE_RECTANGLE || s.type == MTS_SHAPE_DISK) {                          // rectangle.cpp:181-185 == disk.cpp:186-188
         F3 p = ray_at(ray, h.t), n = f3(s.frame_n);
         float dist = dot(f3(s.to_world.m[3], s.to_world.m[7], s.to_world.m[11]) - p, n);
@@ -478,7 +546,7 @@ DEV Hit ray_intersect(const DScene &sc, const DRay &ray) {
         DRay gray = ray;
         if (inst >= 0) { float O[12]; instance_rows(sc, inst, 32, O); gray = make_ray(mat_point_affine(O, ray.o), mat_vector(O, ray.d), ray.mint, ray.maxt); }
         WATERFALL_BEGIN(hit_shape<true>(h), su)
-            hit_point<TAB>(sc, cload(sc.shapes + su), gray, h, tab);
+            hit_point<TAB, true>(sc, cload(sc.shapes + su), gray, h, tab);
         WATERFALL_END
         if (inst >= 0) { float W[12]; instance_rows(sc, inst, 0, W); h.p = mat_point_affine(W, h.p); }
       } else {
@@ -517,6 +585,9 @@ DEV void complete_surface(const DScene &sc, const DShape &s, const Hit &h, F3 d,
         dp_du = mat_vector(s.to_world.m, f3(-local.y, local.x, 0.f)) * (2.f * MTS_PI);
         if (s.flip_normals) shn = -shn;
         sf.n = shn;
+    } else if (INST && s.type == MTS_SHAPE_CONE) {
+        // hit_point() parked the object-space point to_object * ray(t) in (uv.x, uv.y, bits(prim)): object space, so the same inside an instance
+        if constexpr (INST) { shn = cone_normal(s, f3(h.uv.x, h.uv.y, pm_from_bits((uint32_t) h.prim)), dp_du); sf.n = shn; }
     } else {
         float A[9]; tri_attr_load<TAB, 9>(sc, s, h, tab, 0, A);
         F3 p0 = f3(A), p1 = f3(A + 3), p2 = f3(A + 6);
@@ -1287,7 +1358,13 @@ DEV F2 surface_uv(const DScene &sc, const DShape &s, const Hit &h) {
         float phi = atan2f(local.y, local.x);
         if (phi < 0.f) phi += 2.f * MTS_PI;
         uv.x = phi * MTS_INV_TWO_PI; uv.y = theta * MTS_INV_PI;
-    } else {                                                                                  // mesh.cpp:490-497 (cube: a mesh with texcoords)
+    } else if (INST && s.type == MTS_SHAPE_CONE) {                                            // cone.cpp:365-368, from the parked object-space point
+        if constexpr (INST) {
+            float phi = atan2f(h.uv.y, h.uv.x);
+            if (phi < 0.f) phi += 2.f * MTS_PI;
+            uv.x = phi * MTS_INV_TWO_PI; uv.y = pm_from_bits((uint32_t) h.prim) / s.center[2];
+        }
+    } else {                                                                                // mesh.cpp:490-497 (cube: a mesh with texcoords)
         const float b1 = h.uv.x, b2 = h.uv.y, b0 = 1.f - b1 - b2;
         uv.x = b1; uv.y = b2;
         if (s.has_texcoords) {

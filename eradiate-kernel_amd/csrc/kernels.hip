@@ -520,7 +520,7 @@ __global__ void __launch_bounds__(256) intersect_kernel_inst(DScene sc, int32_t 
     if (hit_valid(h)) {
         Surf sf; complete_surface<true>(sc, h, ray.d, sf); nn = sf.n;
         shape = hit_shape<true>(h);
-        prim = sc.shapes[shape].type == MTS_SHAPE_SPHERE ? 0 : h.prim;
+        prim = sc.shapes[shape].type == MTS_SHAPE_SPHERE || sc.shapes[shape].type == MTS_SHAPE_CONE ? 0 : h.prim;     // both park a float's bits there
     }
     out_t[i] = h.t; out_shape[i] = shape; out_prim[i] = prim;
     out_p[3 * i] = h.p.x; out_p[3 * i + 1] = h.p.y; out_p[3 * i + 2] = h.p.z;

@@ -17,7 +17,7 @@ struct RenderArgs {
     hipStream_t stream;
     bool moment;                                    // the `moment` integrator's eleven-channel film (general rgb / mono unit only; variant = kv::moment_variant())
     bool textured;                                  // the scene has textures, a blendbsdf or a twosided (general rgb / mono unit only; variant = kv::textured_variant())
-    bool instanced;                                 // the scene has instances (DScene::instances): the INST kernels of the general rgb / mono unit; `textured` is set as well
+    bool instanced;                                 // the scene has instances (DScene::instances) or a cone: the INST kernels of the general rgb / mono unit; `textured` is set as well
 };
 typedef hipError_t (*RenderLauncher)(const RenderArgs &);
 size_t render_workspace_floats(uint64_t paths, int variant);

@@ -69,7 +69,17 @@ static uint32_t bsdf_flags(int type) {
     return F_GlossyReflection | F_FrontSide;                                               // rpv.cpp:66
 }
 
-// Shape constructors: rectangle.cpp:59-74, cube.cpp:70-112 (+ mesh.cpp), sphere.cpp:80-105
+// cone.cpp:113-124: the box of the two end circles of radius r -- at the tip as well, where the cone has none: restated, not tightened
+static DBBox cone_bbox(const DShape &s) {
+    const F3 x1 = mat_vector(s.to_world.m, f3(s.radius, 0.f, 0.f)), x2 = mat_vector(s.to_world.m, f3(0.f, s.radius, 0.f));
+    const F3 x = f3(pm_sqrt(x1.x * x1.x + x2.x * x2.x), pm_sqrt(x1.y * x1.y + x2.y * x2.y), pm_sqrt(x1.z * x1.z + x2.z * x2.z));
+    const F3 p0 = mat_point_affine(s.to_world.m, f3s(0.f)), p1 = mat_point_affine(s.to_world.m, f3(s.center));
+    DBBox b; bbox_reset(b);
+    bbox_expand(b, p0 - x); bbox_expand(b, p1 - x); bbox_expand(b, p0 + x); bbox_expand(b, p1 + x);
+    return b;
+}
+
+// Shape constructors: rectangle.cpp:59-74, cube.cpp:70-112 (+ mesh.cpp), sphere.cpp:80-105, cone.cpp:79-124
 static DShape build_shape(const mts_shape &d, HostScene &hs, DBBox &shape_bbox, int &prim_count) {
     DShape s; memset(&s, 0, sizeof(s));
     s.type = d.type;
@@ -156,6 +166,36 @@ static DShape build_shape(const mts_shape &d, HostScene &hs, DBBox &shape_bbox, 
         s.inv_surface_area = pm_rcp(4.f * MTS_PI * s.radius * s.radius);
         store3(shape_bbox.min, center - f3s(s.radius)); store3(shape_bbox.max, center + f3s(s.radius));
         prim_count = 1;
+    } else if (d.type == MTS_SHAPE_CONE) {                                                     // cone.cpp:79-124,187-190
+        // to_world = R * diag(r, r, l) + translation: r, l and R recovered from the columns, as the sphere's above (the reference uses
+        // enoki's polar decomposition; identical for such a matrix).  The reference only warns about shear and unequal x / y scale and
+        // goes on with a record that describes no cone; a mirrored matrix gives it a negative radius or length.  All three are refused here.
+        const DXf &tw = s.to_world;
+        F3 c0 = f3(tw.m[0], tw.m[4], tw.m[8]), c1 = f3(tw.m[1], tw.m[5], tw.m[9]), c2 = f3(tw.m[2], tw.m[6], tw.m[10]);
+        float r0 = norm(c0), r1 = norm(c1), l = norm(c2);
+        if (!(r0 > 0.f && r1 > 0.f && l > 0.f))
+            throw std::runtime_error("cone: 'to_world' must scale the x / y axes by a radius > 0 and the z axis by a length > 0");
+        if (pm_abs(dot(c0, c1)) > 1e-6f * r0 * r0 || pm_abs(dot(c0, c2)) > 1e-6f * r0 * l || pm_abs(dot(c1, c2)) > 1e-6f * r0 * l)
+            throw std::runtime_error("cone: 'to_world' transform shouldn't contain any shearing! (refused by this backend: the axes of the cone must stay orthogonal)");
+        if (pm_abs(r0 - r1) > 1e-6f * r0)
+            throw std::runtime_error("cone: 'to_world' transform shouldn't contain non-uniform scaling along the X and Y axes! (refused by this backend)");
+        if (dot(cross(c0, c1), c2) < 0.f)
+            throw std::runtime_error("cone: 'to_world' transform shouldn't mirror the cone (negative determinant; refused by this backend)");
+        s.radius = r0; s.center[0] = s.center[1] = 0.f; s.center[2] = l;
+        F3 q0 = c0 / r0, q1 = c1 / r1, q2 = c2 / l, tr = f3(tw.m[3], tw.m[7], tw.m[11]);
+        float R[9] = { q0.x, q1.x, q2.x, q0.y, q1.y, q2.y, q0.z, q1.z, q2.z };
+        DXf rec = xf_identity();                                                                 // transform_compose(1, Q, T): rigid
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) rec.m[r * 4 + c] = R[r * 3 + c];
+        rec.m[3] = tr.x; rec.m[7] = tr.y; rec.m[11] = tr.z;
+        float invm[16]; memset(invm, 0, sizeof(invm));
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) invm[r * 4 + c] = R[c * 3 + r];
+        for (int r = 0; r < 3; ++r) invm[r * 4 + 3] = -(invm[r * 4] * tr.x + invm[r * 4 + 1] * tr.y + invm[r * 4 + 2] * tr.z);
+        invm[15] = 1.f;
+        mat_transpose(invm, rec.it);
+        s.to_world = rec; s.to_object = xf_inverse(rec);
+        s.inv_surface_area = pm_rcp(MTS_PI * s.radius * pm_sqrt(s.radius * s.radius + l * l));
+        shape_bbox = cone_bbox(s);
+        prim_count = 1;
     } else throw std::runtime_error("unknown shape type");
     return s;
 }
@@ -195,7 +235,7 @@ static DXf xf_perspective(float fov, float near_, float far_) {
 // `se`: the sensor that renders -- a distant sensor's own target / origin shape counts as the scene's shapes do, so the traits are
 // those of a (scene, sensor) pair: HostScene::traits for sensor 0, host_sensor() for any of them.
 static int scene_traits(const HostScene &hs, bool spectral, const DSensor &se) {
-    if (!hs.instances.empty()) return 0;                                // an instanced scene promises nothing either: the INST kernels are the general rgb / mono unit's
+    if (!hs.instances.empty() || hs.has_cone) return 0;                 // an instanced scene, or one with a cone, promises nothing either: the INST kernels are the general rgb / mono unit's
     if (!hs.bsdf_tex.empty()) return 0;                                 // a scene with textures, a blendbsdf or a twosided promises nothing: the general rgb / mono unit holds the TEX kernels
     int tr = 0;
     bool media = !hs.media.empty();
@@ -636,9 +676,9 @@ static void build_textures(const mts_scene_desc &d, bool spectral, HostScene &hs
         // a blend or a twosided renders in the TEX instantiations, which read the index table: all -1 under a constant weight and plain children
         for (int i = 0; i < d.bsdf_count; ++i)
             if (d.bsdfs[i].type == MTS_BSDF_BLEND || d.bsdfs[i].type == MTS_BSDF_TWOSIDED) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
-        // so does an instanced scene: the INST kernels are TEX instantiations
+        // so does an instanced scene, and one with a cone: the INST kernels are TEX instantiations
         for (int i = 0; i < d.shape_count; ++i)
-            if (d.shapes[i].type == MTS_SHAPE_INSTANCE) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
+            if (d.shapes[i].type == MTS_SHAPE_INSTANCE || d.shapes[i].type == MTS_SHAPE_CONE) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
         return;
     }
     // rgb texels need the sRGB upsampling model (bitmap.cpp:169-178), whose data this backend has not got -- as for three-channel grids
@@ -685,6 +725,7 @@ static void add_shape(const mts_scene_desc &d, int i, const DefaultBsdfs &defaul
         DWalkPrim w; memset(&w, 0, sizeof(w)); w.type = ds.type; w.shape = i; w.index = k;
         if (ds.type == MTS_SHAPE_RECTANGLE || ds.type == MTS_SHAPE_DISK) memcpy(w.f, ds.to_object.m, 48);
         else if (ds.type == MTS_SHAPE_SPHERE) { memcpy(w.f, ds.center, 12); w.f[3] = ds.radius; }
+        else if (ds.type == MTS_SHAPE_CONE) { memcpy(w.f, ds.to_object.m, 48); memcpy(&w.index, &ds.radius, 4); memcpy(&w.pad, &ds.center[2], 4); }      // dscene.h: DWalkPrim
         else memcpy(w.f, rec, 36);
         hs.walk.push_back(w);
         hs.area_pmf.push_back(triangles ? 0.5f * norm(cross(f3(rec + 3), f3(rec + 6))) : 0.f);      // mesh.h:108-116: face area
@@ -747,6 +788,24 @@ static std::vector<int32_t> validate_instancing(const mts_scene_desc &d, bool sp
     if (instances > MTS_INST_MAX_INSTANCES)
         throw std::runtime_error("at most " + std::to_string(MTS_INST_MAX_INSTANCES) + " instances per scene (the hit encoding), this one has " + std::to_string(instances));
     return member_of;
+}
+// What a description with a cone (MTS_SHAPE_CONE, plain or a group's member) can get wrong as a scene: such a scene renders in the INST
+// kernels, so it shares their limits.  The cone's own transform is checked where its record is built (build_shape).
+static bool validate_cones(const mts_scene_desc &d, bool spectral) {
+    bool any = false;
+    for (int i = 0; i < d.shape_count; ++i) any = any || d.shapes[i].type == MTS_SHAPE_CONE;
+    if (!any) return false;
+    if (spectral) throw std::runtime_error("cone shapes are not supported in the spectral variant");
+    if (d.integrator.moment != 0) throw std::runtime_error("cone shapes are not supported inside a moment integrator's scene");
+    if (d.shape_count > MTS_INST_MAX_SHAPES)
+        throw std::runtime_error("a scene with a cone holds at most " + std::to_string(MTS_INST_MAX_SHAPES) + " shape records (shape_count = " + std::to_string(d.shape_count) + "): the hit encoding keeps the shape in " + std::to_string(MTS_INST_SHAPE_BITS) + " bits");
+    for (int i = 0; i < d.shape_count; ++i)
+        if (d.shapes[i].type == MTS_SHAPE_CONE && d.shapes[i].emitter != -1)
+            throw std::runtime_error("shape " + std::to_string(i) + ": an area emitter on a cone is not supported on this backend (the cone's sample_position is not built)");
+    for (int i = 0; i < d.emitter_count; ++i)
+        if (d.emitters[i].type == MTS_EMITTER_AREA && d.emitters[i].shape >= 0 && d.emitters[i].shape < d.shape_count && d.shapes[d.emitters[i].shape].type == MTS_SHAPE_CONE)
+            throw std::runtime_error("emitter " + std::to_string(i) + ": its shape " + std::to_string(d.emitters[i].shape) + " is a cone: an area emitter on a cone is not supported on this backend (the cone's sample_position is not built)");
+    return true;
 }
 // A group's bounding box: that of its acceleration structure, the union of its members' (shapegroup.cpp; group space)
 static DBBox group_bbox(const mts_scene_desc &d, int g) {
@@ -967,6 +1026,7 @@ HostScene *build_host_scene(const mts_scene_desc *d) {
     const bool spectral = d->integrator.spectral != 0;
     if (d->shape_count < 0 || (d->shape_count > 0 && !d->shapes)) throw std::runtime_error("shapes: a negative count, or records missing");
     const std::vector<int32_t> member_of = validate_instancing(*d, spectral);      // groups and instances, ahead of every record
+    hs.has_cone = validate_cones(*d, spectral);
     if (spectral) build_spectra(*d, hs);
     build_volumes(*d, spectral, hs);
     build_phases(*d, hs);
@@ -1076,7 +1136,9 @@ static int32_t build_bvh_level(HostScene &hs, int first, int n, F3 diag, int thr
             for (int k = 0; k < 4; ++k) add(mat_point_affine(s.to_world.m, f3((k & 1) ? 1.f : -1.f, (k & 2) ? 1.f : -1.f, 0.f)));
         } else if (s.type == MTS_SHAPE_SPHERE) {
             add(f3(s.center) - f3s(s.radius)); add(f3(s.center) + f3s(s.radius));
-        } else if (s.type == MTS_SHAPE_INSTANCE) {                             // the instance's own box (instance.cpp:81-92)
+        } else if (s.type == MTS_SHAPE_CONE) {
+            const DBBox cb = cone_bbox(s); add(f3(cb.min)); add(f3(cb.max));
+        } else if (s.type == MTS_SHAPE_INSTANCE) {                            // the instance's own box (instance.cpp:81-92)
             const DBBox &ib = hs.instance_boxes[(size_t) hs.walk[(size_t) (first + i)].shape];
             // an instance of an empty group has no box (instance.cpp:84-86): it gets the point of its translation, finite, so that
             // no NaN centroid reaches the builder; the traversal finds nothing inside it
@@ -1164,7 +1226,9 @@ void upload_host_scene(HostScene &hs, int device) {
         sc.textures = upload(hs, hs.textures); sc.bsdf_tex = upload(hs, hs.bsdf_tex);
     }
     sc.instances = nullptr; sc.groups = nullptr;
-    if (!hs.instances.empty()) { sc.instances = upload(hs, hs.instances); sc.groups = upload(hs, hs.groups); }
+    // (a scene with a cone and no instance: both arrays empty, both pointers set -- a non-NULL `instances` is what sends mts_sample and
+    // mts_ray_intersect to the INST kernels, kernels.hip: launch_sample; no walk record names an instance or a group)
+    if (!hs.instances.empty() || hs.has_cone) { sc.instances = upload(hs, hs.instances); sc.groups = upload(hs, hs.groups); }
     sc.spectra = nullptr; sc.bsdf_sp = nullptr; sc.emitter_sp = nullptr; sc.volume_sp = nullptr; sc.cie = nullptr;
     if (hs.integrator.spectral) {
         for (size_t i = 0; i < hs.spectra.size(); ++i)

@@ -57,6 +57,7 @@ struct HostScene {
     // shape records; instance_boxes: the world-space box of each instance (instance.cpp:81-92), by its index in `instances` -- what
     // build_bvh puts around the instance's primitive (DWalkPrim::shape of that primitive is the index)
     std::vector<DInstance> instances; std::vector<DGroup> groups; std::vector<DBBox> instance_boxes;
+    bool has_cone = false;                           // a shape record is an MTS_SHAPE_CONE (plain or a group's member): the scene renders in the INST kernels as an instanced one does
     std::vector<HostSensor> extra_sensors;           // sensors 1, 2, ... in the order they were added; rendering one never writes `scene`
     std::atomic<int> sensor_count{1};                // 1 + extra_sensors.size(), readable without the handle's mutex
     std::vector<void *> device_allocs;

@@ -481,7 +481,22 @@ def _tab_values(vals):
     return np.array([float(s) for s in vals.replace(",", " ").split()], dtype=np.float32)
 
 
-SHAPE_PLUGINS = ("rectangle", "cube", "sphere", "mesh", "obj", "ply", "disk")
+SHAPE_PLUGINS = ("rectangle", "cube", "sphere", "mesh", "obj", "ply", "disk", "cone")
+
+
+def _check_cone_transform(m, where):
+    """What the library refuses of a cone's to_world (scene_host.cpp: build_shape), said where the cone is declared: the linear part must
+    be R * diag(r, r, l) with R a rotation.  The reference (cone.cpp:87-104) only warns and goes on with a record that describes no cone."""
+    c0, c1, c2 = (m[:3, k].astype(np.float64) for k in range(3))
+    r0, r1, l = (float(np.linalg.norm(c)) for c in (c0, c1, c2))
+    if not (r0 > 0 and r1 > 0 and l > 0):
+        raise RuntimeError("cone \"%s\": 'to_world' must scale the x / y axes by a radius > 0 and the z axis by a length > 0" % where)
+    if abs(c0 @ c1) > 1e-6 * r0 * r0 or abs(c0 @ c2) > 1e-6 * r0 * l or abs(c1 @ c2) > 1e-6 * r0 * l:
+        raise RuntimeError("cone \"%s\": 'to_world' transform shouldn't contain any shearing! (refused by this backend: the axes of the cone must stay orthogonal)" % where)
+    if abs(r0 - r1) > 1e-6 * r0:
+        raise RuntimeError("cone \"%s\": 'to_world' transform shouldn't contain non-uniform scaling along the X and Y axes! (refused by this backend)" % where)
+    if np.cross(c0, c1) @ c2 < 0:
+        raise RuntimeError("cone \"%s\": 'to_world' transform shouldn't mirror the cone (negative determinant; refused by this backend)" % where)
 SAMPLING_INTEGRATORS = {"path": A.INTEGRATOR_PATH, "volpath": A.INTEGRATOR_VOLPATH, "volpathmis": A.INTEGRATOR_VOLPATHMIS}
 
 
@@ -515,6 +530,7 @@ class SceneBuilder:
         self.blends = []         # where each blendbsdf sits (what a refusal of the whole scene names)
         self.twosided = []       # and each twosided
         self.groups, self.instanced = [], []     # where each shapegroup / instance sits
+        self.cones = []          # and each cone
 
     def _colour_node(self, kind, index, field, where, spectrum=-1, emitter=False):
         return ("spectrum", spectrum) if _SPECTRAL is not None else ("colour", kind, index, field, where, emitter)
@@ -925,6 +941,11 @@ class SceneBuilder:
             rec.flip_normals = int(bool(p.get("flip_normals", False)))
             rec.center[:] = tuple(float(x) for x in np.asarray(p.get("center", (0, 0, 0)), dtype=np.float32))
             rec.radius = float(p.get("radius", 1.0))
+        elif p.type == "cone":                                           # src/shapes/cone.cpp:79-85: to_world and flip_normals, nothing else --
+            rec.type = A.SHAPE_CONE                                      # "p0", "p1" and "radius" of its documentation are never queried
+            rec.flip_normals = int(bool(p.get("flip_normals", False)))
+            _check_cone_transform(np.array(list(rec.to_world.matrix), np.float32).reshape(4, 4), where)
+            self.cones.append(where)
         elif p.type in ("mesh", "obj", "ply"):
             # "mesh": in-memory triangle mesh (extension); "obj" / "ply": src/shapes/obj.cpp, src/shapes/ply.cpp via mesh_io.py,
             # which applies to_world at load time like the reference's loaders
@@ -987,6 +1008,8 @@ class SceneBuilder:
 
     def add_shape(self, d, where):
         rec, emitter_dict = self.make_shape(d, where)
+        if emitter_dict is not None and rec.type == A.SHAPE_CONE:
+            raise RuntimeError("\"%s\": an \"area\" emitter on a cone is not supported by this backend (the cone's sample_position is not built)" % where)
         self.shapes.append(rec)
         idx = len(self.shapes) - 1
         if emitter_dict is not None:
@@ -1534,6 +1557,10 @@ class SceneBuilder:
             raise RuntimeError("\"shapegroup\" / \"instance\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.groups + self.instanced))
         if (self.groups or self.instanced) and self.spectral:
             raise RuntimeError("\"shapegroup\" / \"instance\" (%s) is not supported in the gpu_spectral variant" % ", ".join(self.groups + self.instanced))
+        if self.cones and self.integrator.moment:
+            raise RuntimeError("\"cone\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.cones))
+        if self.cones and self.spectral:
+            raise RuntimeError("\"cone\" (%s) is not supported in the gpu_spectral variant" % ", ".join(self.cones))
         if self.twosided and self.integrator.moment:
             raise RuntimeError("\"twosided\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.twosided))
         return self.finish()

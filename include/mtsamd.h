@@ -165,7 +165,7 @@ typedef struct mts_texture {
  *      existing record (a library from before them refuses both as "unknown shape type"):
  *      MTS_SHAPE_SHAPEGROUP   shapegroup.cpp: a group of shapes that are NOT part of the scene's own geometry (scene.cpp:36-41).
  *        face_count           the number M >= 0 of its members: the M records that follow it directly in mts_scene_desc.shapes.  A
- *                             member is a rectangle, cube, sphere, mesh or disk with its own to_world (group space = the members'
+ *                             member is a rectangle, cube, sphere, mesh, disk or cone with its own to_world (group space = the members'
  *                             to_world and nothing else) and its own bsdf; it carries no emitter ("Instancing of emitters is not
  *                             supported") and, a limit of this backend, no interior_medium / exterior_medium; it is neither a
  *                             shapegroup ("Nested ShapeGroup is not permitted") nor an instance ("Nested instancing is not
@@ -177,9 +177,19 @@ typedef struct mts_texture {
  *                             bsdf, interior_medium, exterior_medium and emitter must be -1: material and media are the members'.
  *      An area emitter's `shape` names neither a group, a member nor an instance.  Hits report a member's index in `shapes`.
  *      Limits: at most 1024 shape records in an instanced scene and 2^21 - 2 instances (what a hit's packed shape word holds).
- *      The value 7 is the first unassigned one and stays refused as "unknown shape type". */
+ *      MTS_SHAPE_CONE         cone.cpp (rgb / mono variants; not with mts_integrator.moment): the cone with its base circle of radius r
+ *                             in the plane z = 0 and its tip at (0, 0, l) of object space; a plain shape of the scene or a member of a
+ *                             shapegroup.  No new field either:
+ *        to_world             its linear part must be R * diag(r, r, l) with R a rotation, r, l > 0: shear, unequal x / y scale and a
+ *                             mirrored linear part are refused (the reference warns and goes on with a meaningless record).
+ *        flip_normals         normals point inwards.
+ *                             center and radius are not read.  A cone carries no area emitter and is no sensor's target or origin
+ *                             shape (limits of this backend).  A scene that holds a cone anywhere renders in the INST kernels and
+ *                             shares the limit of 1024 shape records.  A hit on a cone reports prim = 0.
+ *      The value 7 is left unassigned -- the test suite probes it as the first unknown type -- and stays refused as "unknown shape
+ *      type", as does every value above 8. */
 enum { MTS_SHAPE_RECTANGLE = 0, MTS_SHAPE_CUBE = 1, MTS_SHAPE_SPHERE = 2, MTS_SHAPE_MESH = 3, MTS_SHAPE_DISK = 4 /* src/shapes/disk.cpp */,
-       MTS_SHAPE_SHAPEGROUP = 5, MTS_SHAPE_INSTANCE = 6 };
+       MTS_SHAPE_SHAPEGROUP = 5, MTS_SHAPE_INSTANCE = 6, MTS_SHAPE_CONE = 8 /* src/shapes/cone.cpp */ };
 typedef struct mts_shape {
     int32_t type;
     mts_transform to_world;
@@ -345,7 +355,7 @@ typedef struct mts_stats {
     double calibration_ms;    /* device time of that launch                                      */
     int32_t textured;         /* 1 when the scene was rendered by the TEX instantiations (a scene with mts_scene_desc.textures or a blendbsdf): kernel_variant still names
                                  the row of the kernel table the scene gets; kernel_names.h: kv::textured_variant maps it to the kernel that ran */
-                              /* 2 when it was rendered by the INST kernels (a scene with an MTS_SHAPE_INSTANCE: the TEX instantiations over the two-level
+                              /* 2 when it was rendered by the INST kernels (a scene with an MTS_SHAPE_INSTANCE or an MTS_SHAPE_CONE: the TEX instantiations over the two-level
                                  traversal, mapped from the row in the same way) */
     int32_t reserved2_;
 } mts_stats;

@@ -282,6 +282,7 @@ private:
         r.to_world = xf(p.transform("to_world", ScalarTransform4f()));
         if (cls == "rectangle") { r.type = MTS_SHAPE_RECTANGLE; r.flip_normals = p.bool_("flip_normals", false); }
         else if (cls == "disk") { r.type = MTS_SHAPE_DISK; r.flip_normals = p.bool_("flip_normals", false); }
+        else if (cls == "cone") { r.type = MTS_SHAPE_CONE; r.flip_normals = p.bool_("flip_normals", false); }      // cone.cpp:79-85: to_world as given; the library decomposes it
         else if (cls == "sphere") {
             r.type = MTS_SHAPE_SPHERE; r.flip_normals = p.bool_("flip_normals", false);
             const ScalarPoint3f c = p.point3f("center", ScalarPoint3f(0.f)); r.center[0] = c.x(); r.center[1] = c.y(); r.center[2] = c.z();
