@@ -25,6 +25,7 @@ PHASE_ISOTROPIC, PHASE_HG, PHASE_RAYLEIGH, PHASE_BLEND, PHASE_TABULATED = 0, 1, 
 MEDIUM_HOMOGENEOUS, MEDIUM_HETEROGENEOUS = 0, 1
 BSDF_DIFFUSE, BSDF_NULL, BSDF_RPV, BSDF_BILAMBERTIAN, BSDF_BLEND = 0, 1, 2, 3, 4
 BSDF_TWOSIDED = 6                # 5 stays unassigned (mtsamd.h)
+BSDF_DIELECTRIC, BSDF_CONDUCTOR = 8, 9      # 7 stays unassigned as well
 SHAPE_RECTANGLE, SHAPE_CUBE, SHAPE_SPHERE, SHAPE_MESH, SHAPE_DISK = 0, 1, 2, 3, 4
 # instanced geometry on the existing record (mtsamd.h): a group's face_count = its member count, the members follow it; an instance's
 # vertex_count = the index of its group's record

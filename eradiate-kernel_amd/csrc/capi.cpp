@@ -384,7 +384,7 @@ int mts_render_sensor(mts_scene *scene, int32_t sensor, const mts_render_opts *o
                                  (hs.integrator.moment ? "X, Y, Z, A, W + the moment integrator's m1.X, m1.Y, m1.Z, m2.X, m2.Y, m2.Z)" : "X, Y, Z, A, W + two per spectral bin)"));
     const KernelChoice kc = kernel_of(hs, sv, block_size, sw, opts.collect_counters != 0);
     // a textured scene: the TEX instantiation that renders the table's row (kernel_names.h); mts_stats.kernel_variant keeps naming the row
-    const bool textured = !hs.bsdf_tex.empty();            // texture records, a blendbsdf or a twosided (scene_host.cpp: build_textures); an instanced scene has the table too
+    const bool textured = !hs.bsdf_tex.empty();            // texture records, a blendbsdf, a twosided, a dielectric or a conductor (scene_host.cpp: build_textures); an instanced scene has the table too
     const bool instanced = !hs.instances.empty() || hs.has_cone;   // instances or a cone: the INST kernels (kernels.hip): the TEX instantiations over the two-level traversal, mapped from the row alike
     const int variant = textured ? kv::textured_variant(kc.variant, hs.integrator.type, se.wavefront != 0, opts.collect_counters != 0) : kc.variant;
 #if defined(MTSAMD_HOST_ONLY)

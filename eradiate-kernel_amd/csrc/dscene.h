@@ -69,6 +69,9 @@ struct DMedium {
 // row = the weight's texture.
 // A twosided (MTS_BSDF_TWOSIDED; TEX instantiations only) keeps the bits of rho_0[0] / rho_0[1] = the indices of brdf_0 (the side
 // cos_theta(wi) > 0) / brdf_1 (< 0), equal when one child was given, and flags = the union of twosided.cpp:78-88; nothing else is read.
+// A dielectric (MTS_BSDF_DIELECTRIC; TEX instantiations only) keeps rho_0[0] = eta = int_ior / ext_ior, reflectance = specular_reflectance,
+// transmittance = specular_transmittance.  A conductor (MTS_BSDF_CONDUCTOR; TEX instantiations only) keeps rho_0 = eta and k = k per
+// channel, reflectance = specular_reflectance.
 struct DBsdf { int32_t type; float reflectance[3], rho_0[3], k[3], g[3], rho_c[3]; uint32_t flags; float transmittance[3]; };
 
 // Textures behind a BSDF's colour parameters (textures/bitmap.cpp, textures/checkerboard.cpp; rgb / mono variants).  to_uv: row-major
@@ -239,6 +242,7 @@ struct DScene {
 
 // bsdf.h:38-124
 enum : uint32_t { F_Null = 0x1, F_DiffuseReflection = 0x2, F_DiffuseTransmission = 0x4, F_GlossyReflection = 0x8,
+                  F_DeltaReflection = 0x20, F_DeltaTransmission = 0x40, F_NonSymmetric = 0x4000,
                   F_FrontSide = 0x8000, F_BackSide = 0x10000,
                   F_Smooth = 0x2 | 0x4 | 0x8 | 0x10, F_Delta = 0x1 | 0x20 | 0x40, F_Transmission = 0x4 | 0x10 | 0x40 | 0x100 | 0x1 };
 

@@ -1471,15 +1471,81 @@ DEV Spec blend_sample(const DScene &sc, const DBsdf &blend, float w, F2 uv, F3 w
     }
     return val;
 }
-// eval + pdf, and sample, of the BSDF record `b` of a hit (a plain one localised already); TEX: a blend resolves through its children
+// ---- smooth specular BSDFs (bsdfs/dielectric.cpp:201-310, bsdfs/conductor.cpp:217-270, render/fresnel.h; DBsdf in dscene.h says where
+// the records keep what).  TEX instantiations only, as a blend: a scene that holds one renders there.  Both have delta lobes alone:
+// eval and pdf are 0 (dielectric.cpp:312-320, conductor.cpp:272-280) and sample() draws nothing from sample2.  The ctx.component /
+// TransportMode::Importance branches are never reached by path / volpath / volpathmis and are not restated.
+// fresnel() (fresnel.h:33-70): selects, no branch -- lanes of one wave stand on both sides of an interface.  Index-matched: r = 0;
+// grazing (cos_theta_i == 0): r = 1; total internal reflection: safe_sqrt gives cos_theta_t = 0, hence a_s = 1, a_p = -1, r = 1.
+struct Fresnel { float r, cos_theta_t, eta_it, eta_ti; };
+DEV Fresnel fresnel_dielectric(float cos_theta_i, float eta) {
+    Fresnel f;
+    const bool outside = cos_theta_i >= 0.f;
+    const float rcp_eta = pm_rcp(eta);
+    f.eta_it = outside ? eta : rcp_eta; f.eta_ti = outside ? rcp_eta : eta;
+    const float cos_theta_t_sqr = pm_fma(-pm_fma(-cos_theta_i, cos_theta_i, 1.f), f.eta_ti * f.eta_ti, 1.f);     // Snell's law
+    const float ci = pm_abs(cos_theta_i), ct = pm_safe_sqrt(cos_theta_t_sqr);
+    const bool index_matched = eta == 1.f, special_case = index_matched || ci == 0.f;
+    const float a_s = pm_fma(-f.eta_it, ct, ci) / pm_fma(f.eta_it, ct, ci);
+    const float a_p = pm_fma(-f.eta_it, ci, ct) / pm_fma(f.eta_it, ci, ct);
+    const float r = .5f * (a_s * a_s + a_p * a_p);
+    f.r = special_case ? (index_matched ? 0.f : 1.f) : r;
+    f.cos_theta_t = pm_mulsign_neg(ct, cos_theta_i);
+    return f;
+}
+// fresnel_conductor() (fresnel.h:91-116) of one channel; the caller guarantees cos_theta_i > 0
+DEV float fresnel_conductor(float cos_theta_i, float eta_r, float eta_i) {
+    const float cos_theta_i_2 = cos_theta_i * cos_theta_i, sin_theta_i_2 = 1.f - cos_theta_i_2, sin_theta_i_4 = sin_theta_i_2 * sin_theta_i_2;
+    const float temp_1 = eta_r * eta_r - eta_i * eta_i - sin_theta_i_2,
+                a_2_pb_2 = pm_safe_sqrt(temp_1 * temp_1 + 4.f * eta_i * eta_i * eta_r * eta_r),
+                a = pm_safe_sqrt(.5f * (a_2_pb_2 + temp_1));
+    const float term_1 = a_2_pb_2 + cos_theta_i_2, term_2 = 2.f * cos_theta_i * a;
+    const float r_s = (term_1 - term_2) / (term_1 + term_2);
+    const float term_3 = a_2_pb_2 * cos_theta_i_2 + sin_theta_i_4, term_4 = term_2 * sin_theta_i_2;
+    const float r_p = r_s * (term_3 - term_4) / (term_3 + term_4);
+    return .5f * (r_s + r_p);
+}
+DEV F3 reflect(F3 wi) { return f3(-wi.x, -wi.y, wi.z); }                                                          // fresnel.h:273-277
+DEV F3 refract(F3 wi, float cos_theta_t, float eta_ti) { return f3(-eta_ti * wi.x, -eta_ti * wi.y, cos_theta_t); }     // fresnel.h:291-294
+// dielectric.cpp:201-310: reflection when sample1 <= r_i; bs.pdf the lobe's probability, bs.eta 1 / eta_it; the weight is the lobe's
+// colour, times eta_ti^2 on transmission (radiance transport: the solid angle is compressed across the interface, :302-307)
+DEV Spec dielectric_sample(const DBsdf &b, F3 wi, float sample1, BSDFSample &bs, const SpecCtx &cx = SpecCtx(), int id = 0) {
+    const Fresnel f = fresnel_dielectric(wi.z, b.rho_0[0]);
+    const bool selected_r = sample1 <= f.r;
+    bs.pdf = selected_r ? f.r : 1.f - f.r;
+    bs.sampled_type = selected_r ? F_DeltaReflection : F_DeltaTransmission;
+    const F3 wr = reflect(wi), wt = refract(wi, f.cos_theta_t, f.eta_ti);
+    bs.wo = selected_r ? wr : wt;
+    bs.eta = selected_r ? 1.f : f.eta_it;
+    const Spec reflectance = BSDF_COLOR(b, reflectance, MTS_BSDF_SP_REFLECTANCE, cx, id), transmittance = BSDF_COLOR(b, transmittance, MTS_BSDF_SP_TRANSMITTANCE, cx, id);
+    return selected_r ? reflectance : transmittance * (f.eta_ti * f.eta_ti);
+}
+// conductor.cpp:217-270: active for cos_theta_i > 0 alone; from behind the zero sample, and the path ends
+DEV Spec conductor_sample(const DBsdf &b, F3 wi, BSDFSample &bs, const SpecCtx &cx = SpecCtx(), int id = 0) {
+    const bool active = wi.z > 0.f;
+    const F3 wr = reflect(wi);
+    bs.wo = active ? wr : f3s(0.f); bs.pdf = active ? 1.f : 0.f; bs.eta = active ? 1.f : 0.f; bs.sampled_type = active ? (uint32_t) F_DeltaReflection : 0u;
+    const Spec eta = BSDF_COLOR(b, rho_0, MTS_BSDF_SP_RHO_0, cx, id), k = BSDF_COLOR(b, k, MTS_BSDF_SP_K, cx, id);
+#if MTS_SPEC_N == 3
+    const Spec fr = f3(fresnel_conductor(wi.z, eta.x, k.x), fresnel_conductor(wi.z, eta.y, k.y), fresnel_conductor(wi.z, eta.z, k.z));
+#else
+    const Spec fr = spec4(fresnel_conductor(wi.z, eta.x, k.x), fresnel_conductor(wi.z, eta.y, k.y), fresnel_conductor(wi.z, eta.z, k.z), fresnel_conductor(wi.z, eta.w, k.w));
+#endif
+    return active ? BSDF_COLOR(b, reflectance, MTS_BSDF_SP_REFLECTANCE, cx, id) * fr : spec_s(0.f);
+}
+// eval + pdf, and sample, of the BSDF record `b` of a hit (a plain one localised already); TEX: a blend resolves through its children,
+// a dielectric and a conductor through the functions above
 template <int TEX, bool U>
 DEV void hit_bsdf_eval_pdf(const DScene &sc, const DBsdf &b, float w, F2 uv, F3 wi, F3 wo, Spec &val, float &pdf, const SpecCtx &cx = SpecCtx(), int id = 0) {
     if constexpr (TEX != 0) if (b.type == MTS_BSDF_BLEND) { blend_eval_pdf<U>(sc, b, w, uv, wi, wo, val, pdf); return; }
+    if constexpr (TEX != 0) if (b.type == MTS_BSDF_DIELECTRIC || b.type == MTS_BSDF_CONDUCTOR) { val = spec_s(0.f); pdf = 0.f; return; }
     val = bsdf_eval(b, wi, wo, cx, id); pdf = bsdf_pdf(b, wi, wo, cx, id);
 }
 template <int TEX, bool U>
 DEV Spec hit_bsdf_sample(const DScene &sc, const DBsdf &b, float w, F2 uv, F3 wi, float sample1, F2 sample2, BSDFSample &bs, const SpecCtx &cx = SpecCtx(), int id = 0) {
     if constexpr (TEX != 0) if (b.type == MTS_BSDF_BLEND) return blend_sample<U>(sc, b, w, uv, wi, sample1, sample2, bs);
+    if constexpr (TEX != 0) if (b.type == MTS_BSDF_DIELECTRIC) return dielectric_sample(b, wi, sample1, bs, cx, id);
+    if constexpr (TEX != 0) if (b.type == MTS_BSDF_CONDUCTOR) return conductor_sample(b, wi, bs, cx, id);
     return bsdf_sample(b, wi, sample1, sample2, bs, cx, id);
 }
 // ---- twosided (bsdfs/twosided.cpp:94-181; DBsdf in dscene.h says where the record keeps its children).  TEX instantiations only, as
@@ -1501,8 +1567,10 @@ DEV BsdfSide twosided_side(const DScene &sc, int bsdf_id, F3 wi) {
 }
 DEV void zero_bsdf_sample(BSDFSample &bs) { bs.wo = f3s(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.sampled_type = 0; }
 // at(): the record of the hit; eval_pdf() / sample() on it.  TEX: a twosided's side is resolved once, in at(), from the local wi --
-// `local` is then the child's record, its flags included (the child is smooth whenever the adapter's union is, for the children this
-// backend nests, so the callers' NEE test reads the same); a blend's weight and the hit's uv are evaluated once, in at(), too, and
+// `local` is then the child's record under the flags of the hit's OWN record, the adapter's union of both sides (twosided.cpp:78-88):
+// that is what the reference's integrators test before they draw an emitter sample (path.cpp:155, volpath.cpp:198) and what the ring
+// machine's blk_surf reads.  With a conductor on one side and a diffuse BSDF on the other the child's flags would differ: a hit on the
+// mirror still draws its emitter sample and evaluates to 0.  A blend's weight and the hit's uv are evaluated once, in at(), too, and
 // serve eval, pdf and sample of that hit, as `local` does for colours.
 // TEX: TEX_NONE the plain instantiations, TEX_ON the textured ones, TEX_INST the textured ones of an instanced scene -- two-level
 // traversal, the instance of a hit in Hit::shape, a member's surface carried to world space (INST = true in the functions above)
@@ -1521,8 +1589,9 @@ template <bool INST> struct HitBsdfTex {
     DBsdf local; F2 uv; float w; bool back, none;
     DEV const DBsdf &at(const DScene &sc, int bsdf_id, const DShape &shape, const Hit &si, F3 wi) {
         const BsdfSide side = twosided_side(sc, bsdf_id, wi);
+        const uint32_t own_flags = as_global(sc.bsdfs)[bsdf_id].flags;
         bsdf_id = side.id; back = side.back; none = side.none;
-        local = sc.bsdfs[bsdf_id]; uv.x = uv.y = 0.f; w = 0.f;
+        local = sc.bsdfs[bsdf_id]; local.flags = own_flags; uv.x = uv.y = 0.f; w = 0.f;
         if (local.type == MTS_BSDF_BLEND) { uv = surface_uv<INST>(sc, shape, si); w = blend_weight(sc, bsdf_id, local, uv); }
         else bsdf_apply_textures(sc, bsdf_id, local, [&]() { return surface_uv<INST>(sc, shape, si); });
         return local;

@@ -26,7 +26,7 @@ constexpr int moment_variant(int variant, int integrator, bool wavefront, bool c
          : variant == ring(512) && integrator == 2 ? variant
          : variant == FLAT && integrator == 0 ? variant : NESTED;
 }
-// A textured scene (mts_scene_desc.textures), or one that holds a blendbsdf or a twosided, renders on the general rgb / mono unit as well, in TEX instantiations: `volpath` on
+// A textured scene (mts_scene_desc.textures), or one that holds a blendbsdf, a twosided, a dielectric or a conductor, renders on the general rgb / mono unit as well, in TEX instantiations: `volpath` on
 // 1024-path rings in its ring TEX kernel (scalar streams, no counters), `path` on the flat row in the flat TEX loop, every other row
 // -- `volpathmis`, wavefront streams, counters, 256-path rings -- in the nested TEX kernel (same functions, same streams: the same film).
 // mts_stats.kernel_variant keeps naming the table's row; mts_stats.textured says that this mapping applied.

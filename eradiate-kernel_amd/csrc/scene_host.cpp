@@ -66,6 +66,8 @@ static uint32_t bsdf_flags(int type) {
     if (type == MTS_BSDF_DIFFUSE) return F_DiffuseReflection | F_FrontSide;                // diffuse.cpp:55
     if (type == MTS_BSDF_NULL) return F_Null | F_FrontSide | F_BackSide;                   // null.cpp:26
     if (type == MTS_BSDF_BILAMBERTIAN) return F_DiffuseReflection | F_DiffuseTransmission | F_FrontSide | F_BackSide;   // bilambertian.cpp:55-60
+    if (type == MTS_BSDF_DIELECTRIC) return F_DeltaReflection | F_DeltaTransmission | F_FrontSide | F_BackSide | F_NonSymmetric;   // dielectric.cpp:193-198
+    if (type == MTS_BSDF_CONDUCTOR) return F_DeltaReflection | F_FrontSide;               // conductor.cpp:201
     return F_GlossyReflection | F_FrontSide;                                               // rpv.cpp:66
 }
 
@@ -476,9 +478,16 @@ static void build_pair_grid(const DVolume &a, const std::vector<float> &ga, cons
 }
 
 static DBsdf build_bsdf(const mts_bsdf &b) {
-    if (b.type < MTS_BSDF_DIFFUSE || b.type > MTS_BSDF_TWOSIDED || b.type == 5) throw std::runtime_error("unknown BSDF type");      // 5: unassigned (mtsamd.h)
+    if (b.type < MTS_BSDF_DIFFUSE || b.type > MTS_BSDF_CONDUCTOR || b.type == 5 || b.type == 7) throw std::runtime_error("unknown BSDF type");      // 5, 7: unassigned (mtsamd.h)
     DBsdf db; memset(&db, 0, sizeof(db));
     db.type = b.type;
+    if (b.type == MTS_BSDF_DIELECTRIC) {                     // dielectric.cpp:174-199: eta = int_ior / ext_ior; the kernels take its reciprocal
+        if (!std::isfinite(b.rho_0[0]) || !(b.rho_0[0] > 0.f)) throw std::runtime_error("dielectric: \"rho_0[0]\" (eta = int_ior / ext_ior) must be finite and positive");
+    }
+    if (b.type == MTS_BSDF_CONDUCTOR) {                      // conductor.cpp:200-215
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(b.rho_0[c]) || !std::isfinite(b.k[c])) throw std::runtime_error("conductor: \"rho_0\" (eta) and \"k\" must be finite");
+    }
     if (b.type == MTS_BSDF_TWOSIDED) {                       // twosided.cpp:63-92: the two child indices and nothing else; flags: resolve_twosided
         memcpy(&db.rho_0[0], &b.spectrum[0], 4); memcpy(&db.rho_0[1], &b.spectrum[1], 4);
         return db;
@@ -507,6 +516,9 @@ static void resolve_blend(DBsdf &db, int i, const std::vector<DBsdf> &all, int32
         if (t == MTS_BSDF_NULL) throw std::runtime_error(field + " is a null BSDF: null children are not supported by this backend");
         if (t == MTS_BSDF_BLEND) throw std::runtime_error(field + " is a blendbsdf: nested blends are not supported by this backend");
         if (t == MTS_BSDF_TWOSIDED) throw std::runtime_error(field + " is a twosided: a twosided inside a blend is not supported by this backend");
+        // a delta lobe in a mixture needs the blend's pdf to stay the child's (blendbsdf.cpp:117-121) through the specular chain: not restated
+        if (t == MTS_BSDF_DIELECTRIC) throw std::runtime_error(field + " is a dielectric: specular children are not supported in a blend by this backend");
+        if (t == MTS_BSDF_CONDUCTOR) throw std::runtime_error(field + " is a conductor: specular children are not supported in a blend by this backend");
     }
     db.flags = all[(size_t) blend_child(db, 0)].flags | all[(size_t) blend_child(db, 1)].flags;
 }
@@ -527,9 +539,11 @@ static void resolve_twosided(DBsdf &db, int i, const std::vector<DBsdf> &all, in
     if (db.flags & F_Transmission) throw std::runtime_error("bsdf " + std::to_string(i) + ": twosided: Only materials without a transmission component can be nested!");
 }
 // which of the six colour parameters each BSDF plugin reads (spectral variant: the spectra it needs); a blend: slot 0 is its weight's texture
-// twosided reads no colour parameter and no texture slot (type 5 is unassigned)
-static const bool BSDF_SP_USED[7][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */,
-                                         { 1, 0, 0, 0, 0, 0 } /* blend */, { 0, 0, 0, 0, 0, 0 } /* unassigned */, { 0, 0, 0, 0, 0, 0 } /* twosided */ };
+// twosided reads no colour parameter and no texture slot (types 5 and 7 are unassigned); a dielectric's eta is a float, a conductor's
+// eta and k are constants: their texture slots stay -1
+static const bool BSDF_SP_USED[10][6] = { { 1, 0, 0, 0, 0, 0 } /* diffuse */, { 0, 0, 0, 0, 0, 0 } /* null */, { 0, 1, 1, 1, 1, 0 } /* rpv */, { 1, 0, 0, 0, 0, 1 } /* bilambertian */,
+                                          { 1, 0, 0, 0, 0, 0 } /* blend */, { 0, 0, 0, 0, 0, 0 } /* unassigned */, { 0, 0, 0, 0, 0, 0 } /* twosided */, { 0, 0, 0, 0, 0, 0 } /* unassigned */,
+                                          { 1, 0, 0, 0, 0, 1 } /* dielectric */, { 1, 0, 0, 0, 0, 0 } /* conductor */ };
 
 // A texture's record and (bitmap) its texels as the device holds them: validated as BitmapTexture's / Checkerboard's constructors
 // validate (bitmap.cpp:92-206, checkerboard.cpp:40-44).  `with_data` = false: the record alone (an update checks the frozen fields first).
@@ -636,11 +650,15 @@ static DefaultBsdfs build_bsdfs(const mts_scene_desc &d, bool spectral, HostScen
         } else if (d.bsdfs[i].type == MTS_BSDF_TWOSIDED) {               // and so is a twosided: it renders in the TEX instantiations alone
             if (spectral) throw std::runtime_error("bsdf " + std::to_string(i) + ": twosided is not supported in the spectral variant");
             if (d.integrator.moment != 0) throw std::runtime_error("bsdf " + std::to_string(i) + ": twosided is not supported inside a moment integrator's scene");
+        } else if (d.bsdfs[i].type == MTS_BSDF_DIELECTRIC || d.bsdfs[i].type == MTS_BSDF_CONDUCTOR) {     // and so are the smooth specular BSDFs
+            const std::string what = d.bsdfs[i].type == MTS_BSDF_DIELECTRIC ? "dielectric" : "conductor";
+            if (spectral) throw std::runtime_error("bsdf " + std::to_string(i) + ": " + what + " is not supported in the spectral variant");
+            if (d.integrator.moment != 0) throw std::runtime_error("bsdf " + std::to_string(i) + ": " + what + " is not supported inside a moment integrator's scene");
         }
     for (int i = 0; i < d.bsdf_count; ++i) {
         const mts_bsdf &b = d.bsdfs[i];
         try { hs.bsdfs.push_back(build_bsdf(b)); }
-        catch (const std::runtime_error &e) { if (b.type != MTS_BSDF_BLEND && b.type != MTS_BSDF_TWOSIDED) throw; throw std::runtime_error("bsdf " + std::to_string(i) + ": " + e.what()); }
+        catch (const std::runtime_error &e) { if (b.type != MTS_BSDF_BLEND && b.type != MTS_BSDF_TWOSIDED && b.type != MTS_BSDF_DIELECTRIC && b.type != MTS_BSDF_CONDUCTOR) throw; throw std::runtime_error("bsdf " + std::to_string(i) + ": " + e.what()); }
         if (spectral)                                                    // which of the six colour parameters each plugin reads
             for (int k = 0; k < MTS_BSDF_SP_COUNT; ++k) hs.bsdf_sp.push_back(BSDF_SP_USED[b.type][k] ? spectrum_index(d, b.spectrum[k], "a BSDF parameter") : 0);
     }
@@ -673,9 +691,9 @@ static void build_textures(const mts_scene_desc &d, bool spectral, HostScene &hs
     if (d.texture_count < 0 || (d.texture_count > 0 && !d.textures)) throw std::runtime_error("textures: a negative count, or records missing");
     if (d.texture_count == 0) {
         for (int i = 0; i < d.bsdf_count; ++i) { int32_t t[MTS_BSDF_SP_COUNT]; bsdf_texture_indices(d, i, t); }        // nothing but -1 is in range
-        // a blend or a twosided renders in the TEX instantiations, which read the index table: all -1 under a constant weight and plain children
+        // a blend, a twosided, a dielectric or a conductor renders in the TEX instantiations, which read the index table: all -1 under a constant weight and plain children
         for (int i = 0; i < d.bsdf_count; ++i)
-            if (d.bsdfs[i].type == MTS_BSDF_BLEND || d.bsdfs[i].type == MTS_BSDF_TWOSIDED) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
+            if (d.bsdfs[i].type == MTS_BSDF_BLEND || d.bsdfs[i].type == MTS_BSDF_TWOSIDED || d.bsdfs[i].type == MTS_BSDF_DIELECTRIC || d.bsdfs[i].type == MTS_BSDF_CONDUCTOR) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }
         // so does an instanced scene, and one with a cone: the INST kernels are TEX instantiations
         for (int i = 0; i < d.shape_count; ++i)
             if (d.shapes[i].type == MTS_SHAPE_INSTANCE || d.shapes[i].type == MTS_SHAPE_CONE) { hs.bsdf_tex.assign(hs.bsdfs.size() * MTS_BSDF_SP_COUNT, -1); break; }

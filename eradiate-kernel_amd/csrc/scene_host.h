@@ -51,7 +51,7 @@ struct HostScene {
     std::vector<int32_t> bsdf_sp, emitter_sp; std::vector<DVolumeSp> volume_sp;
     // textured scenes (DScene::textures ...): the records, each bitmap's texels as the device holds them (three-channel texels padded
     // to four floats), and the per-BSDF index table; all three empty in a scene without textures -- but for the table of a scene that
-    // holds a blendbsdf or a twosided: a non-empty table is what sends a scene to the TEX instantiations
+    // holds a blendbsdf, a twosided, a dielectric or a conductor: a non-empty table is what sends a scene to the TEX instantiations
     std::vector<DTexture> textures; std::vector<std::vector<float>> texels; std::vector<int32_t> bsdf_tex;
     // instanced scenes (DScene::instances / groups): one record per MTS_SHAPE_INSTANCE / MTS_SHAPE_SHAPEGROUP, in the order of their
     // shape records; instance_boxes: the world-space box of each instance (instance.cpp:81-92), by its index in `instances` -- what

@@ -972,7 +972,10 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
                 const DShape s = cload(sc.shapes + su);
                 emitter = s.emitter; bsdf_id = s.bsdf;
                 if constexpr (TEX != 0) tex_uv = surface_uv<INST>(sc, s, p.si);
-                // the shading frame is only read by emitter evaluation and by the NEE of a smooth BSDF: a null boundary needs neither
+                // the shading frame is only read by emitter evaluation and by the NEE of a smooth BSDF: a null boundary needs neither.
+                // Nor does a dielectric or a conductor: its record has no smooth bit, so no emitter sample is drawn here, and blk_bsdf
+                // completes the surface itself before it samples; where a specular sheet carries an emitter, the first test completes it.
+                // bsdf_flags are the hit's own record's: under a twosided with a smooth side the frame is completed for both sides.
                 if (s.emitter >= 0 || (s.bsdf_flags & F_Smooth) != 0) complete_surface<GEOM_TABLE, INST>(sc, s, p.si, p.ray.d, sf);
             WATERFALL_END
         }

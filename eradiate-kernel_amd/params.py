@@ -161,7 +161,7 @@ class ParameterMap:
             return np.array(list(rec.to_uv), np.float32).reshape(3, 3)
         if p.what == "rgb":
             return np.array(list(getattr(rec, p.field.split("+")[0])), np.float32)
-        if p.what == "weight":
+        if p.what in ("weight", "eta"):                         # a float the record holds three times
             return getattr(rec, p.field)[0]
         if p.what == "range":
             return (rec.lambda_min, rec.lambda_max)
@@ -241,6 +241,8 @@ class ParameterMap:
             return SD._color(value, p.where, emitter=p.emitter), None
         if p.what == "weight":
             return (SD._weight(value, p.where),) * 3, None
+        if p.what == "eta":                                     # dielectric.cpp:323: the relative index of refraction, a plain float
+            return (float(value),) * 3, None
         if p.what == "range":
             lo, hi = (float(x) for x in value)
             return (lo, hi), None

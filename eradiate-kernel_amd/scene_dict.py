@@ -348,6 +348,33 @@ def _color_rgb(v, where, default=None, emitter=False):
 
 # BSDFFlags (bsdf.h:38-124) that the twosided adapter's constructor reads; Transmission holds Null
 _F_FRONT, _F_BACK, _F_TRANSMISSION = 0x8000, 0x10000, 0x4 | 0x10 | 0x40 | 0x100 | 0x1
+_F_DELTA_REFLECTION, _F_DELTA_TRANSMISSION, _F_NON_SYMMETRIC = 0x20, 0x40, 0x4000
+
+BSDF_PLUGINS = ("diffuse", "null", "rpv", "bilambertian", "blendbsdf", "twosided", "dielectric", "conductor")
+
+# Indices of refraction by material name, at about 589 nm and standard conditions (the names a `dielectric` accepts for "int_ior" /
+# "ext_ior"; the list order is the order the error message names them in)
+IOR_TABLE = (
+    ("vacuum", 1.0), ("helium", 1.000036), ("hydrogen", 1.000132), ("air", 1.000277), ("carbon dioxide", 1.00045),
+    ("water", 1.3330), ("acetone", 1.36), ("ethanol", 1.361), ("carbon tetrachloride", 1.461), ("glycerol", 1.4729),
+    ("benzene", 1.501), ("silicone oil", 1.52045), ("bromine", 1.661),
+    ("water ice", 1.31), ("fused quartz", 1.458), ("pyrex", 1.470), ("acrylic glass", 1.49), ("polypropylene", 1.49),
+    ("bk7", 1.5046), ("sodium chloride", 1.544), ("amber", 1.55), ("pet", 1.5750), ("diamond", 2.419))
+
+
+def lookup_ior(v, default):
+    """An index of refraction given as a number or as a material name, lower-cased before the lookup (ior.h:52-84) -> np.float32."""
+    if v is None:
+        v = default
+    if isinstance(v, bool) or isinstance(v, dict):
+        raise RuntimeError("An index of refraction is a float or a material name, got %r" % (v,))
+    if isinstance(v, (int, float, np.floating, np.integer)):
+        return np.float32(v)
+    name = str(v).lower()
+    for key, value in IOR_TABLE:
+        if key == name:
+            return np.float32(value)
+    raise RuntimeError("Unable to find an IOR value for \"%s\"! Valid choices are:%s" % (name, ", ".join(k for k, _ in IOR_TABLE)))
 
 
 def _weight(v, where):
@@ -529,6 +556,7 @@ class SceneBuilder:
         self.textures, self.bsdf_textures, self.bitmaps = [], [], {}
         self.blends = []         # where each blendbsdf sits (what a refusal of the whole scene names)
         self.twosided = []       # and each twosided
+        self.specular = []       # and each dielectric / conductor
         self.groups, self.instanced = [], []     # where each shapegroup / instance sits
         self.cones = []          # and each cone
 
@@ -857,6 +885,10 @@ class SceneBuilder:
                     if self.bsdfs[child].type == kind:
                         raise RuntimeError("\"blendbsdf\" %s: the nested BSDF \"%s\" is a \"%s\", which this backend cannot nest in a blend (a null or "
                                            "nested child needs the component flags the integrators read)" % (where, k, plugin))
+                for plugin, kind in (("dielectric", A.BSDF_DIELECTRIC), ("conductor", A.BSDF_CONDUCTOR)):
+                    if self.bsdfs[child].type == kind:
+                        raise RuntimeError("\"blendbsdf\" %s: the nested BSDF \"%s\" is a \"%s\": specular children are not supported in a blend "
+                                           "by this backend" % (where, k, plugin))
                 children.append(child)
             if not p.has("weight"):
                 raise RuntimeError("Property \"weight\" has not been specified!")        # props.texture("weight"), :71
@@ -904,6 +936,46 @@ class SceneBuilder:
             node += [("object", "brdf_0", ("bsdf", children[0])),
                      ("alias" if children[0] == children[1] else "object", "brdf_1", ("bsdf", children[1]))]
             self.twosided.append(where)
+        elif p.type in ("dielectric", "conductor"):                      # src/bsdfs/dielectric.cpp:174-199, src/bsdfs/conductor.cpp:200-215
+            if spectral:
+                raise RuntimeError("\"%s\" is not supported in the spectral variant (%s): it renders in the kernels of textured scenes, "
+                                   "which that variant has not got" % (p.type, where))
+            if p.type == "dielectric":
+                rec.type = A.BSDF_DIELECTRIC
+                int_ior, ext_ior = lookup_ior(p.get("int_ior"), "bk7"), lookup_ior(p.get("ext_ior"), "air")
+                if int_ior < 0 or ext_ior < 0:
+                    raise RuntimeError("The interior and exterior indices of refraction must be positive!")
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    eta = float(np.float32(int_ior) / np.float32(ext_ior))
+                if not (math.isfinite(eta) and eta > 0):
+                    raise RuntimeError("\"dielectric\" %s: eta = int_ior / ext_ior = %r must be finite and positive" % (where, eta))
+                rec.rho_0[:] = (eta,) * 3
+                node.append(("param", "eta", "eta", "rho_0"))            # :322-328: eta, and the two colours only if the scene gave them
+                rec.reflectance[:] = (1.0,) * 3
+                rec.transmittance[:] = (1.0,) * 3
+                if p.has("specular_reflectance"):
+                    colour("reflectance", 0, "specular_reflectance", 1.0)
+                if p.has("specular_transmittance"):
+                    colour("transmittance", 5, "specular_transmittance", 1.0)
+            else:
+                rec.type = A.BSDF_CONDUCTOR
+                colour("reflectance", 0, "specular_reflectance", 1.0)    # :282-286: specular_reflectance, eta, k
+                material = str(p.get("material", "none"))
+                if not (p.has("eta") or material == "none"):
+                    raise RuntimeError("\"conductor\" %s: the material preset \"%s\" is not supported by this backend (the measured indices of "
+                                       "refraction behind the names are not shipped): give \"eta\" and \"k\"" % (where, material))
+                if material != "none":
+                    raise RuntimeError("Should specify either (eta, k) or material, not both.")
+                for field, key, default in (("rho_0", "eta", 0.0), ("k", "k", 1.0)):
+                    if self._is_texture(p.d.get(key)):
+                        raise RuntimeError("\"conductor\" %s: a texture on \"%s\" is not supported by this backend: give a float, an rgb colour "
+                                           "or a uniform spectrum" % (where, key))
+                    c = _color(p.get(key), where + "." + key, default=default)
+                    if not all(math.isfinite(x) for x in c):
+                        raise RuntimeError("\"conductor\" %s: \"%s\" must be finite" % (where, key))
+                    getattr(rec, field)[:] = c
+                    node.append(("object", key, ("colour", "bsdf", len(self.bsdfs), field, where + "." + key, False)))
+            self.specular.append(where)
         else:
             raise RuntimeError("Unknown / unsupported BSDF plugin \"%s\"" % p.type)
         p.finish()
@@ -919,7 +991,9 @@ class SceneBuilder:
         if rec.type in (A.BSDF_BLEND, A.BSDF_TWOSIDED):
             return self._bsdf_flags(rec.spectrum[0]) | self._bsdf_flags(rec.spectrum[1])
         return {A.BSDF_DIFFUSE: 0x2 | _F_FRONT, A.BSDF_NULL: 0x1 | _F_FRONT | _F_BACK, A.BSDF_RPV: 0x8 | _F_FRONT,
-                A.BSDF_BILAMBERTIAN: 0x2 | 0x4 | _F_FRONT | _F_BACK}[rec.type]
+                A.BSDF_BILAMBERTIAN: 0x2 | 0x4 | _F_FRONT | _F_BACK,
+                A.BSDF_DIELECTRIC: _F_DELTA_REFLECTION | _F_DELTA_TRANSMISSION | _F_FRONT | _F_BACK | _F_NON_SYMMETRIC,
+                A.BSDF_CONDUCTOR: _F_DELTA_REFLECTION | _F_FRONT}[rec.type]
 
     # ------------------------------------------------------------ shapes
     def make_shape(self, d, where, in_scene=True):
@@ -983,7 +1057,7 @@ class SceneBuilder:
                 continue
             t = v.get("type")
             kind = self.instances.get(v.get("id"), ("",))[0] if t == "ref" else None
-            if t in ("diffuse", "null", "rpv", "bilambertian", "blendbsdf", "twosided") or kind == "bsdf":
+            if t in BSDF_PLUGINS or kind == "bsdf":
                 if rec.bsdf >= 0:
                     raise RuntimeError("Only a single BSDF child object can be specified per shape.")
                 p.queried.add(k)
@@ -1533,7 +1607,7 @@ class SceneBuilder:
                 if self.integrator is not None:
                     raise RuntimeError("Only one integrator can be specified per scene.")
                 self.set_integrator(v, k)
-            elif t in ("diffuse", "null", "rpv", "bilambertian", "blendbsdf", "twosided"):
+            elif t in BSDF_PLUGINS:
                 self.children.append((name, ("bsdf", self.add_bsdf(v, k))))
             elif t in ("homogeneous", "heterogeneous"):
                 self.children.append((name, ("medium", self.add_medium(v, k))))
@@ -1563,6 +1637,8 @@ class SceneBuilder:
             raise RuntimeError("\"cone\" (%s) is not supported in the gpu_spectral variant" % ", ".join(self.cones))
         if self.twosided and self.integrator.moment:
             raise RuntimeError("\"twosided\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.twosided))
+        if self.specular and self.integrator.moment:
+            raise RuntimeError("\"dielectric\" / \"conductor\" (%s) inside a moment integrator's scene is not supported by this backend" % ", ".join(self.specular))
         return self.finish()
 
     def finish(self):

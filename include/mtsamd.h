@@ -127,8 +127,20 @@ typedef struct mts_medium {
  *                                   another twosided (a limit of this backend, as is a twosided inside a blend) nor the record itself;
  *                                   a child may stand before or behind its parent.
  *      Nothing else of a twosided record is read: no colour parameter, no texture slot.  The value 5 is left unassigned and stays refused
- *      as "unknown BSDF type": the test suite probes 5 as the first unknown type. */
-enum { MTS_BSDF_DIFFUSE = 0, MTS_BSDF_NULL = 1, MTS_BSDF_RPV = 2, MTS_BSDF_BILAMBERTIAN = 3, MTS_BSDF_BLEND = 4, MTS_BSDF_TWOSIDED = 6 };
+ *      as "unknown BSDF type": the test suite probes 5 as the first unknown type.
+ *      MTS_BSDF_DIELECTRIC (rgb / mono variants; not with mts_integrator.moment): dielectric.cpp, a smooth interface between two
+ *      dielectrics: a delta reflection and a delta transmission lobe.  It adds no field:
+ *        rho_0[0]                   eta = int_ior / ext_ior, finite and positive
+ *        reflectance                "specular_reflectance" (default 1), texture slot 0
+ *        transmittance              "specular_transmittance" (default 1), texture slot 5
+ *      It has a transmission component: not a child of a twosided (twosided.cpp:90-91).
+ *      MTS_BSDF_CONDUCTOR (rgb / mono variants; not with mts_integrator.moment): conductor.cpp, a smooth mirror with the complex index
+ *      of refraction eta + i k, one-sided (a twosided may wrap it).  It adds no field:
+ *        rho_0, k                   "eta" (default 0) and "k" (default 1) per channel, finite; constants only (no texture slot)
+ *        reflectance                "specular_reflectance" (default 1), texture slot 0
+ *      Neither may be a child of a blend (a limit of this backend).  The values 5 and 7 are unassigned and stay refused as unknown. */
+enum { MTS_BSDF_DIFFUSE = 0, MTS_BSDF_NULL = 1, MTS_BSDF_RPV = 2, MTS_BSDF_BILAMBERTIAN = 3, MTS_BSDF_BLEND = 4, MTS_BSDF_TWOSIDED = 6,
+       MTS_BSDF_DIELECTRIC = 8, MTS_BSDF_CONDUCTOR = 9 };
 typedef struct mts_bsdf {
     int32_t type;
     float reflectance[3];     /* diffuse "reflectance" (rgb), default 0.5                        */

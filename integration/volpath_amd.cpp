@@ -230,7 +230,8 @@ private:
 
     // ---- BSDFs: diffuse (diffuse.cpp:137-139 "reflectance"), null, rpv (rpv.cpp:169-174 "rho_0", "g", "k", "rho_c"), bilambertian
     // (bilambertian.cpp:195-198 "reflectance", "transmittance"), blendbsdf (blendbsdf.cpp:166-170 "weight", "bsdf_0", "bsdf_1"),
-    // twosided (twosided.cpp:183-186 "brdf_0", "brdf_1")
+    // twosided (twosided.cpp:183-186 "brdf_0", "brdf_1"), dielectric (dielectric.cpp:322-328 "eta", "specular_reflectance",
+    // "specular_transmittance"), conductor (conductor.cpp:282-286 "specular_reflectance", "eta", "k")
     int32_t visit_bsdf(const BSDF *b) {
         if (auto it = m_bsdf_of.find(b); it != m_bsdf_of.end()) return it->second;
         const std::string cls = props_of(b).plugin_name();
@@ -264,6 +265,20 @@ private:
             r.type = MTS_BSDF_TWOSIDED;
             r.spectrum[0] = visit_bsdf((const BSDF *) k.object("brdf_0"));
             r.spectrum[1] = visit_bsdf((const BSDF *) k.object("brdf_1"));
+        } else if (cls == "dielectric") {                                           // dielectric.cpp:322-328: "eta", and the two colours if the scene gave them
+            // MTS_BSDF_DIELECTRIC (mtsamd.h): rho_0[0] = eta, reflectance / transmittance = the two colours, 1 where the plugin holds none
+            if constexpr (is_spectral_v<Spectrum>) Throw("volpath_amd: dielectric is not supported in the spectral variants");
+            r.type = MTS_BSDF_DIELECTRIC;
+            r.rho_0[0] = r.rho_0[1] = r.rho_0[2] = (float) k.get<ScalarFloat>("eta");
+            for (int c = 0; c < 3; ++c) r.reflectance[c] = r.transmittance[c] = 1.f;
+            if (tex("specular_reflectance")) colour(tex("specular_reflectance"), r.reflectance, r.spectrum[0]);
+            if (tex("specular_transmittance")) colour(tex("specular_transmittance"), r.transmittance, r.spectrum[5]);
+        } else if (cls == "conductor") {                                            // conductor.cpp:282-286: "specular_reflectance", "eta", "k"
+            // MTS_BSDF_CONDUCTOR (mtsamd.h): rho_0 = eta, k = k, reflectance = specular_reflectance; constants, as every colour here
+            if constexpr (is_spectral_v<Spectrum>) Throw("volpath_amd: conductor is not supported in the spectral variants");
+            r.type = MTS_BSDF_CONDUCTOR;
+            colour(tex("specular_reflectance"), r.reflectance, r.spectrum[0]);
+            colour(tex("eta"), r.rho_0, r.spectrum[1]); colour(tex("k"), r.k, r.spectrum[2]);
         } else
             Throw("volpath_amd: BSDF plugin \"%s\"", cls);
         bsdfs.push_back(r); return m_bsdf_of[b] = (int32_t) bsdfs.size() - 1;
