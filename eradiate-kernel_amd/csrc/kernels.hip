@@ -214,6 +214,8 @@ __device__ __forceinline__ void path_pixel_flat(const DScene &sc, Pcg32 &rng, co
 // FLAT = true: volpath as the flat state machine of volpath_flat.h (the production kernel of the metric);
 // FLAT = false: the nested formulation of integrator_dev.h (path and volpathmis; volpath cross-check, MTSAMD_KERNEL=nested),
 // one instantiation per integrator (INTEG = NI_*).
+// Written out, not a call of lane_render (below): through it, with the scene by reference, v_rgb::render_kernel<true, false, 0> spills 78 -> 125 VGPRs
+// (the `path` kernel <false, true, 0> 98 -> 89); by value the kernels that share it keep their resources but not their text, which this one must in all nine units.
 #define MTS_NESTED_WAVES 1
 #if MTS_SPEC_N != 3
 #define MTS_PATH_WAVES 3      // four-wide spectra: the register budget of four waves per SIMD is not met
@@ -270,43 +272,33 @@ __global__ void __launch_bounds__(256, (FLAT && INTEG != NI_PATH) ? 1 : (INTEG =
 
 #endif // !MTS_LEAN || MTS_LEAN_PATH
 
-// Asynchronous-regrouping variant of the volpath render kernel (ring_driver.h on the blocks of volpath_flat.h).  The parameter list must stay in
-// sync with WgArgs: the block functions re-read it from the kernarg segment with scalar loads.  WG paths are served by NT threads;
+// Asynchronous-regrouping variant of the volpath render kernel (ring_driver.h on the blocks of volpath_flat.h).  The parameter list of every ring
+// kernel is MTS_WG_PARAMS, stated next to the WgArgs it mirrors: the block functions re-read it from the kernarg segment with scalar loads.  WG paths are served by NT threads;
 // WPE = waves per SIMD the register budget is sized for (512 / WPE VGPRs).
 template <bool COUNT, int WG, int NT, int WPE, bool WF = false>
-__global__ void __launch_bounds__(NT, WPE) render_kernel_wga(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
-                                                           uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
-                                                           unsigned long long *counters, const uint32_t *stop_flag,
-                                                           const uint32_t *tiles, uint32_t n_tiles) {
+__global__ void __launch_bounds__(NT, WPE) render_kernel_wga(MTS_WG_PARAMS) {
     Counters cnt = {};
     ring_workgroup_async<VolpathRing<COUNT, WG, WF>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
     if (COUNT) flush_counters(counters, cnt);
 }
-static_assert(sizeof(WgArgs) % 4 == 0, "WgArgs mirrors the kernel parameters");
 
 // The same driver for volpathmis (volpathmis_flat.h): four weight matrices per path, 512 paths per workgroup, two waves per SIMD.
 template <bool COUNT, bool SPEC, int WG, int NT>
-__global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
-                                                               uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
-                                                               unsigned long long *counters, const uint32_t *stop_flag,
-                                                               const uint32_t *tiles, uint32_t n_tiles) {
+__global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis(MTS_WG_PARAMS) {
     Counters cnt = {};
     ring_workgroup_async<VolpathMisRing<COUNT, SPEC, WG>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
     if (COUNT) flush_counters(counters, cnt);
 }
 
 #if MTS_SPEC_N == 3 && !defined(MTS_LEAN)
-// ---- the `moment` integrator (integrators/moment.cpp): the kernels above with the eleven-channel sample tail (splat_moment_t,
-// volpath_flat.h), under names of their own -- the plain instantiations stay what they are.  launch_render maps a row of the kernel
-// table to one of these (kernel_names.h: kv::moment_variant).
-// Per lane.  FLAT: `path` as the flat loop with regeneration; otherwise the nested formulation of whichever integrator the scene has
-// (decided at run time: one kernel serves the three), which is also the fallback of every row without a moment instantiation.
-template <bool COUNT, bool FLAT>
-__global__ void __launch_bounds__(256, FLAT ? MTS_PATH_WAVES : MTS_NESTED_WAVES) render_kernel_moment(DScene sc, const DBlock *__restrict__ blocks, uint32_t n_blocks, uint32_t block_size,
-                                                     uint32_t sample_count, float *__restrict__ film_base, unsigned long long *__restrict__ counters,
-                                                     const uint32_t *__restrict__ stop_flag) {
-    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];             // as render_kernel
-    {
+// ---- The lane of the per-lane kernels of the `moment` integrator, of textured and of instanced scenes (below): render_kernel's, with the
+// sample tail (MOMENT) and the BSDF / traversal (TEX) of the family; `bvh_top` is the kernel's own LDS array.
+// The scene record comes BY VALUE.  By reference the body is optimised on its own, before it is inlined, against a record that any store may
+// alias: v_rgb::render_kernel_tex<false, true> then spills 344 -> 433 VGPRs, <true, true> 359 -> 417, render_kernel_moment<true, false> 310 -> 312 SGPRs.
+template <bool COUNT, bool FLAT, bool MOMENT, int TEX>
+__device__ __forceinline__ void lane_render(DScene sc, float *bvh_top, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
+                                            uint32_t sample_count, float *film_base, unsigned long long *counters, const uint32_t *stop_flag) {
+    {                                                          // the BVH's top nodes (an instanced scene: of the SCENE level, which bvh_node_count counts alone) and the pmath tables
         const int staged = min(sc.bvh_node_count, MTS_BVH_LDS_NODES);
         for (int k = (int) threadIdx.x; k < staged * 8; k += (int) blockDim.x) bvh_top[k] = sc.bvh_nodes[k];
         pm_tables_to_lds(threadIdx.x);
@@ -324,34 +316,42 @@ __global__ void __launch_bounds__(256, FLAT ? MTS_PATH_WAVES : MTS_NESTED_WAVES)
     Pcg32 rng;
     rng.seed(sc.sensor.seed + (uint64_t) blk.id * ppb + i, PCG32_DEFAULT_STREAM);
     Counters cnt = {};
-    float acc[MTS_MOMENT_CHANNELS] = {};
-    if (FLAT) path_pixel_flat<COUNT, true>(sc, rng, blk, lx, ly, sample_count, film, acc, cnt, stop_flag);
+    constexpr int CH = MOMENT ? MTS_MOMENT_CHANNELS : 5;
+    float acc[CH] = {};
+    if (FLAT) path_pixel_flat<COUNT, MOMENT, TEX>(sc, rng, blk, lx, ly, sample_count, film, acc, cnt, stop_flag);
     else
     for (uint32_t j = 0; j < sample_count; ++j) {
         if ((j & 63u) == 63u && stop_requested(stop_flag)) break;
         if (sc.sensor.wavefront) seed_wavefront_sample(rng, sc.sensor, blk, lx, ly, j);
-        render_sample<COUNT, NI_ANY, true>(sc, rng, blk, lx, ly, film, acc, cnt);
+        render_sample<COUNT, NI_ANY, MOMENT, TEX>(sc, rng, blk, lx, ly, film, acc, cnt);
     }
-    float *dst = film_entry_moment(sc, blk, lx, ly, as_global(film));
-    for (int k = 0; k < MTS_MOMENT_CHANNELS; ++k) atomicAdd(dst + k, acc[k]);
+    float *dst = film_entry_of<MOMENT>(sc, blk, lx, ly, as_global(film));
+    for (int k = 0; k < CH; ++k) atomicAdd(dst + k, acc[k]);
     if (COUNT) flush_counters(counters, cnt);
+}
+
+// ---- the `moment` integrator (integrators/moment.cpp): the kernels above with the eleven-channel sample tail (splat_moment_t,
+// volpath_flat.h), under names of their own -- the plain instantiations stay what they are.  launch_render maps a row of the kernel
+// table to one of these (kernel_names.h: kv::moment_variant).
+// Per lane.  FLAT: `path` as the flat loop with regeneration; otherwise the nested formulation of whichever integrator the scene has
+// (decided at run time: one kernel serves the three), which is also the fallback of every row without a moment instantiation.
+template <bool COUNT, bool FLAT>
+__global__ void __launch_bounds__(256, FLAT ? MTS_PATH_WAVES : MTS_NESTED_WAVES) render_kernel_moment(DScene sc, const DBlock *__restrict__ blocks, uint32_t n_blocks, uint32_t block_size,
+                                                     uint32_t sample_count, float *__restrict__ film_base, unsigned long long *__restrict__ counters,
+                                                     const uint32_t *__restrict__ stop_flag) {
+    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];
+    lane_render<COUNT, FLAT, true, TEX_NONE>(sc, bvh_top, blocks, n_blocks, block_size, sample_count, film_base, counters, stop_flag);
 }
 // The ring machines (render_kernel_wga / render_kernel_wga_mis) with the moment tail in their NEW block; scalar streams, no counters.
 template <int WG, int NT, int WPE>
-__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_moment(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
-                                                                  uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
-                                                                  unsigned long long *counters, const uint32_t *stop_flag,
-                                                                  const uint32_t *tiles, uint32_t n_tiles) {
+__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_moment(MTS_WG_PARAMS) {
     Counters cnt = {};
-    ring_workgroup_async<VolpathRing<false, WG, false, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+    ring_workgroup_async<VolpathRingMoment<WG>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
 }
 template <bool SPEC, int WG, int NT>
-__global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis_moment(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
-                                                                      uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
-                                                                      unsigned long long *counters, const uint32_t *stop_flag,
-                                                                      const uint32_t *tiles, uint32_t n_tiles) {
+__global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) render_kernel_wga_mis_moment(MTS_WG_PARAMS) {
     Counters cnt = {};
-    ring_workgroup_async<VolpathMisRing<false, SPEC, WG, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+    ring_workgroup_async<VolpathMisRingMoment<SPEC, WG>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
 }
 
 // ---- textured scenes (mts_scene_desc.textures) and scenes with a blendbsdf or a twosided: the per-lane kernels above with TEX = true -- every BSDF parameter of a hit goes
@@ -362,51 +362,20 @@ template <bool COUNT, bool FLAT>
 __global__ void __launch_bounds__(256, FLAT ? MTS_PATH_WAVES : MTS_NESTED_WAVES) render_kernel_tex(DScene sc, const DBlock *__restrict__ blocks, uint32_t n_blocks, uint32_t block_size,
                                                      uint32_t sample_count, float *__restrict__ film_base, unsigned long long *__restrict__ counters,
                                                      const uint32_t *__restrict__ stop_flag) {
-    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];             // as render_kernel
-    {
-        const int staged = min(sc.bvh_node_count, MTS_BVH_LDS_NODES);
-        for (int k = (int) threadIdx.x; k < staged * 8; k += (int) blockDim.x) bvh_top[k] = sc.bvh_nodes[k];
-        pm_tables_to_lds(threadIdx.x);
-        __syncthreads();
-        sc.bvh_lds = bvh_top; sc.bvh_lds_count = staged;
-    }
-    const uint32_t ppb = block_size * block_size;
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t b = gid / ppb, i = gid - b * ppb;
-    if (b >= n_blocks) return;
-    const DBlock blk = blocks[b];
-    float *__restrict__ film = film_base + (((size_t) blk.film_off_hi << 32) | blk.film_off_lo);
-    const uint32_t lx = compact_bits(i), ly = compact_bits(i >> 1);
-    if (lx >= (uint32_t) blk.sx || ly >= (uint32_t) blk.sy) return;
-    Pcg32 rng;
-    rng.seed(sc.sensor.seed + (uint64_t) blk.id * ppb + i, PCG32_DEFAULT_STREAM);
-    Counters cnt = {};
-    float acc[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };
-    if (FLAT) path_pixel_flat<COUNT, false, true>(sc, rng, blk, lx, ly, sample_count, film, acc, cnt, stop_flag);
-    else
-    for (uint32_t j = 0; j < sample_count; ++j) {
-        if ((j & 63u) == 63u && stop_requested(stop_flag)) break;
-        if (sc.sensor.wavefront) seed_wavefront_sample(rng, sc.sensor, blk, lx, ly, j);
-        render_sample<COUNT, NI_ANY, false, true>(sc, rng, blk, lx, ly, film, acc, cnt);
-    }
-    float *dst = film_entry(sc, blk, lx, ly, as_global(film));
-    for (int k = 0; k < 5; ++k) atomicAdd(dst + k, acc[k]);
-    if (COUNT) flush_counters(counters, cnt);
+    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];
+    lane_render<COUNT, FLAT, false, TEX_ON>(sc, bvh_top, blocks, n_blocks, block_size, sample_count, film_base, counters, stop_flag);
 }
 
 // `volpath` of a textured scene on the 1024-path rings (render_kernel_wga): the machine's SURFACE and BSDF blocks take the hit's BSDF
 // record through its textures; scalar streams, no counters.
 template <int WG, int NT, int WPE>
-__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_tex(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
-                                                               uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
-                                                               unsigned long long *counters, const uint32_t *stop_flag,
-                                                               const uint32_t *tiles, uint32_t n_tiles) {
+__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_tex(MTS_WG_PARAMS) {
     Counters cnt = {};
-    ring_workgroup_async<VolpathRing<false, WG, false, false, true>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
+    ring_workgroup_async<VolpathRingTex<WG>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
 }
 
-// SamplingIntegrator::sample for caller-supplied rays (librender/python/integrator_v.cpp:62-78); TEX: of a textured scene
-template <bool TEX>
+// SamplingIntegrator::sample for caller-supplied rays (librender/python/integrator_v.cpp:62-78); TEX: of a plain, a textured or an instanced scene
+template <int TEX>
 __global__ void __launch_bounds__(256) sample_kernel(DScene sc, int32_t n, uint64_t seed_offset, const float *__restrict__ rays /* 6 SoA rows */,
                                                      float *__restrict__ out_rgb, uint8_t *__restrict__ out_valid) {
     pm_tables_to_lds(threadIdx.x);
@@ -420,7 +389,9 @@ __global__ void __launch_bounds__(256) sample_kernel(DScene sc, int32_t n, uint6
     out_rgb[3 * i] = L.x; out_rgb[3 * i + 1] = L.y; out_rgb[3 * i + 2] = L.z; out_valid[i] = valid ? 1 : 0;
 }
 
-// Scene::ray_intersect for caller-supplied rays (librender/scene.cpp:117-125)
+// Scene::ray_intersect for caller-supplied rays (librender/scene.cpp:117-125).  INST: of an instanced scene (the two-level traversal of the INST kernels
+// below); a hit reports the member's index in mts_scene_desc.shapes, a miss -1 -- where the plain kernel reports what ray_intersect left in Hit::shape
+template <bool INST>
 __global__ void __launch_bounds__(256) intersect_kernel(DScene sc, int32_t n, const float *__restrict__ o, const float *__restrict__ d,
                                                         const float *__restrict__ mint, const float *__restrict__ maxt,
                                                         float *__restrict__ out_t, int32_t *__restrict__ out_shape, int32_t *__restrict__ out_prim,
@@ -430,14 +401,16 @@ __global__ void __launch_bounds__(256) intersect_kernel(DScene sc, int32_t n, co
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     DRay ray = make_ray(f3(o + 3 * i), f3(d + 3 * i), mint[i], maxt[i]);
-    Hit h = ray_intersect(sc, ray);
+    Hit h = ray_intersect<false, INST>(sc, ray);
     F3 nn = f3s(0.f);
-    int prim = -1;
+    int prim = -1, shape = -1;
+    if constexpr (!INST) shape = h.shape;
     if (hit_valid(h)) {
-        Surf sf; complete_surface(sc, h, ray.d, sf); nn = sf.n;
-        prim = sc.shapes[h.shape].type == MTS_SHAPE_SPHERE ? 0 : h.prim;
+        Surf sf; complete_surface<INST>(sc, h, ray.d, sf); nn = sf.n;
+        shape = hit_shape<INST>(h);
+        prim = sc.shapes[shape].type == MTS_SHAPE_SPHERE || (INST && sc.shapes[shape].type == MTS_SHAPE_CONE) ? 0 : h.prim;     // both park a float's bits there; cones: INST only
     }
-    out_t[i] = h.t; out_shape[i] = h.shape; out_prim[i] = prim;
+    out_t[i] = h.t; out_shape[i] = shape; out_prim[i] = prim;
     out_p[3 * i] = h.p.x; out_p[3 * i + 1] = h.p.y; out_p[3 * i + 2] = h.p.z;
     out_n[3 * i] = nn.x; out_n[3 * i + 1] = nn.y; out_n[3 * i + 2] = nn.z;
 }
@@ -451,80 +424,15 @@ template <bool COUNT, bool FLAT>
 __global__ void __launch_bounds__(256, FLAT ? 2 : MTS_NESTED_WAVES) render_kernel_inst(DScene sc, const DBlock *__restrict__ blocks, uint32_t n_blocks, uint32_t block_size,
                                                      uint32_t sample_count, float *__restrict__ film_base, unsigned long long *__restrict__ counters,
                                                      const uint32_t *__restrict__ stop_flag) {
-    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];             // as render_kernel: the SCENE level's top nodes (bvh_node_count counts that level alone)
-    {
-        const int staged = min(sc.bvh_node_count, MTS_BVH_LDS_NODES);
-        for (int k = (int) threadIdx.x; k < staged * 8; k += (int) blockDim.x) bvh_top[k] = sc.bvh_nodes[k];
-        pm_tables_to_lds(threadIdx.x);
-        __syncthreads();
-        sc.bvh_lds = bvh_top; sc.bvh_lds_count = staged;
-    }
-    const uint32_t ppb = block_size * block_size;
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t b = gid / ppb, i = gid - b * ppb;
-    if (b >= n_blocks) return;
-    const DBlock blk = blocks[b];
-    float *__restrict__ film = film_base + (((size_t) blk.film_off_hi << 32) | blk.film_off_lo);
-    const uint32_t lx = compact_bits(i), ly = compact_bits(i >> 1);
-    if (lx >= (uint32_t) blk.sx || ly >= (uint32_t) blk.sy) return;
-    Pcg32 rng;
-    rng.seed(sc.sensor.seed + (uint64_t) blk.id * ppb + i, PCG32_DEFAULT_STREAM);
-    Counters cnt = {};
-    float acc[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };
-    if (FLAT) path_pixel_flat<COUNT, false, TEX_INST>(sc, rng, blk, lx, ly, sample_count, film, acc, cnt, stop_flag);
-    else
-    for (uint32_t j = 0; j < sample_count; ++j) {
-        if ((j & 63u) == 63u && stop_requested(stop_flag)) break;
-        if (sc.sensor.wavefront) seed_wavefront_sample(rng, sc.sensor, blk, lx, ly, j);
-        render_sample<COUNT, NI_ANY, false, TEX_INST>(sc, rng, blk, lx, ly, film, acc, cnt);
-    }
-    float *dst = film_entry(sc, blk, lx, ly, as_global(film));
-    for (int k = 0; k < 5; ++k) atomicAdd(dst + k, acc[k]);
-    if (COUNT) flush_counters(counters, cnt);
+    __shared__ float bvh_top[MTS_BVH_LDS_NODES * 8];
+    lane_render<COUNT, FLAT, false, TEX_INST>(sc, bvh_top, blocks, n_blocks, block_size, sample_count, film_base, counters, stop_flag);
 }
 // `volpath` of an instanced scene on the 1024-path rings: the INTERSECT block runs the two-level traversal, the SURFACE and BSDF blocks resolve
 // the instance per lane ahead of their waterfalls over shapes; scalar streams, no counters.
 template <int WG, int NT, int WPE>
-__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_inst(DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size,
-                                                                uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride,
-                                                                unsigned long long *counters, const uint32_t *stop_flag,
-                                                                const uint32_t *tiles, uint32_t n_tiles) {
+__global__ void __launch_bounds__(NT, WPE) render_kernel_wga_inst(MTS_WG_PARAMS) {
     Counters cnt = {};
-    ring_workgroup_async<VolpathRing<false, WG, false, false, TEX_INST>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
-}
-// sample_kernel / intersect_kernel of an instanced scene (a hit reports the member's index in mts_scene_desc.shapes)
-__global__ void __launch_bounds__(256) sample_kernel_inst(DScene sc, int32_t n, uint64_t seed_offset, const float *__restrict__ rays /* 6 SoA rows */,
-                                                          float *__restrict__ out_rgb, uint8_t *__restrict__ out_valid) {
-    pm_tables_to_lds(threadIdx.x);
-    __syncthreads();
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Pcg32 rng; rng.seed(sc.sensor.seed + seed_offset + (uint64_t) i, PCG32_DEFAULT_STREAM);
-    DRay ray = make_ray(f3(rays[i], rays[n + i], rays[2 * n + i]), f3(rays[3 * n + i], rays[4 * n + i], rays[5 * n + i]), MTS_RAY_EPSILON, pm_inf());
-    bool valid; Counters cnt;
-    F3 L = integrator_sample<false, NI_ANY, TEX_INST>(sc, rng, ray, sc.sensor.medium, valid, cnt);
-    out_rgb[3 * i] = L.x; out_rgb[3 * i + 1] = L.y; out_rgb[3 * i + 2] = L.z; out_valid[i] = valid ? 1 : 0;
-}
-__global__ void __launch_bounds__(256) intersect_kernel_inst(DScene sc, int32_t n, const float *__restrict__ o, const float *__restrict__ d,
-                                                             const float *__restrict__ mint, const float *__restrict__ maxt,
-                                                             float *__restrict__ out_t, int32_t *__restrict__ out_shape, int32_t *__restrict__ out_prim,
-                                                             float *__restrict__ out_p, float *__restrict__ out_n) {
-    pm_tables_to_lds(threadIdx.x);
-    __syncthreads();
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    DRay ray = make_ray(f3(o + 3 * i), f3(d + 3 * i), mint[i], maxt[i]);
-    Hit h = ray_intersect<false, true>(sc, ray);
-    F3 nn = f3s(0.f);
-    int prim = -1, shape = -1;
-    if (hit_valid(h)) {
-        Surf sf; complete_surface<true>(sc, h, ray.d, sf); nn = sf.n;
-        shape = hit_shape<true>(h);
-        prim = sc.shapes[shape].type == MTS_SHAPE_SPHERE || sc.shapes[shape].type == MTS_SHAPE_CONE ? 0 : h.prim;     // both park a float's bits there
-    }
-    out_t[i] = h.t; out_shape[i] = shape; out_prim[i] = prim;
-    out_p[3 * i] = h.p.x; out_p[3 * i + 1] = h.p.y; out_p[3 * i + 2] = h.p.z;
-    out_n[3 * i] = nn.x; out_n[3 * i + 1] = nn.y; out_n[3 * i + 2] = nn.z;
+    ring_workgroup_async<VolpathRingInst<WG>, NT>((const MTS_CONST_AS void *) __builtin_amdgcn_kernarg_segment_ptr(), cnt);
 }
 
 // sample_tea_32 / sample_tea_64 / sample_tea_float32 for n (v0, v1) pairs (core/random.h:75-140)
@@ -691,25 +599,20 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
     return hipErrorInvalidConfiguration;
 #else                         // the general kernels
 #if MTS_SPEC_N == 3
-    if (a.moment) {                                            // the `moment` wrapper: a.variant is kv::moment_variant() of the table's row (capi.cpp)
-        if (a.variant != kv::moment_variant(a.variant, integ, a.sc->sensor.wavefront != 0, a.count)) return hipErrorInvalidConfiguration;
-        if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, render_kernel_wga_moment<1024, 1024, 4>);
-        if (a.variant == kv::ring(512)) return launch_wg(a, threads, 512, 512, spec_mis ? render_kernel_wga_mis_moment<true, 512, 512> : render_kernel_wga_mis_moment<false, 512, 512>);
-        if (a.variant == kv::FLAT) return launch_lane(a, threads, render_kernel_moment<false, true>);
-        return launch_lane(a, threads, a.count ? render_kernel_moment<true, false> : render_kernel_moment<false, false>);
-    }
-    if (a.instanced) {                                         // an instanced scene: mapped from the table's row as a textured scene is, to the INST kernels
-        if (a.moment || !a.textured || a.sc->instances == nullptr) return hipErrorInvalidConfiguration;
-        if (a.variant != kv::textured_variant(a.variant, integ, a.sc->sensor.wavefront != 0, a.count)) return hipErrorInvalidConfiguration;
-        if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, render_kernel_wga_inst<1024, 1024, 4>);
-        if (a.variant == kv::FLAT) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel_inst, true));
-        return launch_lane(a, threads, MTS_BY_COUNT(render_kernel_inst, false));
-    }
-    if (a.textured) {                                          // a textured scene: a.variant is kv::textured_variant() of the table's row (capi.cpp)
-        if (a.variant != kv::textured_variant(a.variant, integ, a.sc->sensor.wavefront != 0, a.count)) return hipErrorInvalidConfiguration;
-        if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, render_kernel_wga_tex<1024, 1024, 4>);
-        if (a.variant == kv::FLAT) return launch_lane(a, threads, MTS_BY_COUNT(render_kernel_tex, true));
-        return launch_lane(a, threads, MTS_BY_COUNT(render_kernel_tex, false));
+    // The kernel families with names of their own: the `moment` wrapper (it goes first), instanced scenes -- mapped from the table's row as textured scenes are,
+    // to the INST kernels -- and textured scenes.  a.variant is kv::moment_variant() or kv::textured_variant() of the table's row (capi.cpp).
+    if (a.moment || a.instanced || a.textured) {
+        if (!a.moment && a.instanced && (!a.textured || a.sc->instances == nullptr)) return hipErrorInvalidConfiguration;
+        const bool wavefront = a.sc->sensor.wavefront != 0;
+        if (a.variant != (a.moment ? kv::moment_variant(a.variant, integ, wavefront, a.count) : kv::textured_variant(a.variant, integ, wavefront, a.count))) return hipErrorInvalidConfiguration;
+        struct Family { WgKernel ring; LaneKernel flat, nested; };      // a family's 1024-path ring kernel, flat `path` loop and nested kernel
+        const Family f = a.moment    ? Family{ render_kernel_wga_moment<1024, 1024, 4>, render_kernel_moment<false, true>, MTS_BY_COUNT(render_kernel_moment, false) }   // its flat row never counts (kv::moment_variant)
+                       : a.instanced ? Family{ render_kernel_wga_inst<1024, 1024, 4>, MTS_BY_COUNT(render_kernel_inst, true), MTS_BY_COUNT(render_kernel_inst, false) }
+                                     : Family{ render_kernel_wga_tex<1024, 1024, 4>, MTS_BY_COUNT(render_kernel_tex, true), MTS_BY_COUNT(render_kernel_tex, false) };
+        if (a.variant == kv::ring(1024)) return launch_wg(a, threads, 1024, 1024, f.ring);
+        if (a.variant == kv::ring(512))                        // `moment` alone: kv::textured_variant() maps to no such ring
+            return launch_wg(a, threads, 512, 512, spec_mis ? render_kernel_wga_mis_moment<true, 512, 512> : render_kernel_wga_mis_moment<false, 512, 512>);
+        return launch_lane(a, threads, a.variant == kv::FLAT ? f.flat : f.nested);
     }
     if (kv::is_ring(a.variant) && volpath) {                      // asynchronous regrouping
         if (a.sc->sensor.wavefront)                           // gpu_* streams: the instantiation that recomputes the generator's increment (wg_block, WF)
@@ -748,23 +651,16 @@ hipError_t MTS_LAUNCHER(launch_render)(const RenderArgs &a) {
 
 hipError_t launch_sample(const DScene &sc, int32_t n, uint64_t seed_offset, const float *d_rays, float *d_rgb, uint8_t *d_valid, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    if (sc.instances != nullptr) {                             // an instanced scene
-        if (sc.bsdf_tex == nullptr) return hipErrorInvalidConfiguration;
-        hipLaunchKernelGGL(sample_kernel_inst, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(sc.bsdf_tex != nullptr ? sample_kernel<true> : sample_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
+    if (sc.instances != nullptr && sc.bsdf_tex == nullptr) return hipErrorInvalidConfiguration;      // an instanced scene renders as a textured one
+    hipLaunchKernelGGL(sc.instances != nullptr ? sample_kernel<TEX_INST> : sc.bsdf_tex != nullptr ? sample_kernel<TEX_ON> : sample_kernel<TEX_NONE>,
+                       dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, seed_offset, d_rays, d_rgb, d_valid);
     return hipGetLastError();
 }
 
 hipError_t launch_intersect(const DScene &sc, int32_t n, const float *o, const float *d, const float *mint, const float *maxt,
                             float *t, int32_t *shape, int32_t *prim, float *p, float *nn, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    if (sc.instances != nullptr) {                             // an instanced scene
-        hipLaunchKernelGGL(intersect_kernel_inst, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, o, d, mint, maxt, t, shape, prim, p, nn);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, o, d, mint, maxt, t, shape, prim, p, nn);
+    hipLaunchKernelGGL(sc.instances != nullptr ? intersect_kernel<true> : intersect_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, n, o, d, mint, maxt, t, shape, prim, p, nn);
     return hipGetLastError();
 }
 #endif // MTS_SPEC_N == 3

@@ -1307,6 +1307,10 @@ struct WgArgs {
     // finished early and four fifths of the paths of such a workgroup were done while the rest kept it (and its 16 waves) resident.
     const uint32_t *tiles; uint32_t n_tiles;
 };
+// ... and the parameter list of every ring kernel (kernels.hip), which WgArgs mirrors field by field
+#define MTS_WG_PARAMS DScene sc, const DBlock *blocks, uint32_t n_blocks, uint32_t block_size, uint32_t sample_count, float *film, float *cold_g, uint32_t cold_stride, \
+                      unsigned long long *counters, const uint32_t *stop_flag, const uint32_t *tiles, uint32_t n_tiles
+static_assert(sizeof(WgArgs) % 4 == 0, "WgArgs mirrors the kernel parameters");
 #define MTS_TILE_PIXELS 16u
 
 template <int WG>
@@ -1467,6 +1471,10 @@ struct VolpathRing {
     // the block function itself, not a forwarding function: one more layer of inlining changed the code of the flagship kernel
     template <int C> static constexpr auto block = &wg_block<COUNT_, WG_, C, WF, MOMENT, TEX>;
 };
+// the machines of render_kernel_wga_moment / _tex / _inst (rgb / mono general unit): scalar streams, no counters
+template <int WG> using VolpathRingMoment = VolpathRing<false, WG, false, true>;
+template <int WG> using VolpathRingTex = VolpathRing<false, WG, false, false, TEX_ON>;
+template <int WG> using VolpathRingInst = VolpathRing<false, WG, false, false, TEX_INST>;
 
 } // inline namespace
 } // namespace mtsamd

@@ -555,6 +555,7 @@ struct VolpathMisRing {
     }
     template <int C> static constexpr auto block = &mis_block<COUNT_, SPEC, WG_, C, MOMENT>;
 };
+template <bool SPEC, int WG> using VolpathMisRingMoment = VolpathMisRing<false, SPEC, WG, true>;      // the machine of render_kernel_wga_mis_moment: no counters
 
 } // inline namespace
 } // namespace mtsamd

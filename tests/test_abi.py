@@ -54,17 +54,19 @@ def test_missing_library_fails_loudly(monkeypatch):
         A.lib()
 
 
-def test_default_kernel_resource_budget(tmp_path):
-    """Guards the default render kernel against silent code-generation regressions (a reference to the kernel-argument record
-    handed to a real function once put the whole record in scratch memory and cost 2.4x): reads the code object's own metadata."""
-    import re
-    import shutil
+_KERNEL_NOTES = {}
+
+
+def kernel_notes(tmp_path):
+    """{mangled kernel name: resources} of every kernel of the library, from the notes of its code objects; read once per library"""
     import subprocess
+    lib = os.environ.get("MTSAMD_LIB") or os.path.join(ROOT, "eradiate-kernel_amd", "libmtsamd.so")
+    if lib in _KERNEL_NOTES:
+        return _KERNEL_NOTES[lib]
     llvm = "/opt/rocm/lib/llvm/bin"
     tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
     if not all(os.path.exists(t) for t in tools):
         pytest.skip("ROCm LLVM tools not found")
-    lib = os.environ.get("MTSAMD_LIB") or os.path.join(ROOT, "eradiate-kernel_amd", "libmtsamd.so")
     fat = str(tmp_path / "fat.bin")
     subprocess.run([tools[0], "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
     # the section holds one offload bundle per translation unit with device code (kernels.hip: rgb / mono, kernels_spectral.hip: spectral,
@@ -83,6 +85,14 @@ def test_default_kernel_resource_budget(tmp_path):
             name = re.search(r"\.name:\s+(\S+)", block).group(1)
             kernels[name] = {f: int(re.search(r"\.%s:\s+(\d+)" % f, block).group(1))
                              for f in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count")}
+    _KERNEL_NOTES[lib] = kernels
+    return kernels
+
+
+def test_default_kernel_resource_budget(tmp_path):
+    """Guards the default render kernel against silent code-generation regressions (a reference to the kernel-argument record
+    handed to a real function once put the whole record in scratch memory and cost 2.4x): reads the code object's own metadata."""
+    kernels = kernel_notes(tmp_path)
     # measured slower and removed (DESIGN.md section 5): the lane-affine driver, and `volpath` machines with fewer threads than paths
     assert not [k for k in kernels if "render_kernel_wgl" in k], sorted(kernels)
     for k in kernels:
@@ -134,6 +144,38 @@ def test_default_kernel_resource_budget(tmp_path):
     # the spectral variant's volpath: 256 paths x 42 state dwords, three workgroups per CU
     sp = one("10v_spectral17render_kernel_wgaILb0ELi256ELi256ELi2ELb0E")
     assert sp["vgpr_count"] <= 168 and sp["vgpr_spill_count"] == 0 and 3 * sp["group_segment_fixed_size"] <= 160 * 1024, sp
+
+
+def demangled_kernel(mangled):
+    """`_ZN6mtsamd5v_rgb13render_kernelILb0ELb1ELi0EEEv...` -> `mtsamd::v_rgb::render_kernel<false, true, 0>`: a nested name whose last part may
+    carry template arguments, all of them bool or int literals -- what every kernel of the library is; anything else is an error, not a guess"""
+    assert mangled.startswith("_ZN"), mangled
+    at, parts = 3, []
+    while mangled[at].isdigit():
+        n = re.match(r"\d+", mangled[at:]).group(0)
+        parts.append(mangled[at + len(n):at + len(n) + int(n)])
+        at += len(n) + int(n)
+    name = "::".join(parts)
+    if mangled[at] == "I":
+        args = re.match(r"I((?:L[bi]\d+E)+)E", mangled[at:])
+        assert args, mangled
+        lits = re.findall(r"L([bi])(\d+)E", args.group(1))
+        name += "<%s>" % ", ".join(("true" if v != "0" else "false") if t == "b" else v for t, v in lits)
+        at += len(args.group(0))
+    assert mangled[at] == "E", mangled
+    return name
+
+
+def test_kernel_names_of_the_rgb_unit(tmp_path):
+    """The kernels of the rgb / mono general unit (namespace v_rgb) are the committed list, name for name: bench.py, tools/step_loop_stats.py
+    and the scripts behind profiles/ pick kernels by these names, and a renamed or vanished instantiation would pass them by silently.
+    Needs what the resource test needs and nothing else: the names are demangled here."""
+    assert demangled_kernel("_ZN6mtsamd5v_rgb13render_kernelILb0ELb1ELi0EEEvNS_6DSceneE") == "mtsamd::v_rgb::render_kernel<false, true, 0>"
+    assert demangled_kernel("_ZN6mtsamd5v_rgb10tea_kernelEiPKjS2_iPjPmPf") == "mtsamd::v_rgb::tea_kernel"
+    names = sorted(demangled_kernel(k) for k in kernel_notes(tmp_path) if "6mtsamd5v_rgb" in k)
+    with open(os.path.join(ROOT, "tests", "golden", "kernel_names_v_rgb.txt")) as f:
+        expected = f.read().split("\n")[:-1]
+    assert names == expected, (sorted(set(names) - set(expected)), sorted(set(expected) - set(names)))
 
 
 def test_scene_traits(L):

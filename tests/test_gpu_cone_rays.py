@@ -1,4 +1,4 @@
-"""The `cone` shape per ray on the device (run with -m gpu on an MI355X): mts_ray_intersect -> intersect_kernel_inst -> inst_intersect ->
+"""The `cone` shape per ray on the device (run with -m gpu on an MI355X): mts_ray_intersect -> intersect_kernel<true> -> inst_intersect ->
 cone_intersect_v, hit_point, complete_surface (csrc/integrator_dev.h).  Inputs, reference and exclusion rules: tests/cone_ref.py; their
 conditions are asserted on the CPU in tests/test_cone.py.
 

@@ -1,7 +1,7 @@
 """Instanced intersection per ray on the device (run with -m gpu on an MI355X); the inputs and their conditions: tests/instance_rays.py,
 tests/test_instance_rays.py.
 
-(a) exact: on dyadic placements the device's t, member and primitive (mts_ray_intersect: intersect_kernel_inst, inst_intersect,
+(a) exact: on dyadic placements the device's t, member and primitive (mts_ray_intersect: intersect_kernel<true>, inst_intersect,
 hit_point) are the oracle's on the expanded plain scene, bit for bit, on every ray of the four sets; (b) general placements against
 the float64 restatement within 8 x the fp32 scale measured on the dyadic scene; (c) the four list / BVH combinations of the two
 levels; (d) shadow rays with a finite maxt (ray_test<true>) through every kernel row, against a closed form."""
