@@ -379,13 +379,9 @@ def load_dict(d, device=0):
     if isinstance(d, dict) and d.get("type") in ("nbins", "bins", "moment"):
         # the reference's tests construct these integrators on their own (src/integrators/tests/test_bins.py:10-53): validated like
         # inside a scene, and good for aov_names()
-        from . import scene_dict as SD
-        b = SD.SceneBuilder(); b.spectra = []
-        SD._SPECTRAL = b if variant() == "gpu_spectral" else None
-        try:
-            b.set_integrator(d, "integrator")
-        finally:
-            SD._SPECTRAL = None
+        from .scene_dict import SceneBuilder
+        b = SceneBuilder(spectral=variant() == "gpu_spectral")
+        b.set_integrator(d, "integrator")
         return _DetachedIntegrator(b.aov_names)
     desc, keep = build_scene_desc(d, mono=(variant() == "gpu_mono"), spectral=(variant() == "gpu_spectral"))
     return Scene(desc, keep, device)

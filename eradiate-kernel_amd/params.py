@@ -221,13 +221,13 @@ class ParameterMap:
                                            % (key, want, rec.nz, rec.ny, rec.nx, rec.channels, value.numel()))
                     return value, int(value.data_ptr())
                 value = value.detach().numpy()
-            data, mono_max = SD._grid_data(value)
+            data, mono_max = self._keep._grid_data(value)
             if data.shape != (rec.nz, rec.ny, rec.nx, rec.channels):
                 raise RuntimeError("\"%s\": 'size' / 'channels' cannot change: the grid is (nz, ny, nx, channels) = %s, got %s"
                                    % (key, (rec.nz, rec.ny, rec.nx, rec.channels), data.shape))
             return (data, mono_max), None
         if p.what == "texels":
-            data = SD._bitmap_data(value)
+            data = self._keep._bitmap_data(value)
             if data.shape != (rec.height, rec.width, rec.channels):
                 raise RuntimeError("\"%s\": 'resolution' / 'channels' differ from what the scene was created with (the topology of a scene is frozen): "
                                    "the bitmap is (height, width, channels) = %s, got %s" % (key, (rec.height, rec.width, rec.channels), data.shape))
@@ -238,7 +238,7 @@ class ParameterMap:
                 raise RuntimeError("\"%s\": the table length ('tab_count') cannot change: %d entries, got %d" % (key, rec.tab_count, arr.size))
             return arr, None
         if p.what == "rgb":
-            return SD._color(value, p.where, emitter=p.emitter), None
+            return self._keep._color(value, p.where, emitter=p.emitter), None
         if p.what == "weight":
             return (SD._weight(value, p.where),) * 3, None
         if p.what == "eta":                                     # dielectric.cpp:323: the relative index of refraction, a plain float
@@ -262,16 +262,11 @@ class ParameterMap:
         if not pending:
             return
         keep, desc = self._keep, self._desc
-        with SD._BUILD_LOCK:                                    # the conversion helpers read the variant from module state, as at load
-            SD._MONO, SD._SPECTRAL = keep.mono, (keep if keep.spectral else None)
-            try:
-                # a grid marked by set_dirty alone whose data lives in a device tensor (the description no longer points at host data)
-                # goes down as that tensor again
-                pending = {k: (keep.grids[self.properties[k].index] if v is None and self.properties[k].what == "grid"
-                               and _is_tensor(keep.grids[self.properties[k].index]) else v) for k, v in pending.items()}
-                new = {k: (self._convert(k, self.properties[k], v) if v is not None else None) for k, v in pending.items()}
-            finally:
-                SD._MONO, SD._SPECTRAL = False, None
+        # a grid marked by set_dirty alone whose data lives in a device tensor (the description no longer points at host data)
+        # goes down as that tensor again
+        pending = {k: (keep.grids[self.properties[k].index] if v is None and self.properties[k].what == "grid"
+                       and _is_tensor(keep.grids[self.properties[k].index]) else v) for k, v in pending.items()}
+        new = {k: (self._convert(k, self.properties[k], v) if v is not None else None) for k, v in pending.items()}
         undo, dirty, alive = [], {}, []
 
         def put(rec, field, value):

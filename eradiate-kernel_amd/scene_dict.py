@@ -10,7 +10,6 @@ Only the plugins of the path / volpath hot path are known (SURVEY.md section 8(b
 """
 import ctypes as C
 import math
-import threading
 
 import numpy as np
 
@@ -79,132 +78,7 @@ def _xf(t):
     return r
 
 
-_MONO = False      # set by build_scene_desc(mono=True): colours become their luminance (src/spectra/srgb.cpp in *_mono variants)
-_BUILD_LOCK = threading.RLock()
-_SPECTRAL = None   # set by build_scene_desc(spectral=True): the SceneBuilder that collects the scene's spectra
-
-
 WAVELENGTH_MIN, WAVELENGTH_MAX = 280.0, 2400.0       # MTS_WAVELENGTH_MIN / MAX, include/mitsuba/core/spectrum.h:15-21
-
-
-def _spectrum(v, where, default=None, emitter=False):
-    """Spectral variant: a colour parameter -> index of its spectrum record (mts_spectrum).
-    float -> `uniform` (Properties::texture, properties.h:275-296); {"type": "uniform" | "regular" | "d65"} -> the plugin of that
-    name (src/spectra/*.cpp; d65 expands to regular, d65.cpp:52-71); {"type": "spectrum", "value": c} -> uniform, or d65 scaled by c
-    inside an emitter (create_texture_from_spectrum, xml.cpp:1087-1111); a missing emitter spectrum is D65 (directional.cpp:49,
-    area.cpp:39, constant.cpp:33, point.cpp:47).  rgb colours need the sRGB upsampling model, whose data (ext/rgb2spec) is absent."""
-    b = _SPECTRAL
-    if v is None:
-        v = {"type": "d65"} if (emitter and default is None) else default
-    rec = A.Spectrum()
-    rec.lambda_min, rec.lambda_max = WAVELENGTH_MIN, WAVELENGTH_MAX
-    if isinstance(v, dict):
-        p = Props(v, where)
-        t = p.type
-        if t == "spectrum":
-            val = _spectrum_pairs(v, where)                                 # inline pairs or spectrum_from_file (xml.cpp:823-851)
-            if p.has("filename"):
-                p.get("filename")
-            if val is None:
-                val = p.get("value", 1.0)
-            elif p.has("value"):
-                p.get("value")
-            if isinstance(val, (list, tuple)):
-                # create_texture_from_spectrum, xml.cpp:1113-1150 (spectral mode): values scaled by MTS_CIE_Y_NORMALIZATION inside an
-                # emitter; `regular` when the wavelengths are equidistant (to math::Epsilon), `irregular` otherwise
-                pairs = np.asarray(val, np.float64).reshape(-1, 2)
-                f = np.float32
-                wl = pairs[:, 0].astype(np.float32)
-                vals = (pairs[:, 1].astype(np.float32) * (f(1.0 / 106.7502593994140625) if emitter else f(1.0))).astype(np.float32)
-                dist = np.diff(wl)
-                if (dist < 0).any():
-                    raise RuntimeError("Wavelengths must be specified in increasing order!")
-                p.finish()
-                if wl.size >= 2 and (np.abs(dist - dist[0]) <= 2.0 ** -24).all():
-                    return _spectrum({"type": "regular", "lambda_min": float(wl[0]), "lambda_max": float(wl[-1]), "values": vals}, where)
-                return _spectrum({"type": "irregular", "wavelengths": wl, "values": vals}, where)
-            p.finish()
-            return _spectrum({"type": "d65", "scale": float(val)} if emitter else {"type": "uniform", "value": float(val)}, where)
-        if t == "uniform":
-            rec.type = A.SPECTRUM_UNIFORM
-            rec.value = float(p.get("value", 1.0))
-            if p.has("lambda_min"):
-                rec.lambda_min = max(float(p.get("lambda_min")), WAVELENGTH_MIN)
-            if p.has("lambda_max"):
-                rec.lambda_max = min(float(p.get("lambda_max")), WAVELENGTH_MAX)
-            if not rec.lambda_min < rec.lambda_max:
-                raise RuntimeError("UniformSpectrum: 'lambda_min' must be less than 'lambda_max'")
-        elif t in ("regular", "d65"):
-            rec.type = A.SPECTRUM_REGULAR
-            if t == "d65":
-                from .spectra_data import D65, D65_NORMALIZATION
-                f = np.float32
-                scale = f(f(p.get("scale", 1.0)) * f(D65_NORMALIZATION))                  # d65.cpp:56-57: m_scale *= 1.f / 10568.f
-                values = (np.asarray(D65, np.float32) * scale).astype(np.float32)         # :64-65
-                rec.lambda_min, rec.lambda_max = 360.0, 830.0
-            else:
-                if not (p.has("lambda_min") and p.has("lambda_max")):
-                    raise RuntimeError("Property \"lambda_min\" has not been specified!" if not p.has("lambda_min") else "Property \"lambda_max\" has not been specified!")
-                rec.lambda_min, rec.lambda_max = float(p.get("lambda_min")), float(p.get("lambda_max"))
-                vals = p.get("values")
-                if isinstance(vals, str):
-                    vals = [float(x) for x in vals.replace(",", " ").split()]
-                values = np.asarray(vals, np.float32).reshape(-1)
-            values = np.ascontiguousarray(values, np.float32)
-            b.keep.append(values)
-            rec.values = values.ctypes.data_as(A.fp)
-            rec.count = int(values.size)
-        elif t in ("irregular", "discrete"):
-            # spectra/irregular.cpp:33-63 (strings of comma-separated numbers, or arrays), spectra/discrete.cpp:45-100
-            def numbers(key, default=None):
-                x = p.get(key, default)
-                if x is None:
-                    raise RuntimeError("Property \"%s\" has not been specified!" % key)
-                if isinstance(x, str):
-                    try:
-                        x = [float(tok) for tok in x.replace(",", " ").split()]
-                    except ValueError as e:
-                        raise RuntimeError("Could not parse floating point value '%s'" % str(e).split("'")[-2])
-                return np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1), np.float32)
-            wl = numbers("wavelengths")
-            if t == "irregular":
-                rec.type = A.SPECTRUM_IRREGULAR
-                values = numbers("values")
-                if values.size != wl.size:
-                    raise RuntimeError("IrregularSpectrum: 'wavelengths' and 'values' parameters must have the same size!")
-                pmf = None
-            else:
-                rec.type = A.SPECTRUM_DISCRETE
-                values, pmf = numbers("values", "1"), numbers("pmf", "1")
-                if values.size == 1:
-                    values = np.full(wl.size, values[0], np.float32)
-                if pmf.size == 1:
-                    pmf = np.full(wl.size, pmf[0], np.float32)
-                if values.size != wl.size:
-                    raise RuntimeError("DiscreteSpectrum: 'wavelengths' and 'values' parameters must have the same size!")
-                if pmf.size != wl.size:
-                    raise RuntimeError("DiscreteSpectrum: 'wavelengths' and 'pmf' parameters must have the same size!")
-                b.keep.append(pmf)
-                rec.pmf = pmf.ctypes.data_as(A.fp)
-            b.keep.append(wl); b.keep.append(values)
-            rec.wavelengths = wl.ctypes.data_as(A.fp)
-            rec.values = values.ctypes.data_as(A.fp)
-            rec.count = int(wl.size)
-        elif t in ("rgb", "srgb", "srgb_d65"):
-            raise RuntimeError("rgb colours cannot be used in the spectral variant: the sRGB upsampling model needs the coefficient data of "
-                               "ext/rgb2spec, absent here; give a 'uniform' or 'regular' spectrum instead (%s)" % where)
-        else:
-            raise RuntimeError("Unsupported spectrum plugin \"%s\" in %s" % (t, where))
-        p.finish()
-    else:
-        c = np.asarray(v, dtype=np.float32).reshape(-1)
-        if c.size != 1:
-            raise RuntimeError("Cannot interpret %r as a spectrum in %s (spectral variant)" % (v, where))
-        rec.type = A.SPECTRUM_UNIFORM
-        rec.value = float(c[0])
-    b.spectra.append(rec)
-    b.spectrum_plugins.append(v.get("type") if isinstance(v, dict) else "uniform")      # traverse(): the keys of that plugin
-    return len(b.spectra) - 1
 
 
 def spectrum_from_file(filename):
@@ -289,14 +163,12 @@ CIE_Y_NORMALIZATION = 1.0 / 106.856895                     # MTS_CIE_Y_NORMALIZA
 _UNBOUNDED_NAMES = ("eta", "k", "int_ior", "ext_ior")      # is_unbounded_spectrum, xml.cpp:142-144
 
 
-def _color(v, where, default=None, emitter=False):
-    """float | [r,g,b] | {"type":"rgb","value":..} | {"type":"spectrum"/"uniform","value":x} -> (r,g,b)."""
-    c = _color_rgb(v, where, default, emitter)
-    if _MONO and not (c[0] == c[1] == c[2]):
-        f = np.float32
-        lum = float(f(f(f(c[0]) * f(0.212671) + f(c[1]) * f(0.715160)) + f(c[2]) * f(0.072169)))      # spectrum.h:246-248
-        return (lum, lum, lum)
-    return c
+def _luminance(c):
+    """spectrum.h:246-248 over the last axis of an array of linear rgb, in float32: (r * 0.212671 + g * 0.715160) + b * 0.072169, every
+    product and sum rounded to float32 -- one colour, the voxels of a grid or the texels of a bitmap under the *_mono variants."""
+    f = np.float32
+    c = np.asarray(c, dtype=np.float32)
+    return (c[..., 0] * f(0.212671) + c[..., 1] * f(0.715160)) + c[..., 2] * f(0.072169)
 
 
 def _color_rgb(v, where, default=None, emitter=False):
@@ -444,26 +316,6 @@ def parse_fov(p, aspect):
     return float(np.float32(result))
 
 
-def _grid_data(data):
-    """A grid's values as the description holds them: float32, C order, (nz, ny, nx, channels).  Returns (array, mono_max): under the
-    *_mono variants a colour grid becomes its luminance per voxel and keeps the file's maximum as its majorant (grid3d.cpp:157-179)."""
-    data = np.asarray(data, dtype=np.float32)
-    if data.ndim == 3:
-        data = data[..., None]
-    data = np.ascontiguousarray(data, dtype=np.float32)
-    if data.ndim != 4:
-        raise RuntimeError("gridvolume: data must have shape (nz, ny, nx, channels)")
-    mono_max = None
-    if _MONO and data.shape[3] == 3:
-        # grid3d.cpp:178-179: *_mono variants return the luminance of the interpolated colour. Luminance is
-        # linear, so it is applied per voxel here; the majorant stays the file's maximum (volume metadata).
-        mono_max = float(data.max()) if data.size else 0.0
-        f = np.float32
-        data = np.ascontiguousarray(((data[..., 0] * f(0.212671) + data[..., 1] * f(0.715160))
-                                     + data[..., 2] * f(0.072169))[..., None], dtype=np.float32)
-    return data, mono_max
-
-
 TEXTURE_PLUGINS = ("bitmap", "checkerboard")
 
 
@@ -478,27 +330,6 @@ def _to_uv(t):
         t = ScalarTransform4f(np.asarray(t, dtype=np.float32))
     m = np.asarray(t.matrix, np.float32).reshape(4, 4)
     return [float(x) for x in (m[0, 0], m[0, 1], m[0, 3], m[1, 0], m[1, 1], m[1, 3], 0.0, 0.0, m[3, 3])]
-
-
-def _bitmap_data(data):
-    """A bitmap's texels as the description holds them: float32, C order, (height, width, channels), channels 1 or 3.  Under the
-    *_mono variants rgb texels become their luminance (bitmap.cpp:278-279; luminance is linear, so it commutes with the filter)."""
-    data = np.asarray(data, dtype=np.float32)
-    if data.ndim == 2:
-        data = data[..., None]
-    if data.ndim != 3:
-        raise RuntimeError("bitmap: data must have shape (height, width) or (height, width, channels)")
-    if data.shape[2] not in (1, 3):
-        raise RuntimeError("Unsupported channel count: %d (expected 1 or 3)" % data.shape[2])                  # bitmap.cpp:196
-    if data.shape[0] < 2 or data.shape[1] < 2:
-        # bitmap.cpp:155-161 up-samples such an image with a tent filter, which this backend has not got
-        raise RuntimeError("bitmap: Image must be at least 2x2 pixels in size (got %dx%d; this backend does not up-sample)" % (data.shape[1], data.shape[0]))
-    if np.isnan(data).any():
-        raise RuntimeError("bitmap: data contains NaN")
-    if _MONO and data.shape[2] == 3:
-        f = np.float32
-        data = ((data[..., 0] * f(0.212671) + data[..., 1] * f(0.715160)) + data[..., 2] * f(0.072169))[..., None]      # spectrum.h:246-248
-    return np.ascontiguousarray(data, dtype=np.float32)
 
 
 def _tab_values(vals):
@@ -530,7 +361,10 @@ SAMPLING_INTEGRATORS = {"path": A.INTEGRATOR_PATH, "volpath": A.INTEGRATOR_VOLPA
 class SceneBuilder:
     """Accumulates plugin records; keeps every numpy buffer alive for the lifetime of the description."""
 
-    def __init__(self):
+    def __init__(self, mono=False, spectral=False):
+        """mono: the scene is built with the semantics of the *_mono variants (colours become their luminance, src/spectra/srgb.cpp);
+        spectral: with those of scalar_spectral (colours become spectrum records, collected in `spectra`).  Fixed for the builder's life."""
+        self.mono, self.spectral = bool(mono), bool(spectral)
         self.volumes, self.phases, self.media, self.bsdfs, self.shapes, self.emitters = [], [], [], [], [], []
         # the sensors in the order load() visits them: `sensor` is the first (mts_scene_desc.sensor, sensor 0), `extra_sensors` the others
         # (Scene hands them to mts_scene_add_sensor in this order); sensor_pixel_formats: each one's film "pixel_format", in that order
@@ -542,7 +376,6 @@ class SceneBuilder:
         self.instances = {}      # id -> (kind, index)
         self.info = {}
         self.spectra, self.spectrum_plugins = [], []
-        self.mono = self.spectral = False
         # traverse() (params.py): what each record exposes, written down while it is built.  nodes[(kind, index)] lists, in the order of
         # the reference plugin's traverse(), ("param", name, what, field) and ("object", name, node) entries; a colour is a node of its
         # own (`srgb` / `uniform` texture): ("colour", kind, index, field, where, emitter) in rgb / mono, ("spectrum", index) in spectral.
@@ -561,7 +394,176 @@ class SceneBuilder:
         self.cones = []          # and each cone
 
     def _colour_node(self, kind, index, field, where, spectrum=-1, emitter=False):
-        return ("spectrum", spectrum) if _SPECTRAL is not None else ("colour", kind, index, field, where, emitter)
+        return ("spectrum", spectrum) if self.spectral else ("colour", kind, index, field, where, emitter)
+
+    # ------------------------------------------------------------ conversions that depend on the variant (load and ParameterMap.update)
+    def _color(self, v, where, default=None, emitter=False):
+        """float | [r,g,b] | {"type":"rgb","value":..} | {"type":"spectrum"/"uniform","value":x} -> (r,g,b)."""
+        c = _color_rgb(v, where, default, emitter)
+        if self.mono and not (c[0] == c[1] == c[2]):
+            return (float(_luminance(c)),) * 3
+        return c
+
+    def _spectrum(self, v, where, default=None, emitter=False):
+        """Spectral variant: a colour parameter -> index of its spectrum record (mts_spectrum).
+        float -> `uniform` (Properties::texture, properties.h:275-296); {"type": "uniform" | "regular" | "d65"} -> the plugin of that
+        name (src/spectra/*.cpp; d65 expands to regular, d65.cpp:52-71); {"type": "spectrum", "value": c} -> uniform, or d65 scaled by c
+        inside an emitter (create_texture_from_spectrum, xml.cpp:1087-1111); a missing emitter spectrum is D65 (directional.cpp:49,
+        area.cpp:39, constant.cpp:33, point.cpp:47).  rgb colours need the sRGB upsampling model, whose data (ext/rgb2spec) is absent."""
+        if v is None:
+            v = {"type": "d65"} if (emitter and default is None) else default
+        rec = A.Spectrum()
+        rec.lambda_min, rec.lambda_max = WAVELENGTH_MIN, WAVELENGTH_MAX
+        if isinstance(v, dict):
+            p = Props(v, where)
+            t = p.type
+            if t == "spectrum":
+                val = _spectrum_pairs(v, where)                                 # inline pairs or spectrum_from_file (xml.cpp:823-851)
+                if p.has("filename"):
+                    p.get("filename")
+                if val is None:
+                    val = p.get("value", 1.0)
+                elif p.has("value"):
+                    p.get("value")
+                if isinstance(val, (list, tuple)):
+                    # create_texture_from_spectrum, xml.cpp:1113-1150 (spectral mode): values scaled by MTS_CIE_Y_NORMALIZATION inside an
+                    # emitter; `regular` when the wavelengths are equidistant (to math::Epsilon), `irregular` otherwise
+                    pairs = np.asarray(val, np.float64).reshape(-1, 2)
+                    f = np.float32
+                    wl = pairs[:, 0].astype(np.float32)
+                    vals = (pairs[:, 1].astype(np.float32) * (f(1.0 / 106.7502593994140625) if emitter else f(1.0))).astype(np.float32)
+                    dist = np.diff(wl)
+                    if (dist < 0).any():
+                        raise RuntimeError("Wavelengths must be specified in increasing order!")
+                    p.finish()
+                    if wl.size >= 2 and (np.abs(dist - dist[0]) <= 2.0 ** -24).all():
+                        return self._spectrum({"type": "regular", "lambda_min": float(wl[0]), "lambda_max": float(wl[-1]), "values": vals}, where)
+                    return self._spectrum({"type": "irregular", "wavelengths": wl, "values": vals}, where)
+                p.finish()
+                return self._spectrum({"type": "d65", "scale": float(val)} if emitter else {"type": "uniform", "value": float(val)}, where)
+            if t == "uniform":
+                rec.type = A.SPECTRUM_UNIFORM
+                rec.value = float(p.get("value", 1.0))
+                if p.has("lambda_min"):
+                    rec.lambda_min = max(float(p.get("lambda_min")), WAVELENGTH_MIN)
+                if p.has("lambda_max"):
+                    rec.lambda_max = min(float(p.get("lambda_max")), WAVELENGTH_MAX)
+                if not rec.lambda_min < rec.lambda_max:
+                    raise RuntimeError("UniformSpectrum: 'lambda_min' must be less than 'lambda_max'")
+            elif t in ("regular", "d65"):
+                rec.type = A.SPECTRUM_REGULAR
+                if t == "d65":
+                    from .spectra_data import D65, D65_NORMALIZATION
+                    f = np.float32
+                    scale = f(f(p.get("scale", 1.0)) * f(D65_NORMALIZATION))                  # d65.cpp:56-57: m_scale *= 1.f / 10568.f
+                    values = (np.asarray(D65, np.float32) * scale).astype(np.float32)         # :64-65
+                    rec.lambda_min, rec.lambda_max = 360.0, 830.0
+                else:
+                    if not (p.has("lambda_min") and p.has("lambda_max")):
+                        raise RuntimeError("Property \"lambda_min\" has not been specified!" if not p.has("lambda_min") else "Property \"lambda_max\" has not been specified!")
+                    rec.lambda_min, rec.lambda_max = float(p.get("lambda_min")), float(p.get("lambda_max"))
+                    vals = p.get("values")
+                    if isinstance(vals, str):
+                        vals = [float(x) for x in vals.replace(",", " ").split()]
+                    values = np.asarray(vals, np.float32).reshape(-1)
+                values = np.ascontiguousarray(values, np.float32)
+                self.keep.append(values)
+                rec.values = values.ctypes.data_as(A.fp)
+                rec.count = int(values.size)
+            elif t in ("irregular", "discrete"):
+                # spectra/irregular.cpp:33-63 (strings of comma-separated numbers, or arrays), spectra/discrete.cpp:45-100
+                def numbers(key, default=None):
+                    x = p.get(key, default)
+                    if x is None:
+                        raise RuntimeError("Property \"%s\" has not been specified!" % key)
+                    if isinstance(x, str):
+                        try:
+                            x = [float(tok) for tok in x.replace(",", " ").split()]
+                        except ValueError as e:
+                            raise RuntimeError("Could not parse floating point value '%s'" % str(e).split("'")[-2])
+                    return np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1), np.float32)
+                wl = numbers("wavelengths")
+                if t == "irregular":
+                    rec.type = A.SPECTRUM_IRREGULAR
+                    values = numbers("values")
+                    if values.size != wl.size:
+                        raise RuntimeError("IrregularSpectrum: 'wavelengths' and 'values' parameters must have the same size!")
+                    pmf = None
+                else:
+                    rec.type = A.SPECTRUM_DISCRETE
+                    values, pmf = numbers("values", "1"), numbers("pmf", "1")
+                    if values.size == 1:
+                        values = np.full(wl.size, values[0], np.float32)
+                    if pmf.size == 1:
+                        pmf = np.full(wl.size, pmf[0], np.float32)
+                    if values.size != wl.size:
+                        raise RuntimeError("DiscreteSpectrum: 'wavelengths' and 'values' parameters must have the same size!")
+                    if pmf.size != wl.size:
+                        raise RuntimeError("DiscreteSpectrum: 'wavelengths' and 'pmf' parameters must have the same size!")
+                    self.keep.append(pmf)
+                    rec.pmf = pmf.ctypes.data_as(A.fp)
+                self.keep.append(wl); self.keep.append(values)
+                rec.wavelengths = wl.ctypes.data_as(A.fp)
+                rec.values = values.ctypes.data_as(A.fp)
+                rec.count = int(wl.size)
+            elif t in ("rgb", "srgb", "srgb_d65"):
+                raise RuntimeError("rgb colours cannot be used in the spectral variant: the sRGB upsampling model needs the coefficient data of "
+                                   "ext/rgb2spec, absent here; give a 'uniform' or 'regular' spectrum instead (%s)" % where)
+            else:
+                raise RuntimeError("Unsupported spectrum plugin \"%s\" in %s" % (t, where))
+            p.finish()
+        else:
+            c = np.asarray(v, dtype=np.float32).reshape(-1)
+            if c.size != 1:
+                raise RuntimeError("Cannot interpret %r as a spectrum in %s (spectral variant)" % (v, where))
+            rec.type = A.SPECTRUM_UNIFORM
+            rec.value = float(c[0])
+        self.spectra.append(rec)
+        self.spectrum_plugins.append(v.get("type") if isinstance(v, dict) else "uniform")      # traverse(): the keys of that plugin
+        return len(self.spectra) - 1
+
+    def _grid_data(self, data):
+        """A grid's values as the description holds them: float32, C order, (nz, ny, nx, channels).  Returns (array, mono_max): under the
+        *_mono variants a colour grid becomes its luminance per voxel and keeps the file's maximum as its majorant (grid3d.cpp:157-179)."""
+        data = np.asarray(data, dtype=np.float32)
+        if data.ndim == 3:
+            data = data[..., None]
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        if data.ndim != 4:
+            raise RuntimeError("gridvolume: data must have shape (nz, ny, nx, channels)")
+        mono_max = None
+        if self.mono and data.shape[3] == 3:
+            # grid3d.cpp:178-179: *_mono variants return the luminance of the interpolated colour. Luminance is
+            # linear, so it is applied per voxel here; the majorant stays the file's maximum (volume metadata).
+            mono_max = float(data.max()) if data.size else 0.0
+            data = np.ascontiguousarray(_luminance(data)[..., None], dtype=np.float32)
+        return data, mono_max
+
+    def _bitmap_data(self, data):
+        """A bitmap's texels as the description holds them: float32, C order, (height, width, channels), channels 1 or 3.  Under the
+        *_mono variants rgb texels become their luminance (bitmap.cpp:278-279; luminance is linear, so it commutes with the filter)."""
+        data = np.asarray(data, dtype=np.float32)
+        if data.ndim == 2:
+            data = data[..., None]
+        if data.ndim != 3:
+            raise RuntimeError("bitmap: data must have shape (height, width) or (height, width, channels)")
+        if data.shape[2] not in (1, 3):
+            raise RuntimeError("Unsupported channel count: %d (expected 1 or 3)" % data.shape[2])                  # bitmap.cpp:196
+        if data.shape[0] < 2 or data.shape[1] < 2:
+            # bitmap.cpp:155-161 up-samples such an image with a tent filter, which this backend has not got
+            raise RuntimeError("bitmap: Image must be at least 2x2 pixels in size (got %dx%d; this backend does not up-sample)" % (data.shape[1], data.shape[0]))
+        if np.isnan(data).any():
+            raise RuntimeError("bitmap: data contains NaN")
+        if self.mono and data.shape[2] == 3:
+            data = _luminance(data)[..., None]
+        return np.ascontiguousarray(data, dtype=np.float32)
+
+    def _emitter_colour(self, e, v, where):
+        e.radiance_spectrum = -1
+        if self.spectral:
+            e.radiance_spectrum = self._spectrum(v, where, emitter=True)
+        else:
+            e.radiance[:] = self._color(v, where, default=1.0, emitter=True)
 
     # ------------------------------------------------------------ helpers
     def _register(self, d, kind, index):
@@ -601,14 +603,14 @@ class SceneBuilder:
                 rec.type = A.VOLUME_CONST
                 # constant3d.cpp: "color" texture; load_dict users pass "value" (xml.cpp spectrum shorthand)
                 val = p.get("value", p.get("color", 1.0))
-                if _SPECTRAL is not None:
-                    rec.value_spectrum = _spectrum(val, where)
+                if self.spectral:
+                    rec.value_spectrum = self._spectrum(val, where)
                 else:
-                    rec.value[:] = _color(val, where)
+                    rec.value[:] = self._color(val, where)
             else:
                 rec.type = A.VOLUME_GRID
                 if p.type == "gridvolume_spectral":                      # src/textures/gridvolume_spectral.cpp:84-135,186-190
-                    if _SPECTRAL is None:
+                    if not self.spectral:
                         raise RuntimeError("This volume data source can only be used with a spectral variant!")
                     rec.type = A.VOLUME_GRID_SPECTRAL
                     st = str(p.get("spectrum_type", "regular"))
@@ -630,7 +632,7 @@ class SceneBuilder:
                     rec.file_bbox_max[:] = (1.0, 1.0, 1.0)
                 else:
                     raise RuntimeError("gridvolume: property \"filename\" has not been specified!")
-                data, mono_max = _grid_data(data)
+                data, mono_max = self._grid_data(data)
                 self.keep.append(data)
                 self.grids[len(self.volumes)] = data                     # traverse(): "data"; mono_max follows an update unless "max_value" is set
                 self.grid_mono_max[len(self.volumes)] = mono_max is not None and not p.has("max_value")
@@ -658,10 +660,10 @@ class SceneBuilder:
         else:
             # float / rgb given where a volume is expected -> constvolume (properties.h:319-366)
             rec.type = A.VOLUME_CONST
-            if _SPECTRAL is not None:
-                rec.value_spectrum = _spectrum(v, where)
+            if self.spectral:
+                rec.value_spectrum = self._spectrum(v, where)
             else:
-                rec.value[:] = _color(v, where)
+                rec.value[:] = self._color(v, where)
         if rec.type == A.VOLUME_CONST:                                   # constant3d.cpp:39-41
             self.nodes[("volume", len(self.volumes))] = [("object", "color", self._colour_node("volume", len(self.volumes), "value", where, rec.value_spectrum))]
         else:                                                            # grid3d.cpp:366-369, gridvolume_spectral.cpp:388-392
@@ -773,7 +775,7 @@ class SceneBuilder:
         r = self._resolve_ref(d, "texture")
         if r is not None:
             return r
-        if _SPECTRAL is not None:
+        if self.spectral:
             raise RuntimeError("Textures are not supported in the spectral variant (\"%s\" in %s): rgb texels need the sRGB upsampling "
                                "model, whose data this backend has not got" % (d.get("type"), where))
         p = Props(d, where)
@@ -787,7 +789,7 @@ class SceneBuilder:
                 v = p.get(key, default)
                 if isinstance(v, dict) and v.get("type") in TEXTURE_PLUGINS + ("ref",):
                     raise RuntimeError("checkerboard: \"%s\" must be a constant (a float or rgb) in this backend, not a nested texture: %s" % (key, where))
-                getattr(rec, key)[:] = _color(v, where + "." + key)
+                getattr(rec, key)[:] = self._color(v, where + "." + key)
                 node.append(("object", key, ("colour", "texture", index, key, where + "." + key, False)))
         else:
             rec.type = A.TEXTURE_BITMAP
@@ -808,7 +810,7 @@ class SceneBuilder:
             if wm not in ("repeat", "mirror", "clamp"):
                 raise RuntimeError("Invalid wrap mode \"%s\", must be one of: \"repeat\", \"mirror\", or \"clamp\"!" % wm)   # bitmap.cpp:109-118
             p.get("raw", False)                                          # linear float data either way: nothing to undo
-            data = _bitmap_data(data)
+            data = self._bitmap_data(data)
             self.keep.append(data)
             self.bitmaps[index] = data
             rec.data = data.ctypes.data_as(A.fp)
@@ -830,19 +832,19 @@ class SceneBuilder:
         p = Props(d, where)
         rec = A.Bsdf()
         rec.spectrum[:] = [-1] * 6
-        spectral = _SPECTRAL is not None
+        spectral = self.spectral
         node = []
         textures = [-1] * 6                                              # per colour parameter: its texture record, -1 = the constant
         def colour(field, slot, key, default):                           # rgb triple, or (spectral variant) the index of the spectrum
             if self._is_texture(p.d.get(key)):                           # a bitmap / checkerboard; the record's own constant (what a reader that
                 textures[slot] = self.add_texture(p.get(key), where + "." + key)      # knows no textures sees) is the parameter's default
-                getattr(rec, field)[:] = _color(default, where) if default is not None else tuple(rec.rho_0)
+                getattr(rec, field)[:] = self._color(default, where) if default is not None else tuple(rec.rho_0)
                 node.append(("object", key, ("texture", textures[slot])))
                 return
             if spectral:
-                rec.spectrum[slot] = _spectrum(p.get(key), where + "." + key, default=default)
+                rec.spectrum[slot] = self._spectrum(p.get(key), where + "." + key, default=default)
             else:
-                getattr(rec, field)[:] = _color(p.get(key), where, default=default)
+                getattr(rec, field)[:] = self._color(p.get(key), where, default=default)
             node.append(("object", key, self._colour_node("bsdf", len(self.bsdfs), field, where, rec.spectrum[slot])))
         if p.type == "diffuse":
             rec.type = A.BSDF_DIFFUSE
@@ -970,7 +972,7 @@ class SceneBuilder:
                     if self._is_texture(p.d.get(key)):
                         raise RuntimeError("\"conductor\" %s: a texture on \"%s\" is not supported by this backend: give a float, an rgb colour "
                                            "or a uniform spectrum" % (where, key))
-                    c = _color(p.get(key), where + "." + key, default=default)
+                    c = self._color(p.get(key), where + "." + key, default=default)
                     if not all(math.isfinite(x) for x in c):
                         raise RuntimeError("\"conductor\" %s: \"%s\" must be finite" % (where, key))
                     getattr(rec, field)[:] = c
@@ -1201,14 +1203,6 @@ class SceneBuilder:
         return idx
 
     # ------------------------------------------------------------ emitters
-    @staticmethod
-    def _emitter_colour(e, v, where):
-        e.radiance_spectrum = -1
-        if _SPECTRAL is not None:
-            e.radiance_spectrum = _spectrum(v, where, emitter=True)
-        else:
-            e.radiance[:] = _color(v, where, default=1.0, emitter=True)
-
     def add_emitter(self, d, where):
         p = Props(d, where)
         e = A.Emitter()
@@ -1299,7 +1293,7 @@ class SceneBuilder:
                                "Found %s instead." % cf)
         if ff in ("rgbe", "pfm") and not (ff == "pfm" and pf == "luminance"):
             pf = "rgb"                                                     # hdrfilm.cpp:153-176
-        self._pixel_format = "luminance" if _MONO else pf                 # hdrfilm.cpp:122-128 (set_sensor files it under its sensor)
+        self._pixel_format = "luminance" if self.mono else pf                 # hdrfilm.cpp:122-128 (set_sensor files it under its sensor)
         fp_.get("high_quality_edges"); fp_.get("filename")
         rp = Props(fp_.get("rfilter", {"type": "gaussian"}), where + ".film.rfilter")
         s.rfilter_radius, s.rfilter_stddev = 0.5, 0.5
@@ -1467,11 +1461,11 @@ class SceneBuilder:
         if not p.has("srf"):
             return
         v = p.get("srf")
-        if _SPECTRAL is None:
+        if not self.spectral:
             return
         if isinstance(v, dict) and v.get("type") not in ("uniform", "discrete"):
             raise RuntimeError("srf: sample_spectrum is available for 'uniform' and 'discrete' spectra in this backend (%s)" % where)
-        s.srf = 1 + _spectrum(v, where + ".srf")
+        s.srf = 1 + self._spectrum(v, where + ".srf")
 
     # ------------------------------------------------------------ integrator
     def set_integrator(self, d, where):
@@ -1500,7 +1494,7 @@ class SceneBuilder:
 
     def _bin_integrator(self, d, p, where):
         # src/integrators/nbins.cpp:55-98, bins.cpp:23-85: wavelength-bin AOVs around one nested sampling integrator
-        if _SPECTRAL is None:
+        if not self.spectral:
             raise RuntimeError("This integrator can only be used with a spectral variant!")
         nested = self._nested_integrators(d)
         for k, v in nested:
@@ -1550,7 +1544,7 @@ class SceneBuilder:
 
     def _moment(self, d, p, where):
         # src/integrators/moment.cpp:27-58: six AOV channels around one nested sampling integrator -- its result as XYZ and the square
-        if _SPECTRAL is not None:
+        if self.spectral:
             raise RuntimeError("the moment integrator is not supported in the spectral variant by this backend")
         nested = self._nested_integrators(d)
         if not nested:
@@ -1657,6 +1651,7 @@ class SceneBuilder:
         desc.emitters, desc.emitter_count = arr(A.Emitter, self.emitters), len(self.emitters)
         desc.sensor = self.sensor
         desc.integrator = self.integrator
+        desc.integrator.monochrome, desc.integrator.spectral = int(self.mono), int(self.spectral)
         desc.spectra, desc.spectrum_count = arr(A.Spectrum, self.spectra), len(self.spectra)
         if self.textures:                                                # a scene without textures keeps the zeroed tail
             desc.textures, desc.texture_count = arr(A.Texture, self.textures), len(self.textures)
@@ -1675,17 +1670,5 @@ INTEGRATOR_PLUGINS = dict({name: SceneBuilder._sampling_integrator for name in S
 def build_scene_desc(d, mono=False, spectral=False):
     """Returns (SceneDesc, keepalive). The keepalive object owns every buffer the description points to.
     mono: build the scene with the semantics of the *_mono variants; spectral: with those of scalar_spectral."""
-    global _MONO, _SPECTRAL
-    b = SceneBuilder()
-    b.mono, b.spectral = bool(mono), bool(spectral)
-    with _BUILD_LOCK:                    # the variant of the scene being built is module state: one build at a time (threads may load scenes side by side)
-        _MONO = bool(mono)
-        _SPECTRAL = b if spectral else None
-        try:
-            desc = b.load(d)
-        finally:
-            _MONO = False
-            _SPECTRAL = None
-    desc.integrator.monochrome = int(bool(mono))
-    desc.integrator.spectral = int(bool(spectral))
-    return desc, b
+    b = SceneBuilder(mono, spectral)
+    return b.load(d), b

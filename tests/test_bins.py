@@ -18,12 +18,8 @@ def build(d):
 
 
 def integrator_only(d):
-    b = SD.SceneBuilder(); b.spectra = []
-    SD._SPECTRAL = b
-    try:
-        b.set_integrator(d, "integrator")
-    finally:
-        SD._SPECTRAL = None
+    b = SD.SceneBuilder(spectral=True)
+    b.set_integrator(d, "integrator")
     return b
 
 

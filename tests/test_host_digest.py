@@ -131,6 +131,18 @@ def test_sensitivity(digests, name):
     assert not (keeps & changed)
 
 
+def test_loader_cases_keep_their_digests_and_their_parameters():
+    """the `loader.*` cases of tools/host_digest.py -- textures, BSDF trees, specular BSDFs, instancing, the cone, several sensors, `moment`,
+    every spectrum plugin, colour grids, as rgb, mono and spectral -- build the host scenes, and list the traverse() keys and values, that
+    the commit before the variant moved into the SceneBuilder did (tests/golden/host_digest_before_loader_state.txt: those lines of that
+    commit's output, word for word)"""
+    import tools.host_digest as H
+    want = [line.rstrip("\n") for line in open(os.path.join(ROOT, "tests", "golden", "host_digest_before_loader_state.txt")) if line.strip()]
+    got = list(H.lines(H.loader_corpus()))
+    assert len(got) == len(want) == 46 and got == want
+    assert not any(name.startswith(("scenes.", "transport.")) for name, d, kw in H.loader_corpus())
+
+
 # ---------------------------------------------------------------- refusals, with the texts of the parent's source
 def library_refusal(case, edit=None, poke=None):
     """The message mts_debug_desc_digest comes back with: for a dictionary edited by `edit`, or a description hand-filled by `poke`"""

@@ -21,12 +21,8 @@ def wrap(d, name="nested", **outer):
 
 
 def integrator_only(d, spectral=False):
-    b = SD.SceneBuilder(); b.spectra = []
-    SD._SPECTRAL = b if spectral else None
-    try:
-        b.set_integrator(d, "integrator")
-    finally:
-        SD._SPECTRAL = None
+    b = SD.SceneBuilder(spectral=spectral)
+    b.set_integrator(d, "integrator")
     return b
 
 

@@ -1,5 +1,8 @@
 """Host logic: load_dict conventions and error behaviour (src/libcore/python/xml_v.cpp:100-272), transforms."""
+import ctypes as C
 import importlib
+import sys
+import threading
 
 import numpy as np
 import pytest
@@ -133,4 +136,102 @@ def test_mono_scene_description():
     assert np.ctypeslib.as_array(v.data, (8,)).tolist() == [float(lum)] * 8
     desc, keep = SD.build_scene_desc(d)
     assert desc.integrator.monochrome == 0 and desc.volumes[0].channels == 3
-    assert np.allclose(SD._color([0.2, 0.6, 1.0], "t"), (0.2, 0.6, 1.0))          # the switch does not leak
+    assert np.allclose(SD.SceneBuilder()._color([0.2, 0.6, 1.0], "t"), (0.2, 0.6, 1.0))          # the switch does not leak
+
+
+# ---------------------------------------------------------------- the variant is the builder's: builds inside builds, builds side by side
+RGB_GRID = np.stack([np.full((2, 2, 2), c, np.float32) for c in (0.2, 0.6, 1.0)], -1)
+VARIANTS = {"rgb": {}, "mono": {"mono": True}, "spectral": {"spectral": True}}
+
+
+def variant_scene(variant="rgb", grid=RGB_GRID):
+    """A 2 x 2 film, a cube whose heterogeneous interior has a 2 x 2 x 2 x 3 sigma_t grid and a colour albedo, a diffuse rectangle and a
+    directional emitter.  Every colour has three different channels, so a value converted under another variant's rules shows; the
+    spectral scene has `regular` spectra (and a gridvolume_spectral) where the other two have rgb colours."""
+    if variant == "spectral":
+        def colour(*c):
+            return {"type": "regular", "lambda_min": 400.0, "lambda_max": 700.0, "values": list(c)}
+        sigma_t = {"type": "gridvolume_spectral", "data": grid, "lambda_min": 400.0, "lambda_max": 700.0}
+    else:
+        def colour(*c):
+            return list(c)
+        sigma_t = {"type": "gridvolume", "data": grid}
+    return {"type": "scene", "integrator": {"type": "volpath"}, "sensor": {"type": "perspective", "film": dict(FILM, width=2, height=2)},
+            "box": {"type": "cube", "bsdf": {"type": "null"}, "interior": {"type": "heterogeneous", "sigma_t": sigma_t, "albedo": colour(0.2, 0.6, 1.0)}},
+            "floor": {"type": "rectangle", "bsdf": {"type": "diffuse", "reflectance": colour(0.2, 0.6, 1.0)}},
+            "sun": {"type": "directional", "irradiance": colour(1.0, 2.0, 3.0)}}
+
+
+class BuildsInside:
+    """An array-like whose __array__ first builds another scene (`variant`), then hands over its values: what a lazily evaluated grid
+    of an application that keeps scenes of several variants does to a build or an update in progress."""
+
+    def __init__(self, variant, data=RGB_GRID):
+        self.variant, self.data, self.inner = variant, data, []
+
+    def __array__(self, dtype=None, copy=None):
+        self.inner.append(SD.build_scene_desc(variant_scene(self.variant), **VARIANTS[self.variant]))
+        return self.data if dtype is None else self.data.astype(dtype, copy=False)
+
+
+def desc_digest(desc):
+    out = (C.c_uint64 * 8)()
+    A.check(A.lib().mts_debug_desc_digest(C.byref(desc), out))
+    return tuple(out)
+
+
+@pytest.mark.parametrize("outer,inner", [("mono", "rgb"), ("rgb", "mono"), ("mono", "spectral")])
+def test_a_build_inside_a_build_keeps_its_variant(outer, inner):
+    """the outer description is the one the same scene with a plain ndarray gives, whatever was built while its grid was converted"""
+    plain, keep_p = SD.build_scene_desc(variant_scene(outer), **VARIANTS[outer])
+    grid = BuildsInside(inner)
+    desc, keep = SD.build_scene_desc(variant_scene(outer, grid), **VARIANTS[outer])
+    assert len(grid.inner) == 1 and desc_digest(grid.inner[0][0]) == desc_digest(SD.build_scene_desc(variant_scene(inner), **VARIANTS[inner])[0])
+    assert desc.volumes[1].channels == plain.volumes[1].channels == (1 if outer == "mono" else 3)
+    assert list(desc.bsdfs[1].reflectance) == list(plain.bsdfs[1].reflectance) and list(desc.emitters[0].radiance) == list(plain.emitters[0].radiance)
+    assert desc_digest(desc) == desc_digest(plain) and all(desc_digest(desc))
+
+
+def test_builds_on_threads_keep_their_variants():
+    """Three threads build the rgb, the mono and the spectral scene 40 times each while a fourth, in the gpu_spectral variant, loads a
+    detached `nbins` integrator 40 times: every description has the digest of its variant's serial build, every integrator the AOV
+    names of a serial call.  The threads only build; the main thread asserts."""
+    nbins = {"type": "nbins", "wavelengths": "550", "integrator": {"type": "path"}}
+    runs, results, errors = 40, {}, []
+    barrier = threading.Barrier(4, timeout=60)                     # (a thread that failed before it got here breaks it for the others)
+
+    def detached(wait=True):
+        pkg.set_variant("gpu_spectral")                            # the variant is per thread
+        if wait:
+            barrier.wait()
+        return [pkg.load_dict(dict(nbins)).aov_names() for _ in range(runs if wait else 1)]
+
+    def builds(name):
+        barrier.wait()
+        return [SD.build_scene_desc(variant_scene(name), **VARIANTS[name]) for _ in range(runs)]
+
+    def run(key, work, *args):
+        try:
+            results[key] = work(*args)
+        except Exception as e:                                     # kept for the main thread
+            errors.append((key, e))
+
+    serial = {name: desc_digest(SD.build_scene_desc(variant_scene(name), **VARIANTS[name])[0]) for name in VARIANTS}
+    first = threading.Thread(target=run, args=("serial", detached, False))
+    first.start(); first.join()
+    threads = [threading.Thread(target=run, args=(name, builds, name)) for name in VARIANTS] + [threading.Thread(target=run, args=("nbins", detached))]
+    interval = sys.getswitchinterval()
+    sys.setswitchinterval(1e-5)
+    try:
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+    finally:
+        sys.setswitchinterval(interval)
+    assert not errors, errors
+    assert len(set(serial.values())) == 3 and results["serial"] == [["550", "550_pop"]]
+    for name in VARIANTS:
+        assert len(results[name]) == runs
+        assert [desc_digest(desc) for desc, keep in results[name]] == [serial[name]] * runs, name
+    assert results["nbins"] == results["serial"] * runs

@@ -452,3 +452,21 @@ def test_emitter_transform_is_frozen(L):
     b["sun"]["direction"] = a["sun"]["direction"]
     dc, kc = SD.build_scene_desc(b)
     assert plan(L, da, dc, [(A.OBJ_EMITTER, 0)])[0] == 0
+
+
+def test_an_update_keeps_its_variant_through_a_build_inside(L):
+    """One update() of a mono scene converts a grid whose __array__ builds an rgb scene, and after it a colour: the description is that
+    of a fresh mono load of the edited dictionary (the variant an update converts under is its builder's, not the last build's)."""
+    from tests.test_scene_dict import RGB_GRID, BuildsInside, desc_digest, variant_scene
+    new_grid = (RGB_GRID * np.float32(0.5)).astype(np.float32)
+    p, desc, keep = pmap(variant_scene("mono"), mono=True)
+    grid = BuildsInside("rgb", new_grid)
+    p["box.interior_medium.sigma_t.data"] = grid
+    p["floor.bsdf.reflectance.value"] = [0.9, 0.5, 0.1]
+    p.update()
+    assert len(grid.inner) == 1
+    edited = variant_scene("mono", new_grid)
+    edited["floor"]["bsdf"]["reflectance"] = [0.9, 0.5, 0.1]
+    fresh_desc, fresh_keep = SD.build_scene_desc(edited, mono=True)
+    assert desc.bsdfs[1].reflectance[0] == desc.bsdfs[1].reflectance[1] == fresh_desc.bsdfs[1].reflectance[0]
+    assert desc_digest(desc) == desc_digest(fresh_desc)
