@@ -134,17 +134,37 @@ DEV mts_float4 grid_gather_issue(const MTS_GLOBAL_AS float *p) {
 DEV void grid_gather_wait(mts_float4 &a, mts_float4 &b, mts_float4 &c, mts_float4 &d) {
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 }
-DEV void grid_fetch_pair(const MTS_GLOBAL_AS float *__restrict__ P, const GridCell &c, int nx, bool columns_equal, float &sigma_t, float &albedo) {
+// The same wait for a caller that has work of its own between the issue and the wait (step_fast): k0 .. k3 are results of that work,
+// which the wait takes as operands so that they are complete ahead of it -- without that the scheduler is free to sink the
+// arithmetic that forms them behind the wait, where it stands on the voxels' chain again.
+DEV void grid_gather_wait(mts_float4 &a, mts_float4 &b, mts_float4 &c, mts_float4 &d, float &k0, float &k1, float &k2, float &k3) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(k0), "+v"(k1), "+v"(k2), "+v"(k3));
+}
+// A lookup in two halves: the gathers go out (grid_pair_issue), the caller does what does not read a voxel, the one wait and the
+// trilinear blend follow (grid_pair_blend; grid_gather_wait, between them, is the caller's, which may pin values of its own to it).
+struct GridPairLoads { mts_float4 q00, q01, q10, q11; bool hi0, hi1; };
+DEV GridPairLoads grid_pair_issue(const MTS_GLOBAL_AS float *__restrict__ P, const GridCell &c, int nx, bool columns_equal) {
     const int xb = min(c.x0, nx - 2);
-    const bool hi0 = c.x0 != xb, hi1 = c.x1 != xb;           // take the second voxel of the pair
-    mts_float4 q00 = grid_gather_issue(P + 2 * (c.r00 + xb)), q01 = grid_gather_issue(P + 2 * (c.r01 + xb)), q10 = {0.f, 0.f, 0.f, 0.f}, q11 = {0.f, 0.f, 0.f, 0.f};
-    if (!columns_equal) { q10 = grid_gather_issue(P + 2 * (c.r10 + xb)); q11 = grid_gather_issue(P + 2 * (c.r11 + xb)); }
-    grid_gather_wait(q00, q01, q10, q11);
+    GridPairLoads g;
+    g.hi0 = c.x0 != xb; g.hi1 = c.x1 != xb;                    // take the second voxel of the pair
+    g.q00 = grid_gather_issue(P + 2 * (c.r00 + xb)); g.q01 = grid_gather_issue(P + 2 * (c.r01 + xb));
+    g.q10 = mts_float4{0.f, 0.f, 0.f, 0.f}; g.q11 = mts_float4{0.f, 0.f, 0.f, 0.f};
+    if (!columns_equal) { g.q10 = grid_gather_issue(P + 2 * (c.r10 + xb)); g.q11 = grid_gather_issue(P + 2 * (c.r11 + xb)); }
+    return g;
+}
+DEV void grid_pair_blend(GridPairLoads &g, const GridCell &c, bool columns_equal, float &sigma_t, float &albedo) {      // behind the wait
+    const bool hi0 = g.hi0, hi1 = g.hi1;
+    mts_float4 q00 = g.q00, q01 = g.q01, q10 = g.q10, q11 = g.q11;
     if (columns_equal) { q10 = q00; q11 = q01; }
     sigma_t = trilerp(hi0 ? q00.z : q00.x, hi1 ? q00.z : q00.x, hi0 ? q10.z : q10.x, hi1 ? q10.z : q10.x,
                       hi0 ? q01.z : q01.x, hi1 ? q01.z : q01.x, hi0 ? q11.z : q11.x, hi1 ? q11.z : q11.x, c.w0, c.w1);
     albedo = trilerp(hi0 ? q00.w : q00.y, hi1 ? q00.w : q00.y, hi0 ? q10.w : q10.y, hi1 ? q10.w : q10.y,
                      hi0 ? q01.w : q01.y, hi1 ? q01.w : q01.y, hi0 ? q11.w : q11.y, hi1 ? q11.w : q11.y, c.w0, c.w1);
+}
+DEV void grid_fetch_pair(const MTS_GLOBAL_AS float *__restrict__ P, const GridCell &c, int nx, bool columns_equal, float &sigma_t, float &albedo) {
+    GridPairLoads g = grid_pair_issue(P, c, nx, columns_equal);
+    grid_gather_wait(g.q00, g.q01, g.q10, g.q11);
+    grid_pair_blend(g, c, columns_equal, sigma_t, albedo);
 }
 
 template <bool COUNT>
@@ -778,8 +798,13 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
         Pcg32 rng = p.rng;
         const float u = rng.next_1d();                         // volpath.cpp:105 / :294 / :391
         bool rare = false, valid_mi = false, sample_emitters = false;
-        float mint = 0.f, mext = 0.f, rd = 0.f, mi_t = pm_inf(), sig_t = 0.f, sig_s = 0.f;
+        float mext = 0.f, rd = 0.f, mi_t = pm_inf(), sig_t = 0.f, sig_s = 0.f;
         F3 mi_p = f3s(0.f);
+        const float si_t = p.si.t;
+        const bool is_nee = !is_main && p.mode == M_NEE;
+        const float remaining_dist = is_nee ? p.ray.maxt : pm_inf();
+        float w_step = 0.f, u2 = 0.f, u_rr = 0.f, wa = p.wa;   // formed under the gathers, below
+        Pcg32 rng_head = rng;
         WATERFALL_BEGIN(p.medium, mu)
             const DMedium m = cload(sc.media + mu);            // medium_step, pair-grid arm
             {                                                  // a majorant without an invariant reciprocal (rd == 0) makes the lane rare by value: no branch splits the record's loads
@@ -787,7 +812,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
                 bool active = bbox_ray_intersect(m.aabb, p.ray, bmint, bmaxt);
                 active = active && (pm_isfinite(bmint) || pm_isfinite(bmaxt));
                 bmint = active ? bmint : 0.f; bmaxt = active ? bmaxt : pm_inf();
-                mint = pm_max(p.ray.mint, bmint);
+                const float mint = pm_max(p.ray.mint, bmint);
                 const float maxt = pm_min(p.ray.maxt, bmaxt);
                 mext = m.max_density; rd = m.inv_max_density;
                 bool ok_log, ok_div;
@@ -800,34 +825,41 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
                 const F3 at = f3(look ? mi_p.x : p.ray.o.x, look ? mi_p.y : p.ray.o.y, look ? mi_p.z : p.ray.o.z);
                 const int sx = m.pair_nx < 2 ? 2 : m.pair_nx;
                 const GridCell c = grid_cell_clamp(m.pair_w2l, m.pair_affine & 1, m.pair_nx, m.pair_ny, m.pair_nz, sx, at);
+                const bool columns_equal = (m.pair_affine & 2) != 0;
+                GridPairLoads g = grid_pair_issue(as_global(m.pair_grid), c, sx, columns_equal);
+                // In the shadow of the gathers: what the step does not need a voxel for -- the distance, its transmittance and
+                // sampling weight, the walk's bound, the main path's draws.  The waterfall's loop end is a block boundary that the
+                // scheduler does not cross, so this stands inside the body (mext is wave-uniform here); the wait takes the results as
+                // operands, which keeps the arithmetic ahead of it.
+                mi_t = si_t < mi_t ? pm_inf() : mi_t;          // volpath.cpp:112 / :300 / :397
+                float t = pm_min(mi_t, si_t);
+                if (!is_main) t = is_nee ? pm_min(remaining_dist, t) : t;
+                t = t - mint;
+                const bool surface_first = si_t < mi_t || mi_t > remaining_dist;
+                bool ok_exp;
+                float tr = pm_exp_flag(-t * mext, &ok_exp);
+                rare = rare || !ok_exp;
+                const float tr_pdf = surface_first ? tr : tr * mext;
+                w_step = tr_pdf > 0.f ? tr * pm_rcp(tr_pdf) : 0.f;
+                if constexpr (is_main) {
+                    u2 = rng.next_1d();                        // volpath.cpp:123 (drawn even when the medium was left)
+                    rng_head = rng;
+                    u_rr = rng_head.next_1d();                 // the roulette sample of the loop head, used after a null collision
+                    grid_gather_wait(g.q00, g.q01, g.q10, g.q11, w_step, mi_t, u2, u_rr);
+                } else {                                       // volpath.cpp:313-315 (a direct-light walk has no bound: both tests fail)
+                    wa = (mi_t > remaining_dist && mi_t != pm_inf()) ? p.wb : wa;
+                    mi_t = mi_t > remaining_dist ? pm_inf() : mi_t;
+                    grid_gather_wait(g.q00, g.q01, g.q10, g.q11, w_step, mi_t, wa, tr);
+                }
                 float st_raw, al_raw;
-                grid_fetch_pair(as_global(m.pair_grid), c, sx, (m.pair_affine & 2) != 0, st_raw, al_raw);
+                grid_pair_blend(g, c, columns_equal, st_raw, al_raw);
                 sig_t = m.scale * st_raw;
                 if (is_main) sig_s = sig_t * al_raw;
                 sample_emitters = m.sample_emitters != 0;
             }
         WATERFALL_END
-        const float si_t = p.si.t;
-        mi_t = si_t < mi_t ? pm_inf() : mi_t;                  // volpath.cpp:112 / :300 / :397
-        const bool is_nee = !is_main && p.mode == M_NEE;
-        const float remaining_dist = is_nee ? p.ray.maxt : pm_inf();
         Spec weight = is_main ? p.thr : p.trans;
-        float t = pm_min(mi_t, si_t);
-        if (!is_main) t = is_nee ? pm_min(remaining_dist, t) : t;
-        t = t - mint;
-        const bool surface_first = si_t < mi_t || mi_t > remaining_dist;
-        bool ok_exp;
-        const float tr = pm_exp_flag(-t * mext, &ok_exp);
-        rare = rare || !ok_exp;
-        const float tr_pdf = surface_first ? tr : tr * mext;
-        weight = weight * (tr_pdf > 0.f ? tr * pm_rcp(tr_pdf) : 0.f);
-        float u2 = 0.f;
-        if (is_main) u2 = rng.next_1d();                       // volpath.cpp:123 (drawn even when the medium was left)
-        float wa = p.wa;
-        if (!is_main) {                                        // volpath.cpp:313-315 (a direct-light walk has no bound: both tests fail)
-            wa = (mi_t > remaining_dist && mi_t != pm_inf()) ? p.wb : wa;
-            mi_t = mi_t > remaining_dist ? pm_inf() : mi_t;
-        }
+        weight = weight * w_step;
         const bool valid = mi_t != pm_inf();                   // false: escaped_medium, the surface part of this iteration
         const float sigma_n = mext - sig_t;
         int cls;
@@ -844,8 +876,7 @@ struct VolpathMachine : RingMachine<VolpathMachine<COUNT, MOMENT_, GEOM_, TEX_>,
             bool alive = (p.flags & FL_ALIVE) && any_nonzero(thr);
             const float q = pm_min(hmax(thr) * (p.eta * p.eta), .95f);
             const bool perform_rr = p.depth > rr_depth;
-            Pcg32 rng_head = rng;
-            alive = alive && (rng_head.next_1d() < q || !perform_rr);
+            alive = alive && (u_rr < q || !perform_rr);
             const Spec thr_rr = thr * pm_rcp(q);
             const bool null_c = valid && !real, rr_c = null_c && perform_rr;
             const bool ends = !alive || p.depth >= max_depth;

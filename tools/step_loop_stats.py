@@ -1,6 +1,6 @@
 """Static figures of the tracking step: the two in-place repeat loops of wg_block (volpath_flat.h) in one device unit's assembly.
 
-    python tools/step_loop_stats.py [unit.hip] [--kernel SUBSTRING] [--source DIR] [--asm FILE] [--keep FILE] [--histogram] [--trips]
+    python tools/step_loop_stats.py [unit.hip] [--kernel SUBSTRING] [--source DIR] [--asm FILE] [--keep FILE] [--histogram] [--trips] [--chain]
 
 Compiles the unit (default kernels_lean_a.hip) for the device only, to assembly, with the product flags of _buildid.py plus line
 tables (about 30 s; the added flags do not change the code), and finds the loops of the chosen kernel (default: the flagship,
@@ -21,6 +21,9 @@ needs more than a class: a mnemonic with `branch` in it ends a block and names a
 --trips adds, for the common path of each loop, the memory instructions (global_load*, s_load*, ds_read*) and the s_waitcnt between them
 in control-flow order from the loop head, and says whether (a) the grid gathers, (b) the medium record's scalar loads go out in one
 round trip each, and (c) the logarithm's table read is issued ahead of the record (trips(), tests/test_step_round_trips.py).
+
+--chain adds what of the step's table reads (ds_read*) and fp64 arithmetic (*_f64) stands behind the wait for the grid gathers, on the
+voxels' chain (chain(), tests/test_step_chain.py).
 
 The anchors are literal texts of source lines of volpath_flat.h (comments at those lines say so) and, for --trips, of cload's copy
 loop in integrator_dev.h: a reworded line makes the tool stop with a message that names the anchor.
@@ -348,6 +351,58 @@ def render_trips(res):
     return "\n".join(rows)
 
 
+def chain(asm_path, kernel=DEFAULT_KERNEL):
+    """-> {"B_MED": {"behind": [...], "reads": {"ds_read_b128": n, "ds_read_b64": n}}, "B_MEDW": {...}}: what of the step's table reads
+    and fp64 arithmetic (the logarithm, the exponential) stands on the voxels' chain.
+
+      behind  the instructions of the common path that are a ds_read* or carry _f64 in the mnemonic and lie on some path from the
+              gathers' wait -- the first s_waitcnt that names vmcnt behind a global_load_dwordx4 -- to the loop's back edge
+      reads   how many ds_read_b128 (the logarithm's table) and ds_read_b64 (the exponential's) the common path holds
+
+    Paths run inside the common path and stop at a back edge, as in trips()."""
+    insts, blocks, succ, dominates, found = find_loops(asm_path, kernel)
+    res = {}
+    for name, (body, common) in found.items():
+        head = next(b for b in common if all(dominates(b, x) for x in common))
+        fwd = {b: [s for s in succ[b] if s in common and not dominates(s, b)] for b in common}
+        order, seen, stack = [], {head}, [(head, iter(sorted(fwd[head], reverse=True)))]
+        while stack:                                         # reverse postorder: every block after all its predecessors
+            b, it = stack[-1]
+            nxt = next((s for s in it if s not in seen), None)
+            if nxt is None:
+                order.append(b); stack.pop()
+            else:
+                seen.add(nxt); stack.append((nxt, iter(sorted(fwd[nxt], reverse=True))))
+        order.reverse()
+        state, behind = {b: set() for b in order}, []        # states: 0 no gather yet, 1 a gather in flight, 2 behind the gathers' wait
+        state[head] = {0}
+        for b in order:
+            cur = set(state[b])
+            for k in range(blocks[b][0], blocks[b][1] + 1):
+                mn, ops, loc = insts[k]
+                if mn == "global_load_dwordx4":
+                    cur = {1 if s == 0 else s for s in cur}
+                elif mn == "s_waitcnt" and "vmcnt" in ops:
+                    cur = {2 if s == 1 else s for s in cur}
+                elif 2 in cur and (mn.startswith("ds_read") or "_f64" in mn):
+                    behind.append("%s:%d %s %s" % ((loc or ("-", 0)) + (mn, ops)))
+            for s in fwd[b]:
+                state[s] |= cur
+        mns = [insts[k][0] for b in common for k in range(blocks[b][0], blocks[b][1] + 1)]
+        res[name] = {"behind": behind, "reads": {m: mns.count(m) for m in ("ds_read_b128", "ds_read_b64")}}
+    return res
+
+
+def render_chain(res):
+    rows = []
+    for name in ("B_MED", "B_MEDW"):
+        r = res[name]
+        rows.append("%s, common path: %d ds_read_b128, %d ds_read_b64; table reads and fp64 arithmetic behind the gathers' wait: %s"
+                    % (name, r["reads"]["ds_read_b128"], r["reads"]["ds_read_b64"], "none" if not r["behind"] else len(r["behind"])))
+        rows += ["  " + l for l in r["behind"]]
+    return "\n".join(rows)
+
+
 @contextlib.contextmanager
 def compiled(unit="kernels_lean_a.hip", keep=None):
     """the unit's assembly, compiled now: at `keep`, or in a temporary directory that lives as long as the block"""
@@ -385,10 +440,12 @@ if __name__ == "__main__":
         return None
     kernel, asm, keep = opt("--kernel") or DEFAULT_KERNEL, opt("--asm"), opt("--keep")
     SOURCE_DIR = opt("--source") or SOURCE_DIR
-    histogram, want_trips = "--histogram" in argv, "--trips" in argv
-    argv = [a for a in argv if a not in ("--histogram", "--trips")]
+    histogram, want_trips, want_chain = "--histogram" in argv, "--trips" in argv, "--chain" in argv
+    argv = [a for a in argv if a not in ("--histogram", "--trips", "--chain")]
     unit = argv[0] if argv else "kernels_lean_a.hip"
     with (contextlib.nullcontext(asm) if asm else compiled(unit, keep)) as asm:
         print(render(step_loops(asm, kernel), unit, kernel, histogram))
         if want_trips:
             print(render_trips(trips(asm, kernel)))
+        if want_chain:
+            print(render_chain(chain(asm, kernel)))
